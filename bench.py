@@ -10,11 +10,17 @@ Adam, on synthetic 3x256x256 batches already resident in HBM (BASELINE.json conf
 Other single-GPU legs: `--ssim` (configs[2] as written: SSIM reconstruction head + focal) and
 `--model unet --precision fp32 --batch 16` (configs[1]: UNet(3,1) seg-only, focal on sigmoid(logits)).
 
-Timing: W warm-up steps, then `--blocks` (default 5) timed blocks of EXACTLY K steps, each bracketed by a barrier +
+Timing: W warm-up steps, then `--blocks` timed blocks of EXACTLY K steps, each bracketed by a barrier +
 torch.cuda.synchronize() on both sides and reduced with MAX over ranks.  `value` / `ms_per_step` are those of the
 MEDIAN block (boxes of the pool differ by up to 10 %, blocks on one box by ~1 %); `ms_per_step_p10/p90/blocks` say so.
+A plain run times one block, so K is the number of timed steps; `--full` defaults to 5 blocks.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus:
+`--dump-outputs DIR` writes what the timed path computed in its last timed step (losses, reconstruction, anomaly map,
+the updated parameters and BatchNorm buffers, the gradients) as DIR/<name>.npy, float32 / float64, under 64 MB in all:
+an array larger than its cap is written as a fixed, seeded sample (drawn with replacement) of its flattened elements.
+Inputs and weights are seeded, so two builds can be compared output for output.
+
+Prints ONE JSON line (rank 0) with the driver's contract.  `--full` adds the measurements that take runs of their own:
   roofline     -- the dominant KERNEL (most event time among the MFMA kernels), timed live with hipEvents on its own
                   stream (libunet_hip's per-launch brackets) against the dense MFMA peak of the dtype; `traffic` =
                   HBM bytes per launch of that kernel from the committed PMC passes of this same command
@@ -55,7 +61,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the extra measurements: 5 timed blocks (p10/p90), roofline steps, CPU baseline")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="timed blocks of --steps steps each, so B blocks time B*K steps (median block reported); "
+                         "default 1, with --full 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (weak scaling); default 32 (unet: 16)")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--height", type=int, default=None, help="non-square frames (BASELINE configs[4]: --height 1408 --width 512)")
@@ -64,10 +76,13 @@ def parse():
     ap.add_argument("--precision", default=None, choices=["bf16", "fp32"], help="default bf16 (unet: fp32, configs[1])")
     ap.add_argument("--ssim", action="store_true", help="SSIM reconstruction head instead of MSE (configs[2] --use_ssim)")
     ap.add_argument("--mask", default="bernoulli", choices=["bernoulli", "zeros"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the two event-bracketed extra steps (PMC passes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="(--full) skip the two event-bracketed extra steps (PMC passes)")
     ap.add_argument("--cpu-batch", type=int, default=4)
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
     if args.batch is None:
         args.batch = 32 if args.model == "anomaly_unet" else 16
     if args.precision is None:
@@ -115,6 +130,33 @@ def cpu_baseline(size, batch, model):
     return {"value": round(batch * steps / dt, 3), "unit": "images/sec", "cores": cores, "kind": "port",
             "sample": f"{steps} timed steps ({dt:.1f} s, after 1 warm-up) of the oracle train step, {name} "
                       f"{size}x{size} bs={batch} fp32, torch {torch.__version__} CPU"}
+
+
+# element caps per dumped array: 15.25 M float32 elements (61 MB) in all at most; the reconstruction and anomaly map of
+# the default configuration (32x3x256x256, 32x1x256x256) fit whole
+DUMP_CAPS = {"recon": 6_500_000, "anomaly_map": 2_500_000, "params": 3_000_000, "grads": 3_000_000,
+             "bn_buffers": 250_000}
+
+
+def dump_outputs(out_dir, tensors):
+    """Write name -> tensor as out_dir/<name>.npy: 0-d tensors as float64, the rest as float32, whole when within
+    DUMP_CAPS[name] elements, else the elements at DUMP_CAPS[name] flat indices drawn with replacement (an index may
+    repeat) from a fixed, name-dependent seed, in ascending order."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.dim() == 0:
+            a = np.asarray(float(t), dtype=np.float64)
+        else:
+            cap = DUMP_CAPS[name]
+            if t.numel() > cap:
+                g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+                idx = torch.randint(t.numel(), (cap,), generator=g).sort().values
+                t = t.reshape(-1)[idx.to(t.device)]
+            a = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -173,7 +215,7 @@ def main():
         if world > 1:
             net.finish_gradients()
         optimizer.step()
-        return losses
+        return recon, amap, losses
 
     def fence():
         if world > 1:
@@ -188,7 +230,7 @@ def main():
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            losses = step()
+            recon, amap, losses = step()
         fence()
         elapsed = time.perf_counter() - t0
         if world > 1:
@@ -197,6 +239,15 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t)
         block_s.append(elapsed)
+    if args.dump_outputs and rank == 0:
+        # before the --full roofline steps, which train on; zero_grad(set_to_none) leaves the last step's own grads
+        params = list(core.parameters())
+        dump_outputs(args.dump_outputs, {
+            **losses, "recon": recon, "anomaly_map": amap,
+            "params": torch.cat([p.detach().reshape(-1).float() for p in params]),
+            "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                for p in params]),
+            "bn_buffers": torch.cat([b.detach().reshape(-1).float() for b in core.buffers() if b.is_floating_point()])})
     loss_val = float(losses["total_loss"].detach())
     ordered = sorted(block_s)
     elapsed = ordered[len(ordered) // 2] if len(ordered) % 2 else 0.5 * (ordered[len(ordered) // 2 - 1] + ordered[len(ordered) // 2])
@@ -208,7 +259,7 @@ def main():
     roof = None
     default_cfg = (args.model == "anomaly_unet" and args.precision == "bf16" and args.batch == 32 and args.size == 256 and not args.height and not args.width
                    and not args.ssim and args.mask == "bernoulli")
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # (every rank runs the two extra steps -- they contain the gradient collectives; only rank 0 brackets them)
         # The two decoder branches normally run on two HIP streams; for these two steps they run on ONE stream so
         # that an event bracket times its kernel alone (concurrent kernels would inflate each other's brackets).
@@ -320,7 +371,7 @@ def main():
             "final_loss": round(loss_val, 5),
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(s, args.cpu_batch, args.model)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -336,7 +336,7 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     env = dict(os.environ, UNET_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--batch", "2", "--size", "64"]
+           "--warmup", "1", "--batch", "2", "--size", "64", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -344,6 +344,7 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["config"]["parallelism"] == "dp2" and rec["config"]["global_batch"] == 4
     assert rec["scaling"] == "weak" and rec["value"] > 0 and "cpu_baseline" not in rec
+    assert rec["blocks"] == 5 and rec["roofline"] is not None
 
 
 def test_nonsquare_config_shapes():
