@@ -108,13 +108,49 @@ int32_t unet_pack_weight(const float* w, void* out, int32_t c_out, int32_t c_in,
                          int32_t k, int32_t mode, int32_t dtype, void* stream);
 
 /* All of a model's weights in ONE launch (after each optimiser step): `descs` is a DEVICE array of n
- * descriptors (the fields of unet_pack_weight; dtype is per call). */
+ * descriptors (the fields of unet_pack_weight; dtype is per call).  `reserved` of a 3x3 conv descriptor is the segment
+ * map of its input channels (unet_pack_weight_seg's `split`); 0 = the contiguous layout. */
 typedef struct unet_pack_desc {
   const float* w;
   void* out;
   int32_t c_out, c_in, rows, k, mode, reserved;
 } unet_pack_desc;
 int32_t unet_pack_weights_batched(const unet_pack_desc* descs, int32_t n, int32_t dtype, void* stream);
+
+/* ---- channel widths that are not multiples of 64 (widths.hip) ----------------------------------------------------
+ * DoubleConv / Down / Up / OutConv with any widths (src/model.py:9-75): a layer of c channels runs as the layer of
+ * cp = pad64(c) channels with zero weight rows / columns and zero BatchNorm gamma / beta in the pad lanes, so every
+ * activation and gradient keeps exactly 0 in its pad lanes through the existing kernels.
+ *
+ * The 3x3 conv weight of an Up block whose skip (source 0) has split = c0 % 64 != 0 channels: packed input column q
+ * holds parameter column q for q < c0, zero for c0 <= q < pad64(c0) and parameter column q - pad64(c0) + c0 after that
+ * (source 1 starts at pad64(c0)).  mode: UNET_PACK_CONV_FWD or UNET_PACK_CONV_DGRAD; split = 0 is unet_pack_weight. */
+int32_t unet_pack_weight_seg(const float* w, void* out, int32_t c_out, int32_t c_in, int32_t rows, int32_t k,
+                             int32_t mode, int32_t split, int32_t dtype, void* stream);
+/* unet_pack_conv_weight_folded through the same segment map. */
+int32_t unet_pack_conv_weight_folded_seg(const float* w, const float* scale, void* out, int32_t c_out, int32_t c_in,
+                                         int32_t rows, int32_t k, int32_t split, int32_t dtype, void* stream);
+
+/* fp32 tensor [rows][cols][inner] (the parameter's shape: a BatchNorm vector is [1][c][1], a conv weight
+ * [co][ci][9], a transposed-conv weight [ci][co][4], a head weight [co][ci][1]) <-> its padded form
+ * [prows][pcols][inner], columns through the segment map `split` (0 = contiguous).  UNET_REMAP_PAD writes the whole
+ * padded tensor (zeros outside the logical one); UNET_REMAP_UNPAD writes the logical tensor from the padded one.
+ * descs: HOST array of n descriptors, UNET_REMAP_MAX per launch. */
+enum unet_remap_op { UNET_REMAP_PAD = 0, UNET_REMAP_UNPAD = 1 };
+#define UNET_REMAP_MAX 8
+typedef struct unet_remap_desc {
+  const float* src;
+  float* dst;
+  int32_t rows, cols, inner;
+  int32_t prows, pcols;
+  int32_t split, op, reserved;
+} unet_remap_desc;
+int32_t unet_remap_batched(const unet_remap_desc* descs, int32_t n, void* stream);
+
+/* The gradient w.r.t. a narrow block's logical-shape output -> dense NHWC [n][h][w][c_pad] in `dtype`, 0 in the pad
+ * lanes.  src: [n][c][h][w] of src_dtype (UNET_F32 / UNET_BF16) with element strides strides[4] (HOST, NCHW order). */
+int32_t unet_widen_channels(const void* src, int32_t src_dtype, const int64_t* strides, int32_t n, int32_t c, int32_t h,
+                            int32_t w, void* dst, int32_t c_pad, int32_t dtype, void* stream);
 
 /* ---- 3x3 convolution, pad 1, stride 1, no bias (nn.Conv2d at src/model.py:14,17) ------ */
 /* y = conv(concat(src[0], src[1])) as an implicit GEMM on MFMA.  Output channels below
@@ -123,7 +159,8 @@ int32_t unet_pack_weights_batched(const unet_pack_desc* descs, int32_t n, int32_
  * dX = conv(dY, flipped W^T).  `accumulate` is a bit mask: bit 0 -> dst[0] += result, bit 1 -> dst[1] += result
  * (gradient fan-in of the skip connections: the three consumers of a skip tensor add into one buffer).
  * Requires: channel counts of each src multiples of 64 (or a single src of 8/16 for the
- * image layer), c_out multiple of 64. */
+ * image layer), c_out multiple of 64.  Narrower layers (any width c) run as the pad64(c) layer with zero pad lanes
+ * (widths section below), doing pad64(c)/c times the useful MFMA work: a 32-wide layer runs a 64-wide GEMM. */
 int32_t unet_conv3x3(int32_t dtype, int32_t n, int32_t h, int32_t w, const unet_view src[2],
                      const void* w_packed, int32_t c_out, const unet_view dst[2], int32_t dst_split,
                      int32_t accumulate, int32_t kclass, void* stream);

@@ -29,6 +29,16 @@ class View(C.Structure):
 
 
 View2 = View * 2
+
+
+class RemapDesc(C.Structure):
+    """struct unet_remap_desc"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("inner", C.c_int32), ("prows", C.c_int32), ("pcols", C.c_int32), ("split", C.c_int32),
+                ("op", C.c_int32), ("reserved", C.c_int32)]
+
+
+REMAP_PAD, REMAP_UNPAD = 0, 1
 _i, _l, _f, _p, _z, _d = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes): every symbol include/unet_hip.h declares
@@ -47,6 +57,10 @@ SIGNATURES = {
     "unet_nhwc_to_nchw": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "unet_pack_weight": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "unet_pack_weights_batched": (_i, [_p, _i, _i, _p]),
+    "unet_pack_weight_seg": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "unet_pack_conv_weight_folded_seg": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "unet_remap_batched": (_i, [_p, _i, _p]),
+    "unet_widen_channels": (_i, [_p, _i, _p, _i, _i, _i, _i, _p, _i, _i, _p]),
     "unet_conv3x3": (_i, [_i, _i, _i, _i, C.POINTER(View), _p, _i, C.POINTER(View), _i, _i, _i, _p]),
     "unet_pack_conv_weight_folded": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "unet_conv3x3_bias_relu": (_i, [_i, _i, _i, _i, C.POINTER(View), _p, _i, _p, _p, _i, _p]),

@@ -126,3 +126,30 @@ template <> struct Vec<bf16_t> {
 
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- segment map of a two-source (skip | up-sampled) convolution input with a narrow first source (widths.hip) ------
+// Packed column q of the padded input -> column of the parameter's input axis, or -1 (a zero column).  split = logical
+// channels of source 0; source 1 starts at pad64(split).  split == 0: contiguous, the columns >= c are zero.
+__host__ __device__ static inline int unet_seg_col(int q, int split, int c) {
+  if (split > 0 && q >= split) {
+    const int p0 = (split + 63) / 64 * 64;
+    if (q < p0) return -1;
+    q = q - p0 + split;
+  }
+  return q < c ? q : -1;
+}
+
+// element i of a 3x3 conv weight packed (UNET_PACK_CONV_FWD [9][rows][k] / UNET_PACK_CONV_DGRAD [9 flipped][rows][k])
+// through the segment map `split` of its input-channel axis; scale (may be NULL): BatchNorm fold per output channel
+__device__ static inline float unet_pack_seg_value(const float* __restrict__ w, int Co, int Ci, int rows, int K, int mode,
+                                                   int split, long long i, const float* __restrict__ scale) {
+  const int b = (int)(i % K);
+  const long long t = i / K;
+  const int a = (int)(t % rows), tap = (int)(t / rows);
+  if (mode == UNET_PACK_CONV_FWD) {                // a = co, b = packed input column
+    const int ci = unet_seg_col(b, split, Ci);
+    return (a < Co && ci >= 0) ? w[((long long)a * Ci + ci) * 9 + tap] * (scale ? scale[a] : 1.f) : 0.f;
+  }
+  const int ci = unet_seg_col(a, split, Ci);       // a = packed input row, b = co
+  return (b < Co && ci >= 0) ? w[((long long)b * Ci + ci) * 9 + (8 - tap)] : 0.f;
+}

@@ -90,6 +90,14 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(const unet_pa
   __shared__ float tile[32 * 289];                 // (>= 64 * 8 * 9 + 64 of the single-layout path)
   const unet_pack_desc d = descs[blockIdx.y];
   const int mode = d.mode;
+  if (d.reserved > 0 && mode <= UNET_PACK_CONV_DGRAD) {
+    // the input channels follow the segment map of a narrow skip (widths.hip): a plain element loop
+    const long long total = 9LL * d.rows * d.k;
+    T* __restrict__ out = reinterpret_cast<T*>(d.out);
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
+      out[i] = ET<T>::from_f(unet_pack_seg_value(d.w, d.c_out, d.c_in, d.rows, d.k, mode, d.reserved, i, nullptr));
+    return;
+  }
   // PAIRED fast path (bf16, 3x3 conv, unpadded dims that are multiples of 32): the forward layout [tap][co][ci] and the
   // data-gradient layout [8 - tap][ci][co] of one weight are consecutive descriptors; the forward descriptor's blocks
   // write BOTH from one 32 (co) x 32 (ci) x 9 tile -- the fp32 parameter is read once instead of twice (346 -> 173 MB of

@@ -53,7 +53,7 @@ class _HipBlock(nn.Module):
 
 
 def _conv_bn_relu(conv: nn.Conv2d, bn: nn.BatchNorm2d, x, x_up, first: bool = False, in_link=None, out_link=None,
-                  head=None, pool=False):
+                  head=None, pool=False, split=0):
     """One conv3x3 -> BatchNorm2d -> ReLU third of DoubleConv.  Batch vs running statistics follow ``bn.training``
     (the holder module itself, so a frozen ``bn.eval()`` inside a training model is honoured like in the reference's
     nn.Sequential); ``bn.momentum is None`` is torch's cumulative moving average (factor 1 / num_batches_tracked).
@@ -75,7 +75,7 @@ def _conv_bn_relu(conv: nn.Conv2d, bn: nn.BatchNorm2d, x, x_up, first: bool = Fa
         fold = (not track) and not torch.is_grad_enabled()
         hw, hb, hs = (head[0].conv.weight, head[0].conv.bias, head[1]) if head is not None else (None, None, False)
         out = ops.ConvBnRelu.apply(x, x_up, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                   track, momentum, fold, in_link, out_link, hw, hb, hs, pool)
+                                   track, momentum, fold, in_link, out_link, hw, hb, hs, pool, split)
     if training and bn.num_batches_tracked is not None:
         if _deferred_counters is not None:
             _deferred_counters.append(bn.num_batches_tracked)
@@ -106,14 +106,18 @@ class _BatchedCounters:
 
 
 class DoubleConv(_HipBlock):
-    """(conv3x3 => BatchNorm => ReLU) * 2 on MFMA implicit-GEMM kernels."""
+    """(conv3x3 => BatchNorm => ReLU) * 2 on MFMA implicit-GEMM kernels.
+
+    Any widths: a layer whose channel count c is not a multiple of 64 runs as the pad64(c)-wide layer with zero pad
+    lanes (ops: padded weights and BatchNorm parameters, gradients and running statistics mapped back to the
+    parameters' shapes); the result is then a logical-shape [N, c, H, W] view of the padded activation, which the next
+    block takes back without a copy."""
+
+    skip_split = 0          # (set by Up) logical width of a narrow skip in front of the up-sampled tensor
 
     def __init__(self, in_channels, out_channels, mid_channels=None, precision=None):
         super().__init__()
         mid_channels = mid_channels or out_channels
-        if mid_channels % 64 or out_channels % 64:
-            raise ValueError("the gfx950 kernels need output channel counts that are multiples of 64 "
-                             f"(got {mid_channels}, {out_channels})")
         self.precision = precision
         self.double_conv = nn.Sequential(
             nn.Conv2d(in_channels, mid_channels, kernel_size=3, padding=1, bias=False),
@@ -124,7 +128,7 @@ class DoubleConv(_HipBlock):
             nn.ReLU(inplace=True),
         )
 
-    def forward(self, x, x_up=None, head=None, pool=False, out_link=None):
+    def forward(self, x, x_up=None, head=None, pool=False, out_link=None, split=0):
         """``out_link`` (internal, optional): ops.BnLink to the ONE consumer of the result (the transposed convolution of
         the next Up block), which then produces this block's last ReLU mask / BatchNorm-backward sums in its data gradient.
         ``x_up`` (internal, optional): second channel block of the input, i.e. the up-sampled
@@ -132,7 +136,8 @@ class DoubleConv(_HipBlock):
         ``head`` (internal, optional): (OutConv, sigmoid) applied to the result -- in training mode the 1x1 head
         is fused with the last BatchNorm + ReLU (the activation is never written).
         ``pool`` (internal, optional): also return ``max_pool2d(result, 2)`` -- in training mode the pool is fused with
-        the last BatchNorm + ReLU (forward) and with its backward (see ops.ConvBnRelu)."""
+        the last BatchNorm + ReLU (forward) and with its backward (see ops.ConvBnRelu).
+        ``split`` (internal, optional): logical channels of ``x`` when it is a narrow skip next to ``x_up``."""
         seq = self.double_conv
         # the intermediate activation has exactly one consumer (the second convolution): its ReLU mask and
         # BatchNorm-backward sums are produced by that convolution's data-gradient kernel (ops.BnLink)
@@ -144,15 +149,22 @@ class DoubleConv(_HipBlock):
             x = ops.to_operator_layout(x, self.compute_dtype)
             if x_up is not None:
                 x_up = ops.to_operator_layout(x_up, self.compute_dtype)
-            a = _conv_bn_relu(seq[0], seq[1], x, x_up, out_link=link)
+            a = _conv_bn_relu(seq[0], seq[1], x, x_up, out_link=link, split=split)
+        c_out = seq[3].out_channels
         fuse_pool = pool and ops.FUSE_BN_POOL and seq[4].training and a.shape[2] >= 2 and a.shape[3] >= 2 and \
-            bool(ops.L.lib().unet_bn_relu_pool_supported(ops._DT[a.dtype], seq[3].out_channels))
+            bool(ops.L.lib().unet_bn_relu_pool_supported(ops._DT[a.dtype], ops._pad64(c_out)))
         if fuse_head or fuse_pool or head is not None or pool:
             out_link = None
         out = _conv_bn_relu(seq[3], seq[4], a, None, in_link=link, out_link=out_link, head=head if fuse_head else None,
                             pool=fuse_pool)
         if head is not None and not fuse_head:
-            out = head[0](out, sigmoid=head[1])
+            return head[0](out, sigmoid=head[1])
+        if fuse_head:
+            return out
+        if c_out % 64:                                   # the logical-shape view of the padded result
+            if fuse_pool:
+                return ops.narrow_channels(out[0], c_out), out[1]
+            out = ops.narrow_channels(out, c_out)
         if pool and not fuse_pool:
             return out, None
         return out
@@ -188,18 +200,25 @@ class Up(_HipBlock):
         else:
             self.up = nn.ConvTranspose2d(in_channels, in_channels // 2, kernel_size=2, stride=2)
             self.conv = DoubleConv(in_channels, out_channels, precision=precision)
+        skip = in_channels - in_channels // 2        # the skip's width in the reference's use of the block
+        self.conv.skip_split = skip % 64 and skip     # (the pack cache's guess; forward uses the actual width)
 
     def forward(self, x1, x2, head=None, in_link=None, out_link=None):
         """``in_link`` / ``out_link`` (internal, optional): ops.BnLink from the block that produced ``x1`` / to the one
         consumer of the result (see DoubleConv.forward)."""
         dt = self.compute_dtype
+        skip = x2.shape[1]                  # logical widths (a narrow tensor is stored padded to a multiple of 64)
+        c_up = x1.shape[1] if self.bilinear else self.up.out_channels
+        if skip + c_up != self.conv.double_conv[0].in_channels:
+            raise ValueError(f"Up: {skip} skip + {c_up} up-sampled channels, the convolution expects "
+                             f"{self.conv.double_conv[0].in_channels}")
         x1 = ops.to_operator_layout(x1, dt)
         x2 = ops.to_operator_layout(x2, dt)
         if self.bilinear:
             u = ops.Bilinear2x.apply(x1)
         else:
             u = ops.ConvT2x2.apply(x1, self.up.weight, self.up.bias, in_link)
-        return self.conv(x2, u, head=head, out_link=out_link)
+        return self.conv(x2, u, head=head, out_link=out_link, split=skip % 64 and skip)
 
 
 class OutConv(_HipBlock):
@@ -225,13 +244,14 @@ def _pack_cache(model):
             if isinstance(mod, DoubleConv):
                 for idx in (0, 3):
                     w = mod.double_conv[idx].weight
-                    co, ci = w.shape[0], w.shape[1]
-                    ctot = (ci + 63) // 64 * 64
-                    cache.add(w, ops.L.PACK_CONV_FWD, co, ctot)
-                    cache.add(w, ops.L.PACK_CONV_DGRAD, ctot, co)
+                    co, ci = ops._pad64(w.shape[0]), w.shape[1]
+                    split = mod.skip_split if idx == 0 else 0
+                    ctot = ops.seg_cols(ci, split)
+                    cache.add(w, ops.L.PACK_CONV_FWD, co, ctot, split)
+                    cache.add(w, ops.L.PACK_CONV_DGRAD, ctot, co, split)
             elif isinstance(mod, Up) and not mod.bilinear:
                 w = mod.up.weight
-                ci, co = w.shape[0], w.shape[1]
+                ci, co = ops._pad64(w.shape[0]), ops._pad64(w.shape[1])
                 cache.add(w, ops.L.PACK_CONVT_FWD, co, ci)
                 cache.add(w, ops.L.PACK_CONVT_DGRAD, ci, co)
         model.__dict__["_packs"] = cache

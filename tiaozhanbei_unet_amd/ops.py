@@ -160,10 +160,15 @@ class PackInput(torch.autograd.Function):
 
 def to_operator_layout(x: torch.Tensor, dtype) -> torch.Tensor:
     """Accept what a caller of the reference modules would pass (NCHW fp32, any channel count) or an
-    activation already in operator layout."""
+    activation already in operator layout.  The logical-shape view a narrow block returned (narrow_channels) gives
+    back its padded tensor without a copy."""
     _require_cuda(x)
     if x.dim() != 4:
         raise ValueError(f"expected a 4-D NCHW tensor, got shape {tuple(x.shape)}")
+    if x.shape[1] % 64:
+        hit = _narrow_views.get(id(x))
+        if hit is not None and hit[0]() is x and x._version == hit[2] and hit[1].dtype == dtype:
+            return hit[1]
     if x.dtype == dtype and _is_nhwc(x) and x.shape[1] % 64 == 0:
         return x
     if x.shape[1] % 64 == 0 and x.dtype == dtype:
@@ -181,13 +186,113 @@ class _ToNHWC(torch.autograd.Function):
         return g
 
 
-def pack_weight(w: torch.Tensor, mode: int, rows: int, k: int, dtype) -> torch.Tensor:
+# ----------------------------------------------------------------------------- widths that are not multiples of 64
+# A layer of c channels runs as the layer of cp = pad64(c) channels: zero weight rows / columns and zero BatchNorm
+# gamma / beta in the pad lanes keep every padded activation and gradient exactly 0 there (DESIGN.md section 7).
+_narrow_views = {}       # id(view) -> (weakref to the view, its padded tensor, the view's _version when made)
+
+
+class _NarrowChannels(torch.autograd.Function):
+    """[N, c, H, W] view of a padded [N, cp, H, W] operator-layout tensor; the backward widens the gradient back into a
+    dense NHWC cp-wide buffer with zero pad lanes (unet_widen_channels)."""
+
+    @staticmethod
+    def forward(ctx, x, c):
+        ctx.cp, ctx.dtype = x.shape[1], x.dtype
+        return x[:, :c]
+
+    @staticmethod
+    def backward(ctx, g):
+        n, c, h, w = g.shape
+        if g.dtype not in _DT:
+            g = g.float()
+        out = _nhwc_empty(n, ctx.cp, h, w, ctx.dtype, g.device)
+        strides = (C.c_int64 * 4)(*g.stride())
+        L.check(L.lib().unet_widen_channels(_ptr(g), _DT[g.dtype], strides, n, c, h, w, _ptr(out), ctx.cp,
+                                            _DT[ctx.dtype], _stream()), "unet_widen_channels")
+        return out, None
+
+
+def narrow_channels(x: torch.Tensor, c: int) -> torch.Tensor:
+    """The logical-shape result of a narrow block: a view of its padded tensor ``x`` that to_operator_layout maps back
+    to ``x`` (by identity, while the view is unmodified)."""
+    import weakref
+    v = _NarrowChannels.apply(x, c)
+    key = id(v)
+
+    def _gone(ref, k=key):
+        if _narrow_views.get(k, (None,))[0] is ref:
+            del _narrow_views[k]
+    _narrow_views[key] = (weakref.ref(v, _gone), x, v._version)
+    return v
+
+
+def seg_cols(c_in: int, split: int) -> int:
+    """Packed input columns of a 3x3 conv weight with c_in parameter columns under the segment map ``split`` (logical
+    channels of source 0, stored pad64(split) wide; 0 = contiguous)."""
+    return _pad64(split) + _pad64(c_in - split) if split else _pad64(c_in)
+
+
+def seg_col(q: int, split: int, c_in: int) -> int:
+    """Parameter column of packed column ``q`` under the segment map, -1 for a zero column (unet_seg_col)."""
+    if split and q >= split:
+        if q < _pad64(split):
+            return -1
+        q = q - _pad64(split) + split
+    return q if q < c_in else -1
+
+
+def _remap(items):
+    """ONE unet_remap_batched launch.  items: (op, src, dst, rows, cols, inner, prows, pcols, split) -- fp32 contiguous
+    [rows][cols][inner] <-> [prows][pcols][inner] (L.REMAP_PAD: padded dst; L.REMAP_UNPAD: logical dst)."""
+    arr = (L.RemapDesc * len(items))()
+    for i, (op, src, dst, rows, cols, inner, prows, pcols, split) in enumerate(items):
+        arr[i] = L.RemapDesc(src.data_ptr(), dst.data_ptr(), rows, cols, inner, prows, pcols, split, op, 0)
+    L.check(L.lib().unet_remap_batched(arr, len(items), _stream()), "unet_remap_batched")
+
+
+def _vec_item(op, src, dst, c, cp):
+    return (op, src, dst, 1, c, 1, 1, cp, 0)
+
+
+class _NarrowBn:
+    """cp-length copies of a narrow BatchNorm's gamma, beta, running_mean, running_var with zero pad lanes (one pad
+    launch, plus ``extra`` pad items): the BatchNorm kernels then give scale = shift = 0 and dgamma = dbeta = 0 there.
+    write_back() returns the running statistics a finalize updated to the module's buffers."""
+
+    def __init__(self, gamma, beta, running_mean, running_var, cp, extra=()):
+        c = gamma.shape[0]
+        self.c, self.cp = c, cp
+        self.buf = torch.empty((4, cp), dtype=torch.float32, device=gamma.device)
+        self.stats = None if running_mean is None else (running_mean, running_var)
+        items = [_vec_item(L.REMAP_PAD, gamma, self.buf[0], c, cp), _vec_item(L.REMAP_PAD, beta, self.buf[1], c, cp)]
+        if self.stats is not None:
+            items += [_vec_item(L.REMAP_PAD, running_mean, self.buf[2], c, cp),
+                      _vec_item(L.REMAP_PAD, running_var, self.buf[3], c, cp)]
+        _remap(items + list(extra))
+
+    @property
+    def params(self):
+        b = self.buf
+        return (b[0], b[1]) + ((b[2], b[3]) if self.stats is not None else (None, None))
+
+    def write_back(self):
+        if self.stats is not None:
+            _remap([_vec_item(L.REMAP_UNPAD, self.buf[2], self.stats[0], self.c, self.cp),
+                    _vec_item(L.REMAP_UNPAD, self.buf[3], self.stats[1], self.c, self.cp)])
+
+
+def pack_weight(w: torch.Tensor, mode: int, rows: int, k: int, dtype, split: int = 0) -> torch.Tensor:
     taps = 9 if mode in (L.PACK_CONV_FWD, L.PACK_CONV_DGRAD) else 4
     out = torch.empty(taps * rows * k, dtype=dtype, device=w.device)
     if mode in (L.PACK_CONV_FWD, L.PACK_CONV_DGRAD):
         co, ci = w.shape[0], w.shape[1]
     else:
         ci, co = w.shape[0], w.shape[1]
+    if split:
+        L.check(L.lib().unet_pack_weight_seg(_ptr(w), _ptr(out), co, ci, rows, k, mode, split, _DT[dtype], _stream()),
+                "unet_pack_weight_seg")
+        return out
     L.check(L.lib().unet_pack_weight(_ptr(w), _ptr(out), co, ci, rows, k, mode, _DT[dtype], _stream()),
             "unet_pack_weight")
     return out
@@ -199,21 +304,22 @@ class PackCache:
 
     def __init__(self, dtype):
         self.dtype = dtype
-        self.items = []        # (weight, mode, rows, k)
-        self.slots = {}        # (id(weight), mode) -> [packed view, rows, k, version]
+        self.items = []        # (weight, mode, rows, k, split)
+        self.slots = {}        # (id(weight), mode) -> [packed view, rows, k, version, split]
         self.table = None
         self.ptrs = None
         self.gen = -1          # ops._train_generation when the packs were last written
 
-    def add(self, weight, mode, rows, k):
+    def add(self, weight, mode, rows, k, split=0):
+        """``split``: segment map of a 3x3 conv weight's input channels (unet_pack_desc.reserved; 0 = contiguous)."""
         if (id(weight), mode) not in self.slots:
-            self.items.append((weight, mode, rows, k))
-            self.slots[(id(weight), mode)] = [None, rows, k, -1]
+            self.items.append((weight, mode, rows, k, split))
+            self.slots[(id(weight), mode)] = [None, rows, k, -1, split]
 
     def _build(self):
         import numpy as np
         es = 2 if self.dtype == torch.bfloat16 else 4
-        sizes = [(9 if m <= L.PACK_CONV_DGRAD else 4) * r * k for (_, m, r, k) in self.items]
+        sizes = [(9 if m <= L.PACK_CONV_DGRAD else 4) * r * k for (_, m, r, k, _) in self.items]
         offs = [0]
         for s_ in sizes:
             offs.append(offs[-1] + (s_ + 7) // 8 * 8)
@@ -221,13 +327,13 @@ class PackCache:
         self.buf = torch.empty(offs[-1], dtype=self.dtype, device=dev)
         rec = np.zeros(len(self.items), dtype=[("w", "<u8"), ("out", "<u8"), ("c_out", "<i4"), ("c_in", "<i4"),
                                                ("rows", "<i4"), ("k", "<i4"), ("mode", "<i4"), ("pad", "<i4")])
-        for i, (w, m, r, k) in enumerate(self.items):
+        for i, (w, m, r, k, sp) in enumerate(self.items):
             view = self.buf[offs[i]:offs[i] + sizes[i]]
             co, ci = (w.shape[0], w.shape[1]) if m <= L.PACK_CONV_DGRAD else (w.shape[1], w.shape[0])
-            rec[i] = (w.data_ptr(), view.data_ptr(), co, ci, r, k, m, 0)
+            rec[i] = (w.data_ptr(), view.data_ptr(), co, ci, r, k, m, sp)
             self.slots[(id(w), m)][0] = view
         self.table = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
-        self.ptrs = [w.data_ptr() for (w, _, _, _) in self.items]
+        self.ptrs = [w.data_ptr() for (w, _, _, _, _) in self.items]
 
     def refresh(self, force=False):
         """``force``: repack regardless of the version counters (fused optimisers update parameters without
@@ -236,22 +342,23 @@ class PackCache:
         followed it changed the weights through raw pointers that no version counter sees."""
         if not self.items:
             return
-        if self.table is None or self.ptrs != [w.data_ptr() for (w, _, _, _) in self.items]:
+        if self.table is None or self.ptrs != [w.data_ptr() for (w, _, _, _, _) in self.items]:
             self._build()
             stale = True
         else:
             stale = force or self.gen != _train_generation or \
-                any(self.slots[(id(w), m)][3] != w._version for (w, m, _, _) in self.items)
+                any(self.slots[(id(w), m)][3] != w._version for (w, m, _, _, _) in self.items)
         if stale:
             L.check(L.lib().unet_pack_weights_batched(_ptr(self.table), len(self.items), _DT[self.dtype], _stream()),
                     "unet_pack_weights_batched")
-            for (w, m, _, _) in self.items:
+            for (w, m, _, _, _) in self.items:
                 self.slots[(id(w), m)][3] = w._version
             self.gen = _train_generation
 
-    def get(self, weight, mode, rows, k):
+    def get(self, weight, mode, rows, k, split=0):
         s_ = self.slots.get((id(weight), mode))
-        if s_ is not None and s_[0] is not None and s_[1] == rows and s_[2] == k and s_[3] == weight._version:
+        if s_ is not None and s_[0] is not None and s_[1] == rows and s_[2] == k and s_[3] == weight._version \
+                and s_[4] == split:
             return s_[0]
         return None
 
@@ -264,12 +371,12 @@ def set_active_packs(cache):
     _active_packs = cache
 
 
-def packed(weight, mode, rows, k, dtype):
+def packed(weight, mode, rows, k, dtype, split=0):
     if _active_packs is not None and _active_packs.dtype == dtype:
-        hit = _active_packs.get(weight, mode, rows, k)
+        hit = _active_packs.get(weight, mode, rows, k, split)
         if hit is not None:
             return hit
-    return pack_weight(weight, mode, rows, k, dtype)
+    return pack_weight(weight, mode, rows, k, dtype, split)
 
 
 # ----------------------------------------------------------------------------- gradient fan-in of the skips
@@ -335,11 +442,13 @@ _folded = {}                                             # id(weight) -> (weakre
 _train_generation = 0                                    # bumped by every training forward (see below)
 
 
-def _folded_pack(weight, gamma, beta, running_mean, running_var, co, ctot, dtype):
+def _folded_pack(weight, gamma, beta, running_mean, running_var, co, ctot, dtype, rows=None, split=0):
     """(packed folded weights, shift) of an eval-mode conv+BN layer.  Cached per weight Parameter; an entry is valid
     while the autograd version counters of the five tensors AND the training generation are unchanged -- the HIP
     kernels update running statistics (and fused optimisers update parameters) through raw pointers, which no version
-    counter sees, so any training forward in between invalidates every entry."""
+    counter sees, so any training forward in between invalidates every entry.  ``rows`` (> co for a narrow layer:
+    zero-padded BatchNorm coefficients, zero weight rows) and ``split`` (segment map of the input channels) give the
+    padded layer's pack."""
     stamp = (_train_generation, weight._version, gamma._version, beta._version, running_mean._version,
              running_var._version, running_mean.data_ptr(), running_var.data_ptr(), weight.data_ptr())
     import weakref
@@ -349,10 +458,22 @@ def _folded_pack(weight, gamma, beta, running_mean, running_var, co, ctot, dtype
         slot = (weakref.ref(weight, lambda _r, k=key: _folded.pop(k, None)), {})
         _folded[key] = slot
     per_weight = slot[1]
-    hit = per_weight.get((dtype, ctot))
+    rows = co if rows is None else rows
+    key = (dtype, ctot) if (rows == co and not split) else (dtype, ctot, rows, split)
+    hit = per_weight.get(key)
     if hit is not None and hit[0] == stamp:
         return hit[1]
     lib, st, dev = L.lib(), _stream(), weight.device
+    if key != (dtype, ctot):
+        g, b, rm, rv = _NarrowBn(gamma, beta, running_mean, running_var, rows).params
+        ss = torch.empty((2, rows), dtype=torch.float32, device=dev)
+        L.check(lib.unet_bn_eval_coeffs(rows, _ptr(g), _ptr(b), _ptr(rm), _ptr(rv), BN_EPS, _ptr(ss[0]), _ptr(ss[1]), st),
+                "unet_bn_eval_coeffs")
+        wq = torch.empty(9 * rows * ctot, dtype=dtype, device=dev)
+        L.check(lib.unet_pack_conv_weight_folded_seg(_ptr(weight.detach()), _ptr(ss[0]), _ptr(wq), co, weight.shape[1],
+                                                     rows, ctot, split, _DT[dtype], st), "unet_pack_conv_weight_folded_seg")
+        per_weight[key] = (stamp, (wq, ss[1]))
+        return wq, ss[1]
     ss = torch.empty((2, co), dtype=torch.float32, device=dev)
     L.check(lib.unet_bn_eval_coeffs(co, _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), BN_EPS,
                                     _ptr(ss[0]), _ptr(ss[1]), st), "unet_bn_eval_coeffs")
@@ -401,13 +522,15 @@ def _bn_stats_conv(lib, dt, n, h, w, src, wp, co, y, gamma, beta, running_mean, 
             "unet_bn_finalize_partials")
 
 
-def _bn_relu_backward(lib, dt, dtype, da, y, gamma, coef, link, out_sink, dev, st, frozen=False, beta_key=None):
+def _bn_relu_backward(lib, dt, dtype, da, y, gamma, coef, link, out_sink, dev, st, frozen=False, beta_key=None,
+                      gamma_key=None):
     """Gradient w.r.t. the raw conv output of a conv-BN-ReLU layer -> (dy, dgamma/dbeta [2, C]).  Premasked path: the
     consumer's data-gradient kernel already applied the ReLU mask and reduced the BatchNorm-backward sums (BnLink).
     ``frozen``: the layer normalised with its running statistics (BatchNorm2d in eval mode inside a training graph)."""
     n, co, h, w = y.shape
     pixels = n * h * w
-    dgb = (grad_out(gamma.shape, dev, gamma.data_ptr()), grad_out(gamma.shape, dev, beta_key))
+    dgb = (grad_out(gamma.shape, dev, gamma.data_ptr() if gamma_key is None else gamma_key),
+           grad_out(gamma.shape, dev, beta_key))
     if link is not None and link.dz_ptr and link.dz_ptr == da.data_ptr() and da.dtype == dtype and _is_nhwc(da):
         dy = da
         ws = _workspace(3 * co * 4, dev)
@@ -447,11 +570,15 @@ class ConvBnRelu(torch.autograd.Function):
       * ``pool``: the layer closes an encoder level (src/model.py:18-19, next level's MaxPool2d :32): BatchNorm-apply +
         ReLU + 2x2 max pool in one pass; returns (a, maxpool2(a)).  The backward routes the pooled gradient, adds it to
         what the decoders left in the skip's gradient buffer, masks and reduces in one pass (no separate pool backward,
-        no (y, da) reduction pass)."""
+        no (y, da) reduction pass).
+
+    Widths: a layer whose output channel count is not a multiple of 64 runs as the padded layer (zero weight rows,
+    zero-padded BatchNorm parameters, running statistics written back) and returns padded tensors; ``split`` = logical
+    channels of a narrow ``x0`` next to ``x1`` (the segment map of the packed input channels, 0 = contiguous)."""
 
     @staticmethod
     def forward(ctx, x0, x1, weight, gamma, beta, running_mean, running_var, training, momentum, fold=False,
-                in_link=None, out_link=None, head_w=None, head_b=None, head_sigmoid=False, pool=False):
+                in_link=None, out_link=None, head_w=None, head_b=None, head_sigmoid=False, pool=False, split=0):
         _require_cuda(x0, weight)
         dtype = x0.dtype
         dt = _DT[dtype]
@@ -463,29 +590,46 @@ class ConvBnRelu(torch.autograd.Function):
             if dy_ < 0 or dx_ < 0:
                 raise ValueError("Up: the skip tensor must be at least as large as the up-sampled one")
             oy, ox = dy_ // 2, dx_ // 2
-        co, ci = weight.shape[0], weight.shape[1]
+        co_p, ci = weight.shape[0], weight.shape[1]
+        co = _pad64(co_p)                     # the kernels' output width (co_p itself for multiples of 64)
         ctot = c0 + c1
-        if not (ci <= ctot < ci + 64):
+        split = int(split or 0)
+        if split:
+            if x1 is None or c0 != _pad64(split) or ctot != seg_cols(ci, split):
+                raise ValueError(f"conv weight expects {split} + {ci - split} input channels, activations carry "
+                                 f"{c0} + {c1} (padded)")
+        elif not (ci <= ctot < ci + 64):
             raise ValueError(f"conv weight expects {ci} input channels, activations carry {ctot}")
         if (head_w is not None or pool) and not training:
             raise RuntimeError("ConvBnRelu: the fused head / pool are training-path fusions")
         lib, st, dev = L.lib(), _stream(), x0.device
+        bn_param = (gamma, beta, running_mean, running_var)
+        narrow = co != co_p
         y = _nhwc_empty(n, co, h, w, dtype, dev)
         src = _views([(x0, 0, 0), None if x1 is None else (x1, oy, ox)])
         pixels = n * h * w
         coef = torch.empty((4, co), dtype=torch.float32, device=dev)   # mean, istd, scale, shift
         fold = bool(fold) and FOLD_EVAL_BN and not training
+        nb = None
         if not fold:
-            wp = packed(weight, L.PACK_CONV_FWD, co, ctot, dtype)
+            wp = packed(weight, L.PACK_CONV_FWD, co, ctot, dtype, split)
+            if narrow:
+                nb = _NarrowBn(gamma, beta, running_mean, running_var, co)
+                gamma, beta, running_mean, running_var = nb.params
         if training:
             global _train_generation
             _train_generation += 1
             _bn_stats_conv(lib, dt, n, h, w, src, wp, co, y, gamma, beta, running_mean, running_var, momentum, coef,
                            dev, st)
+            if nb is not None:
+                nb.write_back()
         elif fold:
             # inference: BatchNorm(eval) folded into the layer -- scale into the packed weights, shift + ReLU in the
             # convolution's epilogue: one kernel, the activation is written once
-            wf = _folded_pack(weight, gamma, beta, running_mean, running_var, co, ctot, dtype)
+            if narrow or split:
+                wf = _folded_pack(weight, *bn_param, co_p, ctot, dtype, rows=co, split=split)
+            else:
+                wf = _folded_pack(weight, gamma, beta, running_mean, running_var, co, ctot, dtype)
             L.check(lib.unet_conv3x3_bias_relu(dt, n, h, w, src, _ptr(wf[0]), co, _ptr(y), _ptr(wf[1]), 1, st),
                     "unet_conv3x3_bias_relu")
             return y
@@ -496,8 +640,9 @@ class ConvBnRelu(torch.autograd.Function):
                                              BN_EPS, _ptr(coef[0]), _ptr(coef[1]), _ptr(coef[2]), _ptr(coef[3]), st),
                     "unet_bn_eval_coeffs4")
         ctx.geom = (oy, ox, training)
-        ctx.keys = (weight.data_ptr(), beta.data_ptr(), 0 if head_w is None else head_w.data_ptr(),
+        ctx.keys = (weight.data_ptr(), bn_param[1].data_ptr(), 0 if head_w is None else head_w.data_ptr(),
                     0 if head_b is None else head_b.data_ptr())          # gradient bucket slots (data parallelism)
+        ctx.widths = (co_p, split, bn_param[0].data_ptr())
         ctx.sink0 = getattr(x0, "_unet_sink", None)     # x0 is a skip with a shared gradient buffer
         ctx.out_sink = None                              # set by share_grad() when THIS output is a skip
         ctx.in_link = in_link if (in_link is not None and in_link.y is not None and x1 is None) else None
@@ -515,6 +660,10 @@ class ConvBnRelu(torch.autograd.Function):
             return a, pooled
         if head_w is not None:
             hc = head_w.shape[0]
+            if narrow:                        # head weight [hc][co_p] -> [hc][co], zero columns
+                hw_p = torch.empty((hc, co, 1, 1), dtype=torch.float32, device=dev)
+                _remap([(L.REMAP_PAD, head_w.detach(), hw_p, hc, co_p, 1, hc, co, 0)])
+                head_w = hw_p
             out = torch.empty((n, hc, h, w), dtype=torch.float32, device=dev)
             L.check(lib.unet_head_bnrelu_fwd(dt, _ptr(y), n, h, w, co, _ptr(coef[2]), _ptr(coef[3]), _ptr(head_w),
                                              _ptr(head_b), hc, int(head_sigmoid), _ptr(out), st), "unet_head_bnrelu_fwd")
@@ -538,7 +687,11 @@ class ConvBnRelu(torch.autograd.Function):
         dtype = x0.dtype
         dt = _DT[dtype]
         n, c0, h, w = x0.shape
-        co, ci = weight.shape[0], weight.shape[1]
+        co, ci = y.shape[1], weight.shape[1]
+        co_p, split, gamma_key = ctx.widths
+        narrow = co != co_p
+        # a narrow layer's gradients w.r.t. gamma / beta / the head weight come out padded: fresh memory, unpadded last
+        gkey, bkey, hkey = (0, 0, 0) if narrow else (gamma_key, ctx.keys[1], ctx.keys[2])
         ctot = c0 + (0 if x1 is None else x1.shape[1])
         lib, st, dev = L.lib(), _stream(), x0.device
         pixels = n * h * w
@@ -550,8 +703,8 @@ class ConvBnRelu(torch.autograd.Function):
             hc = head_w.shape[0]
             dout = da.contiguous().float()
             dy = _nhwc_empty(n, co, h, w, dtype, dev)
-            dgb = (grad_out(gamma.shape, dev, gamma.data_ptr()), grad_out(gamma.shape, dev, ctx.keys[1]))
-            dhw = grad_out(head_w.shape, dev, ctx.keys[2])
+            dgb = (grad_out(gamma.shape, dev, gkey), grad_out(gamma.shape, dev, bkey))
+            dhw = grad_out(head_w.shape, dev, hkey)
             dhb = grad_out((hc,), dev, ctx.keys[3])
             part = torch.empty((lib.unet_head_bnrelu_max_parts(), 2, co), dtype=torch.float32, device=dev)
             nparts = C.c_int32(0)
@@ -583,7 +736,7 @@ class ConvBnRelu(torch.autograd.Function):
             L.check(lib.unet_bn_relu_pool_bwd(dt, _ptr(y), _ptr(dpooled), _ptr(da), n, h, w, co, _ptr(coef[2]),
                                               _ptr(coef[3]), _ptr(coef[0]), _ptr(dy), _ptr(part), C.byref(nparts), st),
                     "unet_bn_relu_pool_bwd")
-            dgb = (grad_out(gamma.shape, dev, gamma.data_ptr()), grad_out(gamma.shape, dev, ctx.keys[1]))
+            dgb = (grad_out(gamma.shape, dev, gkey), grad_out(gamma.shape, dev, bkey))
             ws = _workspace(3 * co * 4, dev)
             L.check(lib.unet_bn_bwd_premasked(dt, _ptr(dy), _ptr(y), pixels, co, _ptr(gamma), _ptr(coef[0]),
                                               _ptr(coef[1]), _ptr(part), nparts.value, _ptr(dgb[0]), _ptr(dgb[1]),
@@ -592,7 +745,7 @@ class ConvBnRelu(torch.autograd.Function):
             if da is None:                       # (a pooled pair whose skip half nobody used, and no pooled gradient)
                 da = torch.zeros_like(y)
             dy, dgb = _bn_relu_backward(lib, dt, dtype, da, y, gamma, coef, link, ctx.out_sink, dev, st,
-                                        frozen=not training, beta_key=ctx.keys[1])
+                                        frozen=not training, beta_key=bkey, gamma_key=gkey)
         src = _views([(x0, 0, 0), None if x1 is None else (x1, oy, ox)])
         dw = None
         wgrad_done = None
@@ -605,10 +758,13 @@ class ConvBnRelu(torch.autograd.Function):
                 helper.wait_stream(cur)
                 torch.cuda.set_stream(helper)
             try:
-                dw = grad_out(weight.shape, dev, ctx.keys[0])
+                # padded layer: the kernel writes dW of the padded one ([co][ctot] under a segment map, [co][ci] else)
+                ci_k = ctot if split else ci
+                dw = torch.empty((co, ci_k, 3, 3), dtype=torch.float32, device=dev) if (narrow or split) else \
+                    grad_out(weight.shape, dev, ctx.keys[0])
                 need = lib.unet_conv3x3_wgrad_workspace(n, h, w, ctot, co)
                 ws2 = _workspace(need, dev)
-                L.check(lib.unet_conv3x3_wgrad(dt, n, h, w, src, _ptr(dy), co, _ptr(dw), ci, _ptr(ws2), ws2.numel(),
+                L.check(lib.unet_conv3x3_wgrad(dt, n, h, w, src, _ptr(dy), co, _ptr(dw), ci_k, _ptr(ws2), ws2.numel(),
                                                _stream()), "unet_conv3x3_wgrad")
                 if helper is not None:
                     wgrad_done = torch.cuda.Event()
@@ -620,7 +776,7 @@ class ConvBnRelu(torch.autograd.Function):
                     torch.cuda.set_stream(cur)
         dx0 = dx1 = None
         if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
-            wp = packed(weight, L.PACK_CONV_DGRAD, ctot, co, dtype)
+            wp = packed(weight, L.PACK_CONV_DGRAD, ctot, co, dtype, split)
             sink = ctx.sink0
             ilink = ctx.in_link if (FUSE_BN_BWD and sink is None and x1 is None) else None
             if ilink is not None and ilink.y is not None and \
@@ -650,7 +806,23 @@ class ConvBnRelu(torch.autograd.Function):
                         dx0 = None              # already inside the buffer the first consumer returned
         if wgrad_done is not None:
             torch.cuda.current_stream(dev).wait_event(wgrad_done)
-        return dx0, dx1, dw, dgb[0], dgb[1], None, None, None, None, None, None, None, dhw, dhb, None, None
+        if narrow or split:
+            # padded gradients -> the parameters' shapes, one launch
+            items = []
+            if dw is not None:
+                dw, dw_pad = grad_out(weight.shape, dev, ctx.keys[0]), dw
+                items.append((L.REMAP_UNPAD, dw_pad, dw, co_p, ci, 9, co, dw_pad.shape[1], split))
+            if narrow:
+                dgb_pad, dgb = dgb, (grad_out((co_p,), dev, gamma_key), grad_out((co_p,), dev, ctx.keys[1]))
+                items += [_vec_item(L.REMAP_UNPAD, dgb_pad[0], dgb[0], co_p, co),
+                          _vec_item(L.REMAP_UNPAD, dgb_pad[1], dgb[1], co_p, co)]
+                if dhw is not None:
+                    hc = dhw.shape[0]
+                    dhw, dhw_pad = grad_out((hc, co_p, 1, 1), dev, ctx.keys[2]), dhw
+                    items.append((L.REMAP_UNPAD, dhw_pad, dhw, hc, co_p, 1, hc, co, 0))
+            if items:
+                _remap(items)
+        return dx0, dx1, dw, dgb[0], dgb[1], None, None, None, None, None, None, None, dhw, dhb, None, None, None
 
 
 class FirstConvBnRelu(torch.autograd.Function):
@@ -663,13 +835,22 @@ class FirstConvBnRelu(torch.autograd.Function):
         _require_cuda(x, weight)
         x = x.contiguous().float()
         n, ci, h, w = x.shape
-        co = weight.shape[0]
+        co_p = weight.shape[0]
+        co = _pad64(co_p)                     # 64: a narrow image layer runs with zero weight rows
         dtype = torch.bfloat16
         lib, st, dev = L.lib(), _stream(), x.device
         y = _nhwc_empty(n, co, h, w, dtype, dev)
         pixels = n * h * w
         coef = torch.empty((4, co), dtype=torch.float32, device=dev)
         wq = weight.detach().contiguous()
+        ctx.keys = (weight.data_ptr(), beta.data_ptr(), gamma.data_ptr())
+        nb = None
+        if co != co_p:
+            wq_p = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=dev)
+            nb = _NarrowBn(gamma, beta, running_mean, running_var, co,
+                           extra=[(L.REMAP_PAD, wq, wq_p, co_p, ci, 9, co, ci, 0)])
+            wq = wq_p
+            gamma, beta, running_mean, running_var = nb.params
         if training:
             cap = lib.unet_conv3x3_stats_max_parts(n, h, w)
             part = _workspace(cap * 2 * co * 4, dev)
@@ -680,6 +861,8 @@ class FirstConvBnRelu(torch.autograd.Function):
                                                   _ptr(running_mean), _ptr(running_var), momentum, BN_EPS,
                                                   _ptr(coef[0]), _ptr(coef[1]), _ptr(coef[2]), _ptr(coef[3]), st),
                     "unet_bn_finalize_partials")
+            if nb is not None:
+                nb.write_back()
         else:
             L.check(lib.unet_conv3x3_first_stats(n, h, w, _ptr(x), ci, _ptr(wq), _ptr(y), None, None, st),
                     "unet_conv3x3_first_stats")
@@ -691,7 +874,6 @@ class FirstConvBnRelu(torch.autograd.Function):
                 "unet_bn_relu_apply")
         ctx.save_for_backward(x, y, weight, gamma, coef)
         ctx.training = training
-        ctx.keys = (weight.data_ptr(), beta.data_ptr())
         ctx.out_sink = None
         ctx.out_link = None
         if out_link is not None and training:
@@ -705,35 +887,48 @@ class FirstConvBnRelu(torch.autograd.Function):
         dtype = torch.bfloat16
         dt = _DT[dtype]
         n, ci, h, w = x.shape
-        co = weight.shape[0]
+        co, co_p = y.shape[1], weight.shape[0]
+        narrow = co != co_p
+        gkey, bkey = (0, 0) if narrow else (ctx.keys[2], ctx.keys[1])
         lib, st, dev = L.lib(), _stream(), x.device
         link = ctx.out_link
+        dw, dgb = None, None
         if FUSE_FIRST_BN_BWD and link is not None and link.dz_ptr and link.dz_ptr == da.data_ptr() and da.dtype == dtype \
                 and _is_nhwc(da) and ctx.training and ctx.needs_input_grad[1]:
             # The image layer's dy has ONE consumer, its weight gradient (nothing flows back into the image): the
             # BatchNorm-backward apply pass is folded into that kernel's operand -- finalize only (dy = NULL), then
             # unet_conv3x3_first_wgrad_bn streams dz and y and forms dy = A*dz + B*y + K per lane (bit-identical dW).
-            dgb = (grad_out(gamma.shape, dev, gamma.data_ptr()), grad_out(gamma.shape, dev, ctx.keys[1]))
+            dgb = (grad_out(gamma.shape, dev, gkey), grad_out(gamma.shape, dev, bkey))
             cf = torch.empty(3 * co, dtype=torch.float32, device=dev)
             L.check(lib.unet_bn_bwd_premasked(dt, None, None, n * h * w, co, _ptr(gamma), _ptr(coef[0]), _ptr(coef[1]),
                                               _ptr(link.partial), link.n_parts, _ptr(dgb[0]), _ptr(dgb[1]), None, _ptr(cf),
                                               cf.numel() * 4, st), "unet_bn_bwd_premasked(coefficients)")
             link.y = link.coef = link.partial = None
             link.dz_ptr = 0
-            dw = grad_out(weight.shape, dev, ctx.keys[0])
+            dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=dev) if narrow else \
+                grad_out(weight.shape, dev, ctx.keys[0])
             ws2 = _workspace(lib.unet_conv3x3_first_wgrad_workspace(n, h, w), dev)
             L.check(lib.unet_conv3x3_first_wgrad_bn(n, h, w, _ptr(x), ci, _ptr(da), _ptr(y), _ptr(cf), _ptr(dw), _ptr(ws2),
                                                     ws2.numel(), st), "unet_conv3x3_first_wgrad_bn")
-            return None, dw, dgb[0], dgb[1], None, None, None, None, None
-        dy, dgb = _bn_relu_backward(lib, dt, dtype, da, y, gamma, coef, ctx.out_link, ctx.out_sink, dev, st,
-                                    frozen=not ctx.training, beta_key=ctx.keys[1])
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = grad_out(weight.shape, dev, ctx.keys[0])
-            need = lib.unet_conv3x3_first_wgrad_workspace(n, h, w)
-            ws2 = _workspace(need, dev)
-            L.check(lib.unet_conv3x3_first_wgrad(n, h, w, _ptr(x), ci, _ptr(dy), _ptr(dw), _ptr(ws2), ws2.numel(), st),
-                    "unet_conv3x3_first_wgrad")
+        else:
+            dy, dgb = _bn_relu_backward(lib, dt, dtype, da, y, gamma, coef, ctx.out_link, ctx.out_sink, dev, st,
+                                        frozen=not ctx.training, beta_key=bkey, gamma_key=gkey)
+            if ctx.needs_input_grad[1]:
+                dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=dev) if narrow else \
+                    grad_out(weight.shape, dev, ctx.keys[0])
+                need = lib.unet_conv3x3_first_wgrad_workspace(n, h, w)
+                ws2 = _workspace(need, dev)
+                L.check(lib.unet_conv3x3_first_wgrad(n, h, w, _ptr(x), ci, _ptr(dy), _ptr(dw), _ptr(ws2), ws2.numel(), st),
+                        "unet_conv3x3_first_wgrad")
+        if narrow:
+            # padded gradients -> the parameters' shapes, one launch
+            dgb_pad, dgb = dgb, (grad_out((co_p,), dev, ctx.keys[2]), grad_out((co_p,), dev, ctx.keys[1]))
+            items = [_vec_item(L.REMAP_UNPAD, dgb_pad[0], dgb[0], co_p, co),
+                     _vec_item(L.REMAP_UNPAD, dgb_pad[1], dgb[1], co_p, co)]
+            if dw is not None:
+                dw, dw_pad = grad_out(weight.shape, dev, ctx.keys[0]), dw
+                items.append((L.REMAP_UNPAD, dw_pad, dw, co_p, ci, 9, co, ci, 0))
+            _remap(items)
         return None, dw, dgb[0], dgb[1], None, None, None, None, None
 
 
@@ -746,7 +941,8 @@ def first_layer_ok(x: torch.Tensor, conv, dtype) -> bool:
     gradient, <= 3 channels into 64, width a multiple of 16."""
     return (FIRST_LAYER_KERNELS and dtype == torch.bfloat16 and x.dim() == 4 and x.dtype == torch.float32
             and not x.requires_grad and x.shape[1] == conv.in_channels
-            and bool(L.lib().unet_conv3x3_first_supported(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3])))
+            and bool(L.lib().unet_conv3x3_first_supported(conv.in_channels, _pad64(conv.out_channels), x.shape[2],
+                                                          x.shape[3])))
 
 
 class ChannelDropout(torch.autograd.Function):
@@ -835,14 +1031,18 @@ class ConvT2x2(torch.autograd.Function):
         its BatchNorm-backward sums (unet_convt2x2_dgrad_bnrelu)."""
         _require_cuda(x, weight)
         n, ci, h, w = x.shape
-        co = weight.shape[1]
+        co = _pad64(weight.shape[1])          # narrow layer: zero weight rows / bias lanes
         dtype = x.dtype
         wp = packed(weight, L.PACK_CONVT_FWD, co, ci, dtype)
+        if co != weight.shape[1]:
+            bias_p = torch.empty(co, dtype=torch.float32, device=x.device)
+            _remap([_vec_item(L.REMAP_PAD, bias.detach(), bias_p, weight.shape[1], co)])
+            bias = bias_p
         y = _nhwc_empty(n, co, 2 * h, 2 * w, dtype, x.device)
         L.check(L.lib().unet_convt2x2_fwd(_DT[dtype], n, h, w, _ptr(x), ci, _ptr(wp), _ptr(bias), _ptr(y), co,
                                           _stream()), "unet_convt2x2_fwd")
         ctx.save_for_backward(x, weight)
-        ctx.keys = (weight.data_ptr(), bias.data_ptr())
+        ctx.keys = (weight.data_ptr(), bias.data_ptr() if co == weight.shape[1] else 0)
         ctx.in_link = in_link if (in_link is not None and in_link.y is not None and
                                   in_link.y.data_ptr() != 0 and tuple(in_link.y.shape) == tuple(x.shape)) else None
         return y
@@ -851,7 +1051,9 @@ class ConvT2x2(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         n, ci, h, w = x.shape
-        co = weight.shape[1]
+        ci_p, co_p = weight.shape[0], weight.shape[1]
+        co = _pad64(co_p)
+        padded = (ci, co) != (ci_p, co_p)
         dtype = x.dtype
         lib, st, dev = L.lib(), _stream(), x.device
         dy = _as_nhwc(dy, dtype)
@@ -872,11 +1074,19 @@ class ConvT2x2(torch.autograd.Function):
             else:
                 L.check(lib.unet_convt2x2_dgrad(_DT[dtype], n, h, w, _ptr(dy), co, _ptr(wp), _ptr(dx), ci, st),
                         "unet_convt2x2_dgrad")
-        dw = grad_out(weight.shape, dev, ctx.keys[0])
-        db = grad_out((co,), dev, ctx.keys[1])
+        if padded:
+            dw = torch.empty((ci, co, 2, 2), dtype=torch.float32, device=dev)
+            db = torch.empty(co, dtype=torch.float32, device=dev)
+        else:
+            dw = grad_out(weight.shape, dev, ctx.keys[0])
+            db = grad_out((co,), dev, ctx.keys[1])
         ws = _workspace(lib.unet_convt2x2_wgrad_workspace(n, h, w, ci, co), dev)
         L.check(lib.unet_convt2x2_wgrad(_DT[dtype], n, h, w, _ptr(x), ci, _ptr(dy), co, _ptr(dw), _ptr(db),
                                         _ptr(ws), ws.numel(), st), "unet_convt2x2_wgrad")
+        if padded:
+            (dw, dw_pad), (db, db_pad) = (grad_out(weight.shape, dev, ctx.keys[0]), dw), (grad_out((co_p,), dev, 0), db)
+            _remap([(L.REMAP_UNPAD, dw_pad, dw, ci_p, co_p, 4, ci, co, 0),
+                    _vec_item(L.REMAP_UNPAD, db_pad, db, co_p, co)])
         return dx, dw, db, None
 
 
@@ -913,6 +1123,11 @@ class Head(torch.autograd.Function):
         _require_cuda(x, weight)
         n, ci, h, w = x.shape
         co = weight.shape[0]
+        ctx.ci_p = weight.shape[1]
+        if ci != ctx.ci_p:                    # padded input (a narrow OutConv): zero weight columns
+            w_p = torch.empty((co, ci, 1, 1), dtype=torch.float32, device=x.device)
+            _remap([(L.REMAP_PAD, weight.detach(), w_p, co, ctx.ci_p, 1, co, ci, 0)])
+            weight = w_p
         out = torch.empty((n, co, h, w), dtype=torch.float32, device=x.device)
         L.check(L.lib().unet_head_fwd(_DT[x.dtype], _ptr(x), n, h, w, ci, _ptr(weight), _ptr(bias), co,
                                       int(sigmoid), _ptr(out), _stream()), "unet_head_fwd")
@@ -929,12 +1144,17 @@ class Head(torch.autograd.Function):
         lib, dev = L.lib(), x.device
         dout = dout.contiguous().float()
         dx = _nhwc_empty(n, ci, h, w, x.dtype, dev)
-        dw = grad_out(weight.shape, dev, ctx.keys[0])
+        padded = ci != ctx.ci_p
+        dw = torch.empty((co, ci, 1, 1), dtype=torch.float32, device=dev) if padded else \
+            grad_out(weight.shape, dev, ctx.keys[0])
         db = grad_out((co,), dev, ctx.keys[1])
         ws = _workspace(lib.unet_head_bwd_workspace(n, h, w, ci, co), dev)
         L.check(lib.unet_head_bwd(_DT[x.dtype], _ptr(x), _ptr(out), _ptr(dout), n, h, w, ci, _ptr(weight), co,
                                   int(ctx.sigmoid), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), _stream()),
                 "unet_head_bwd")
+        if padded:
+            dw, dw_pad = grad_out((co, ctx.ci_p, 1, 1), dev, ctx.keys[0]), dw
+            _remap([(L.REMAP_UNPAD, dw_pad, dw, co, ctx.ci_p, 1, co, ci, 0)])
         return dx, dw, db, None
 
 
