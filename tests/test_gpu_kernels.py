@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _ref64 as R
 from conftest import load_golden
 from oracle import unet_oracle as O
 from oracle import weights as W
@@ -96,16 +97,25 @@ def test_conv3x3_fwd_dgrad_wgrad(hip, dtype, case):
     L.check(L.lib().unet_conv3x3(dt, n, h, w, views(L, [(xd, 0, 0), None]), p(wp), co, views(L, [(y, 0, 0), None]),
                                  co, 0, L.K_CONV_FWD, st()), "conv fwd")
     check(y, ref, dtype, "conv3x3 fwd")
+    bf = dtype == torch.bfloat16
+    if bf:      # float64 reference, half a bf16 ulp + 2^-18 S (tests/_ref64.py)
+        R.assert_bf16(y, R.conv3x3(x, wt), "conv3x3 fwd")
     # data gradient (same kernel, flipped weights)
     dx = ops._nhwc_empty(n, ci, h, w, dtype, dev())
     wpd = ops.pack_weight(wd, L.PACK_CONV_DGRAD, ci, co, dtype)
     L.check(L.lib().unet_conv3x3(dt, n, h, w, views(L, [(gd, 0, 0), None]), p(wpd), ci, views(L, [(dx, 0, 0), None]),
                                  ci, 0, L.K_CONV_DGRAD, st()), "conv dgrad")
     check(dx, xq.grad, dtype, "conv3x3 dgrad")
+    if bf:
+        rd = R.conv3x3_dgrad(gy, wt)
+        R.assert_bf16(dx, rd, "conv3x3 dgrad")
+        old = dx.double().cpu()
     # accumulate flag: dst += result
     L.check(L.lib().unet_conv3x3(dt, n, h, w, views(L, [(gd, 0, 0), None]), p(wpd), ci, views(L, [(dx, 0, 0), None]),
                                  ci, 1, L.K_CONV_DGRAD, st()), "conv dgrad acc")
     check(dx, 2 * xq.grad, dtype, "conv3x3 dgrad accumulate", bf=2.5e-2)
+    if bf:      # the stored old value + the exact gradient, rounded once
+        R.assert_bf16(dx, (old + rd[0], old.abs() + rd[1]), "conv3x3 dgrad accumulate")
     # weight gradient
     dw = torch.empty(co, ci, 3, 3, device=dev())
     need = L.lib().unet_conv3x3_wgrad_workspace(n, h, w, ci, co)
@@ -113,6 +123,9 @@ def test_conv3x3_fwd_dgrad_wgrad(hip, dtype, case):
     L.check(L.lib().unet_conv3x3_wgrad(dt, n, h, w, views(L, [(xd, 0, 0), None]), p(gd), co, p(dw), ci, p(ws), need,
                                        st()), "conv wgrad")
     check(dw, wq.grad, dtype, "conv3x3 wgrad", f32=5e-5, bf=5e-3)
+    if bf:
+        assert n * h * w <= R.MAX_WGRAD_K
+        R.assert_fp32(dw, R.conv3x3_wgrad(x, gy), "conv3x3 wgrad")
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
@@ -288,6 +301,13 @@ def test_convt2x2(hip, dtype, case):
     check(xd.grad, xq.grad, dtype, "convT dgrad")
     check(wd.grad, wq.grad, dtype, "convT wgrad", f32=5e-5, bf=5e-3)
     check(bd.grad, bq.grad, dtype, "convT bias grad", f32=5e-5, bf=5e-3)
+    if dtype == torch.bfloat16:     # float64 reference, half a bf16 ulp + 2^-18 S (tests/_ref64.py)
+        R.assert_bf16(y, R.convt2x2(x, wt, b), "convT fwd")
+        R.assert_bf16(xd.grad, R.convt2x2_dgrad(gy, wt), "convT dgrad")
+        assert n * h * w <= R.MAX_WGRAD_K
+        rw, rb = R.convt2x2_wgrad(x, gy)
+        R.assert_fp32(wd.grad, rw, "convT wgrad")
+        R.assert_fp32(bd.grad, rb, "convT bias grad")
 
 
 # ------------------------------------------------------------------ BatchNorm + ReLU
@@ -735,6 +755,7 @@ def test_conv3x3_persistent_kernels_many_work_items(hip, case):
     L.check(L.lib().unet_conv3x3_stats(dt, n, h, w, views(L, [(xd, 0, 0), None]), p(wp), co, p(y), p(part), C.byref(nparts),
                                        st()), "conv stats")
     check(y, ref, dtype, "conv3x3 fwd (many work items)")
+    R.assert_bf16(y, R.conv3x3(x, wt), "conv3x3 fwd (many work items)")
     sums = part[:nparts.value * 2 * co].view(nparts.value, 2, co).double().sum(0).cpu()
     yf = y.float().cpu().double()
     assert torch.allclose(sums[0], yf.sum((0, 2, 3)), rtol=2e-4, atol=5e-2), "fused sum(y)"
@@ -749,15 +770,21 @@ def test_conv3x3_persistent_kernels_many_work_items(hip, case):
         L.check(L.lib().unet_conv3x3(dt, n, h, w, views(L, [(gd, 0, 0), None]), p(wpd), ci, views(L, [(dx, 0, 0), None]),
                                      ci, 0, L.K_CONV_DGRAD, st()), "conv dgrad")
         check(dx, xq.grad, dtype, "conv3x3 dgrad (many work items)")
+        rd = R.conv3x3_dgrad(gy, wt)
+        R.assert_bf16(dx, rd, "conv3x3 dgrad (many work items)")
+        old = dx.double().cpu()
         L.check(L.lib().unet_conv3x3(dt, n, h, w, views(L, [(gd, 0, 0), None]), p(wpd), ci, views(L, [(dx, 0, 0), None]),
                                      ci, 1, L.K_CONV_DGRAD, st()), "conv dgrad acc")
         check(dx, 2 * xq.grad, dtype, "conv3x3 dgrad accumulate (many work items)", bf=2.5e-2)
+        R.assert_bf16(dx, (old + rd[0], old.abs() + rd[1]), "conv3x3 dgrad accumulate (many work items)")
     dw = torch.empty(co, ci, 3, 3, device=dev())
     need = L.lib().unet_conv3x3_wgrad_workspace(n, h, w, ci, co)
     ws = torch.empty(need, dtype=torch.uint8, device=dev())
     L.check(L.lib().unet_conv3x3_wgrad(dt, n, h, w, views(L, [(xd, 0, 0), None]), p(gd), co, p(dw), ci, p(ws), need, st()),
             "conv wgrad")
     check(dw, wq.grad, dtype, "conv3x3 wgrad (many work items)", bf=5e-3)
+    assert n * h * w <= R.MAX_WGRAD_K
+    R.assert_fp32(dw, R.conv3x3_wgrad(x, gy), "conv3x3 wgrad (many work items)")
 
 
 TWO_SOURCE_CASES = [  # n, c_skip, c_up, cout, h, w
@@ -786,12 +813,16 @@ def test_conv3x3_persistent_two_source_many_work_items(hip, case):
     L.check(L.lib().unet_conv3x3(dt, n, h, w, views(L, [(x2d, 0, 0), (x1d, 0, 0)]), p(wp), co, views(L, [(y, 0, 0), None]), co, 0,
                                  L.K_CONV_FWD, st()), "conv fwd 2 src")
     check(y, ref, dtype, "two-source conv fwd (many work items)")
+    R.assert_bf16(y, R.conv3x3(torch.cat([x2, x1], 1), wt), "two-source conv fwd (many work items)")
     d2, d1 = ops._nhwc_empty(n, c0, h, w, dtype, dev()), ops._nhwc_empty(n, c1, h, w, dtype, dev())
     wpd = ops.pack_weight(wd, L.PACK_CONV_DGRAD, c0 + c1, co, dtype)
     L.check(L.lib().unet_conv3x3(dt, n, h, w, views(L, [(gd, 0, 0), None]), p(wpd), c0 + c1, views(L, [(d2, 0, 0), (d1, 0, 0)]),
                                  c0, 0, L.K_CONV_DGRAD, st()), "conv dgrad 2 dst")
     check(d2, x2q.grad, dtype, "two-destination dgrad, skip half")
     check(d1, x1q.grad, dtype, "two-destination dgrad, up half")
+    rd = R.conv3x3_dgrad(gy, wt)
+    R.assert_bf16(d2, (rd[0][:, :c0], rd[1][:, :c0]), "two-destination dgrad, skip half")
+    R.assert_bf16(d1, (rd[0][:, c0:], rd[1][:, c0:]), "two-destination dgrad, up half")
     # weight gradient over the two column sources (the XCD-aware block order of wgrad_dma_kernel)
     dw = torch.empty(co, c0 + c1, 3, 3, device=dev())
     need = L.lib().unet_conv3x3_wgrad_workspace(n, h, w, c0 + c1, co)
@@ -799,6 +830,8 @@ def test_conv3x3_persistent_two_source_many_work_items(hip, case):
     L.check(L.lib().unet_conv3x3_wgrad(dt, n, h, w, views(L, [(x2d, 0, 0), (x1d, 0, 0)]), p(gd), co, p(dw), c0 + c1, p(ws), need,
                                        st()), "conv wgrad 2 src")
     check(dw, wq.grad, dtype, "two-source wgrad", bf=5e-3)
+    assert n * h * w <= R.MAX_WGRAD_K
+    R.assert_fp32(dw, R.conv3x3_wgrad(torch.cat([x2, x1], 1), gy), "two-source wgrad")
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
@@ -825,14 +858,24 @@ def test_conv3x3_two_sources_with_centre_pad_offsets(hip, dtype, case):
     wp = ops.pack_weight(wd, L.PACK_CONV_FWD, co, c0 + c1, dtype)
     L.check(L.lib().unet_conv3x3(dt, n, h, w, src, p(wp), co, views(L, [(y, 0, 0), None]), co, 0, L.K_CONV_FWD, st()), "fwd")
     check(y, ref, dtype, "two-source forward with a padded second source")
+    bf = dtype == torch.bfloat16
+    xcat = torch.cat([x2, F.pad(x1, [ox, w - w1 - ox, oy, h - h1 - oy])], 1)
+    if bf:
+        R.assert_bf16(y, R.conv3x3(xcat, wt), "two-source forward with a padded second source")
     d2, d1 = ops._nhwc_empty(n, c0, h, w, dtype, dev()), ops._nhwc_empty(n, c1, h1, w1, dtype, dev())
     wpd = ops.pack_weight(wd, L.PACK_CONV_DGRAD, c0 + c1, co, dtype)
     L.check(L.lib().unet_conv3x3(dt, n, h, w, views(L, [(gd, 0, 0), None]), p(wpd), c0 + c1,
                                  views(L, [(d2, 0, 0), (d1, oy, ox)]), c0, 0, L.K_CONV_DGRAD, st()), "dgrad")
     check(d2, x2q.grad, dtype, "dgrad, skip half")
     check(d1, x1q.grad, dtype, "dgrad, up-sampled half (cropped back to its own size)")
+    if bf:
+        rd, sd = R.conv3x3_dgrad(gy, wt)
+        R.assert_bf16(d2, (rd[:, :c0], sd[:, :c0]), "dgrad, skip half")
+        R.assert_bf16(d1, (rd[:, c0:, oy:oy + h1, ox:ox + w1], sd[:, c0:, oy:oy + h1, ox:ox + w1]), "dgrad, up-sampled half")
     dw = torch.empty(co, c0 + c1, 3, 3, device=dev())
     need = L.lib().unet_conv3x3_wgrad_workspace(n, h, w, c0 + c1, co)
     ws = torch.empty(need, dtype=torch.uint8, device=dev())
     L.check(L.lib().unet_conv3x3_wgrad(dt, n, h, w, src, p(gd), co, p(dw), c0 + c1, p(ws), need, st()), "wgrad")
     check(dw, wq.grad, dtype, "wgrad over a padded second source", f32=5e-5, bf=5e-3)
+    if bf:
+        R.assert_fp32(dw, R.conv3x3_wgrad(xcat, gy), "wgrad over a padded second source")
