@@ -449,6 +449,17 @@ int32_t unet_resize_bilinear_u8(const uint8_t* src, int32_t n, int32_t h, int32_
 int32_t unet_resize_nearest_index(int32_t in_size, int32_t out_size, int32_t* idx);
 int32_t unet_resize_nearest_u8(const uint8_t* src, int32_t n, int32_t h, int32_t w, int32_t c, int32_t out_h,
                                int32_t out_w, const int32_t* yidx, const int32_t* xidx, uint8_t* dst, void* stream);
+/* Gear label masks (reference src/gear_dataset.py:112-201 _create_mask_from_labelme, then :241-259 Resize(NEAREST)):
+ * dst[n][out_h][out_w] = class of source pixel (yidx[n][i], xidx[n][j]) -- the highest-priority raw class (1 -> 2, then
+ * 0 -> 1, then 2 -> 3; others ignored) with a polygon whose ImageDraw.polygon(xy, fill=1) covers it, else 0.  verts
+ * [V][2] (x, y) integer pixel coordinates; polygon p owns verts[poly_offsets[p] .. poly_offsets[p+1]) (>= 3 vertices,
+ * at most max_poly_vertices <= 512), raw class poly_class[p], image poly_image[p] (non-decreasing); src_hw[n] = source
+ * (h, w); per-image index tables from unet_resize_nearest_index (identity tables = the full-resolution mask).  All
+ * arrays in DEVICE memory; out_w <= 4096. */
+int32_t unet_polygon_mask_u8(const int32_t* verts, const int32_t* poly_offsets, const int32_t* poly_class,
+                             const int32_t* poly_image, int32_t n_polys, int32_t max_poly_vertices, const int32_t* src_hw,
+                             int32_t n, int32_t out_h, int32_t out_w, const int32_t* yidx, const int32_t* xidx,
+                             uint8_t* dst, void* stream);
 /* RandomHorizontalFlip + RandomRotation: dst = rotate(flip[n] ? mirror(src) : src) with Image.rotate(angle, NEAREST,
  * expand=False, fill 0) = Geometry.c affine_fixed in 16.16 fixed point.  matrices[n][6] (DEVICE, may be NULL: no
  * rotation) = {a0, a1, a2, a3, a4, a5} ALREADY in fixed point, a2 / a5 including the half-pixel terms (FIX(a[2] +

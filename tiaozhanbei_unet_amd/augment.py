@@ -237,3 +237,61 @@ class DeviceTransform:
             device = torch.device("cuda", torch.cuda.current_device())
         m = _resize_any(masks, self.size[0], self.size[1], device)
         return (m.permute(0, 3, 1, 2).float() / 255.0).contiguous()
+
+
+POLY_MAX_VERTICES = 512      # unet_polygon_mask_u8: crossings of one polygon on one scan line live in LDS
+
+
+def _nearest_tables(sizes, out_h, out_w, device):
+    """Per-image NEAREST index tables [N, out_h] / [N, out_w] (unet_resize_nearest_index) for a list of (h, w)."""
+    ys = [_axis_tables("nearest", h, out_h, device)[0] for h, _ in sizes]
+    xs = [_axis_tables("nearest", w, out_w, device)[0] for _, w in sizes]
+    return torch.stack(ys).contiguous(), torch.stack(xs).contiguous()
+
+
+def polygon_masks_u8(polys, src_sizes, out_h: int, out_w: int, device="cuda") -> torch.Tensor:
+    """Gear class masks of a batch, on the device (unet_polygon_mask_u8): ``GearDataset._create_mask_from_labelme`` of the
+    reference (src/gear_dataset.py:112-201) followed by ``Image.resize((out_w, out_h), NEAREST)``, without a
+    full-resolution mask ever existing.  Equal to the reference on every fixture case except polygons that revisit a
+    vertex, where a few pixels on that vertex's row can differ (csrc/polygon.hip, "Known divergence").  ``polys`` = the flat arrays ``gear_dataset.collate_raw`` builds: ``verts`` int32
+    [V, 2] pixel (x, y), ``offsets`` [P + 1], ``classes`` [P] raw class ids, ``images`` [P] (non-decreasing);
+    ``src_sizes`` = [(h, w)] per image.  Output sizes equal to a source size give that image's full-resolution mask.
+    Returns uint8 [N, out_h, out_w]."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    sizes = [(int(h), int(w)) for h, w in src_sizes]
+    n = len(sizes)
+    if n == 0 or out_h <= 0 or out_w <= 0:
+        raise ValueError("polygon_masks_u8: need at least one image and a positive output size")
+    verts = np.ascontiguousarray(np.asarray(polys["verts"], dtype=np.int64).reshape(-1, 2))
+    offsets = np.asarray(polys["offsets"], dtype=np.int64).reshape(-1)
+    classes = np.asarray(polys["classes"], dtype=np.int64).reshape(-1)
+    images = np.asarray(polys["images"], dtype=np.int64).reshape(-1)
+    p = len(classes)
+    if len(offsets) != p + 1 or len(images) != p or offsets[0] != 0 or offsets[-1] != len(verts):
+        raise ValueError("polygon_masks_u8: offsets / classes / images do not describe the vertex array")
+    counts = np.diff(offsets)
+    if p and (counts.min() < 3 or counts.max() > POLY_MAX_VERTICES):
+        bad = int(np.argmax((counts < 3) | (counts > POLY_MAX_VERTICES)))
+        raise ValueError(f"polygon_masks_u8: polygon {bad} of image {int(images[bad])} has {int(counts[bad])} vertices; "
+                         f"every polygon needs 3..{POLY_MAX_VERTICES}")
+    if p and (np.any(np.diff(images) < 0) or images.min() < 0 or images.max() >= n):
+        raise ValueError("polygon_masks_u8: image indices must be non-decreasing and inside the batch")
+    if verts.size and np.abs(verts).max() >= (1 << 24):
+        raise ValueError("polygon_masks_u8: coordinates must stay below 2^24 in magnitude (exact in float32)")
+    if any(h <= 0 or w <= 0 or h >= (1 << 24) or w >= (1 << 24) for h, w in sizes):
+        raise ValueError("polygon_masks_u8: bad source size")
+    if p == 0:                               # nothing to draw: all background
+        return torch.zeros((n, out_h, out_w), dtype=torch.uint8, device=device)
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device, non_blocking=True)
+
+    yi, xi = _nearest_tables(sizes, out_h, out_w, device)
+    hw = dev(np.asarray(sizes, dtype=np.int32).reshape(n, 2))
+    v_d, o_d, c_d, i_d = dev(verts), dev(offsets), dev(classes), dev(images)
+    out = torch.empty((n, out_h, out_w), dtype=torch.uint8, device=device)
+    L.check(L.lib().unet_polygon_mask_u8(_ptr(v_d), _ptr(o_d), _ptr(c_d), _ptr(i_d), p, int(counts.max()), _ptr(hw), n,
+                                         out_h, out_w, _ptr(yi), _ptr(xi), _ptr(out), _stream()), "unet_polygon_mask_u8")
+    return out
