@@ -398,6 +398,17 @@ int32_t unet_seg_loss(const float* logits, const int64_t* target, int32_t n, int
  * labels or confusion (with target) may be NULL.  Integer atomics: exact. */
 int32_t unet_seg_confusion(const float* logits, const int64_t* target, int32_t n, int32_t c, int64_t hw,
                            int64_t ignore_index, int64_t* labels, int64_t* confusion, void* stream);
+/* Per-image evaluation statistics (SegmentationMetrics.update per image, visualize.py:239-257 compute_prediction_stats)
+ * of fp32 NCHW logits [n][c][hw], 2 <= c <= 8, in one pass: confusion[n][c][c] (uint64 counts, rows = truth, columns =
+ * prediction; the first maximum wins ties; pixels whose target is ignore_index or not a class are skipped; target NULL:
+ * all zeros; confusion may be NULL), conf[n][2] (fp64) = mean and unbiased standard deviation (n - 1, torch.std) of the
+ * per-pixel maximum softmax probability over all hw pixels, labels[n][hw] (uint8 argmax, may be NULL).  Ordered fp64
+ * reductions through the workspace, no float atomics: bitwise reproducible.  Allocates nothing, does not synchronise.
+ * The workspace query returns 0 for unsupported shapes. */
+size_t unet_seg_image_stats_workspace(int32_t n, int32_t c, int64_t hw);
+int32_t unet_seg_image_stats(const float* logits, const int64_t* target, int32_t n, int32_t c, int64_t hw,
+                             int64_t ignore_index, uint8_t* labels, int64_t* confusion, double* conf, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* Pixel-level threshold epilogue of the anomaly branch (src/test.py:79-106 evaluate_results, src/train_utils.py:232-245
  * validate_epoch): for each of k <= 8 thresholds the confusion counts {tp, fp, fn, tn} of (pred > t) against

@@ -235,3 +235,45 @@ def compute_metrics_from_predictions(predictions, targets, num_classes, class_na
     calc = SegmentationMetrics(num_classes)
     calc.update(predictions, targets)
     return calc.compute_all_metrics()
+
+
+# ---- per-image evaluation statistics (the Gear / Kolektor evaluation CLIs, seg_eval.py)
+def per_image_stats(logits, target=None, ignore_index=None, labels=False):
+    """Per-image statistics of (N, C, H, W) logits, 2 <= C <= 8, in one device pass (unet_seg_image_stats):
+    ``confusion`` int64 (N, C, C) (rows = truth, columns = prediction; None without ``target``), ``conf_mean`` /
+    ``conf_std`` float64 (N,) = mean and unbiased std of the per-pixel maximum softmax probability, ``labels`` uint8
+    (N, H, W) argmax (first maximum wins ties) when ``labels`` else None.  Device tensors; nothing is read back."""
+    _require_cuda(logits, target)
+    if logits.dim() < 3 or (target is not None and tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:])):
+        raise ValueError(f"expected (N, C, ...) logits and (N, ...) labels, got {tuple(logits.shape)} / "
+                         f"{None if target is None else tuple(target.shape)}")
+    n, c = logits.shape[0], logits.shape[1]
+    hw = int(np.prod(logits.shape[2:]))
+    x = logits.detach().contiguous().float()
+    t = None if target is None else target.detach().contiguous().long()
+    dev = x.device
+    conf = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    cm = None if t is None else torch.empty((n, c, c), dtype=torch.int64, device=dev)
+    lab = torch.empty((n,) + tuple(logits.shape[2:]), dtype=torch.uint8, device=dev) if labels else None
+    lib = L.lib()
+    ws = _workspace(max(int(lib.unet_seg_image_stats_workspace(n, c, hw)), 8), dev)
+    L.check(lib.unet_seg_image_stats(_ptr(x), _ptr(t), n, c, hw, _NO_IGNORE if ignore_index is None else int(ignore_index),
+                                     _ptr(lab), _ptr(cm), _ptr(conf), _ptr(ws), ws.numel(), _stream()),
+            "unet_seg_image_stats")
+    return {"confusion": cm, "conf_mean": conf[:, 0], "conf_std": conf[:, 1], "labels": lab}
+
+
+def image_prediction_stats(confusion, conf_mean, conf_std, class_names):
+    """The reference's ``compute_prediction_stats`` dict (visualize.py:239-257) of one image from its
+    ``per_image_stats`` entry: ``accuracy``, ``confidence_mean``, ``confidence_std`` and ``accuracy_{name}`` for every
+    class present in the truth.  The accuracies are ratios of the C x C counts, so pixels left out of the counts
+    (ignore_index, targets outside 0..C-1) are left out of them too; the reference counts such pixels as misses."""
+    cm = np.asarray(confusion.cpu() if torch.is_tensor(confusion) else confusion, dtype=np.int64)
+    total = int(cm.sum())
+    stats = {"accuracy": float(np.trace(cm)) / total if total else float("nan"),
+             "confidence_mean": float(conf_mean), "confidence_std": float(conf_std)}
+    rows = cm.sum(axis=1)
+    for i, name in enumerate(class_names):
+        if i < len(rows) and rows[i] > 0:
+            stats[f"accuracy_{name}"] = float(cm[i, i]) / float(rows[i])
+    return stats

@@ -66,15 +66,16 @@ def _seg_batches(loader, preprocess, device):
         yield preprocess(images, polys, sizes, device=device)
 
 
-def train_seg_epoch(model, dataloader, criterion, optimizer, device, epoch, num_classes, preprocess):
+def train_seg_epoch(model, dataloader, criterion, optimizer, device, epoch, num_classes, preprocess, *, batches=None):
     """One training epoch (reference train.py:118-160): the loss is the UNWEIGHTED mean of the per-batch losses, the
-    metrics those of a ``SegmentationMetrics`` updated with every batch.  Losses are summed on the device and read once."""
+    metrics those of a ``SegmentationMetrics`` updated with every batch.  Losses are summed on the device and read once.
+    ``batches``: an iterable of (images, masks) device batches to use instead of ``dataloader`` + ``preprocess``."""
     from .metrics import SegmentationMetrics
     model.train()
     metrics = SegmentationMetrics(num_classes)
     total = torch.zeros((), dtype=torch.float64, device=device)
-    batches = 0
-    for images, masks in _seg_batches(dataloader, preprocess, device):
+    n_batches = 0
+    for images, masks in _seg_batches(dataloader, preprocess, device) if batches is None else batches:
         optimizer.zero_grad(set_to_none=True)
         outputs = model(images)
         loss = criterion(outputs, masks)
@@ -82,24 +83,25 @@ def train_seg_epoch(model, dataloader, criterion, optimizer, device, epoch, num_
         optimizer.step()
         total += loss.detach().double()
         metrics.update(outputs, masks)
-        batches += 1
-    return {"loss": float(total) / max(batches, 1), "metrics": metrics.compute_all_metrics()}
+        n_batches += 1
+    return {"loss": float(total) / max(n_batches, 1), "metrics": metrics.compute_all_metrics()}
 
 
-def validate_seg_epoch(model, dataloader, criterion, device, num_classes, preprocess):
-    """Eval-mode pass (reference train.py:163-202): unweighted mean of the per-batch losses + device metrics."""
+def validate_seg_epoch(model, dataloader, criterion, device, num_classes, preprocess, *, batches=None):
+    """Eval-mode pass (reference train.py:163-202): unweighted mean of the per-batch losses + device metrics.
+    ``batches``: as in ``train_seg_epoch``."""
     from .metrics import SegmentationMetrics
     model.eval()
     metrics = SegmentationMetrics(num_classes)
     total = torch.zeros((), dtype=torch.float64, device=device)
-    batches = 0
+    n_batches = 0
     with torch.no_grad():
-        for images, masks in _seg_batches(dataloader, preprocess, device):
+        for images, masks in _seg_batches(dataloader, preprocess, device) if batches is None else batches:
             outputs = model(images)
             total += criterion(outputs, masks).detach().double()
             metrics.update(outputs, masks)
-            batches += 1
-    return {"loss": float(total) / max(batches, 1), "metrics": metrics.compute_all_metrics()}
+            n_batches += 1
+    return {"loss": float(total) / max(n_batches, 1), "metrics": metrics.compute_all_metrics()}
 
 
 def _print_epoch(epoch, tr, vr, seconds):
@@ -114,56 +116,40 @@ def _print_epoch(epoch, tr, vr, seconds):
     print(f"Epoch time: {seconds:.2f}s")
 
 
-def main(argv=None):
-    from . import SegmentationUNet, UNet
-    from .gear_dataset import GearPreprocess, collate_raw, get_gear_dataloaders, write_synthetic_gear
-    from .metrics import CombinedSegmentationLoss
-    from .train_utils import get_optimizer
-    from .utils import create_output_dirs, load_checkpoint, save_checkpoint
-
-    args = parse_args(argv)
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
+def require_gpu(args):
+    """The device of a seg CLI (train or eval); exits with the package's one-line message for a CPU device."""
     if args.device == "cpu" or not torch.cuda.is_available():
         raise SystemExit("this build computes only on an AMD GPU (libunet_hip.so); there is no CPU path")
     device = torch.device(args.device if args.device not in ("auto", "cuda") else "cuda")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     torch.cuda.set_device(device)
+    return device
 
-    if args.synthetic:
-        args.data_root = write_synthetic_gear(tempfile.mkdtemp(prefix="gear_syn_"), seed=args.seed)
-    stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
-    exp_dir = os.path.join(args.save_dir, f"gear_seg_{args.model}_{stamp}")
-    dirs = create_output_dirs(exp_dir)
-    print(f"Using device: {device}\nExperiment directory: {exp_dir}")
-    class_weights = [float(w) for w in args.class_weights.split(",")] if args.class_weights else None
-    with open(os.path.join(exp_dir, "args.json"), "w") as f:
-        json.dump(vars(args), f, indent=2)
 
-    size = (args.image_size, args.image_size)
-    train_loader, val_loader, _test_loader, num_classes = get_gear_dataloaders(
-        args.data_root, args.batch_size, size, args.num_workers, seed=args.seed)
-    if args.debug:
-        from torch.utils.data import DataLoader, Subset
-
-        def limit(loader, shuffle):
-            idx = random.sample(range(len(loader.dataset)), min(args.debug_samples, len(loader.dataset)))
-            return DataLoader(Subset(loader.dataset, idx), batch_size=args.batch_size, shuffle=shuffle,
-                              num_workers=args.num_workers, pin_memory=True, collate_fn=collate_raw)
-        train_loader, val_loader = limit(train_loader, True), limit(val_loader, False)
-    print(f"Number of classes: {num_classes}\nTrain samples: {len(train_loader.dataset)}\n"
-          f"Val samples: {len(val_loader.dataset)}")
-
+def build_seg_model(args, num_classes, device):
+    """SegmentationUNet / UNet of the seg CLIs' --model, --bilinear, --dropout and --precision."""
+    from . import SegmentationUNet, UNet
     if args.model == "seg_unet":
         model = SegmentationUNet(n_channels=3, n_classes=num_classes, bilinear=args.bilinear, dropout=args.dropout,
                                  precision=args.precision)
     else:
         model = UNet(n_channels=3, n_classes=num_classes, bilinear=args.bilinear, precision=args.precision)
-    model = model.to(device)
+    return model.to(device)
+
+
+def fit_segmentation(args, exp_dir, dirs, model, train_loader, val_loader, num_classes, device, train_batches,
+                     val_batches):
+    """The epoch loop, checkpoints and ``training_results.json`` shared by the Gear and KolektorSDD trainers (reference
+    train.py:333-400, train_kolektorsdd.py:370-452).  ``train_batches`` / ``val_batches``: loader -> iterable of
+    (images, masks) device batches."""
+    from .metrics import CombinedSegmentationLoss
+    from .train_utils import get_optimizer
+    from .utils import load_checkpoint, save_checkpoint
+
     total_params = sum(p.numel() for p in model.parameters())
     print(f"Total parameters: {total_params:,}")
+    class_weights = [float(w) for w in args.class_weights.split(",")] if args.class_weights else None
     criterion = CombinedSegmentationLoss(ce_weight=args.ce_weight, dice_weight=args.dice_weight,
                                          focal_weight=args.focal_weight, class_weights=class_weights)
     optimizer = get_optimizer(model, args.optimizer, args.learning_rate, args.weight_decay)
@@ -172,17 +158,17 @@ def main(argv=None):
         start_epoch = load_checkpoint(model, optimizer, args.resume, device)[0] + 1
         print(f"Resumed from epoch {start_epoch}")
 
-    train_pre = GearPreprocess(size, train=True, sync_mask=args.sync_mask, seed=args.seed)
-    eval_pre = GearPreprocess(size, train=False)
     train_losses, val_losses, best_val_miou = [], [], 0.0
     for epoch in range(start_epoch, args.epochs):
         t0 = time.time()
-        tr = train_seg_epoch(model, train_loader, criterion, optimizer, device, epoch, num_classes, train_pre)
+        tr = train_seg_epoch(model, train_loader, criterion, optimizer, device, epoch, num_classes, None,
+                             batches=train_batches(train_loader))
         train_seconds = time.time() - t0
         train_losses.append(tr["loss"])
         vr = None
         if epoch % args.val_freq == 0 or epoch == args.epochs - 1:
-            vr = validate_seg_epoch(model, val_loader, criterion, device, num_classes, eval_pre)
+            vr = validate_seg_epoch(model, val_loader, criterion, device, num_classes, None,
+                                    batches=val_batches(val_loader))
             val_losses.append(vr["loss"])
             if vr["metrics"]["mean_iou"] > best_val_miou:
                 best_val_miou = float(vr["metrics"]["mean_iou"])
@@ -200,6 +186,47 @@ def main(argv=None):
         json.dump(results, f, indent=2)
     print(f"Training completed!\nBest validation mIoU: {best_val_miou:.4f}\nResults saved to: {exp_dir}")
     return exp_dir
+
+
+def main(argv=None):
+    from .gear_dataset import GearPreprocess, collate_raw, get_gear_dataloaders, write_synthetic_gear
+    from .utils import create_output_dirs
+
+    args = parse_args(argv)
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    device = require_gpu(args)
+
+    if args.synthetic:
+        args.data_root = write_synthetic_gear(tempfile.mkdtemp(prefix="gear_syn_"), seed=args.seed)
+    stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
+    exp_dir = os.path.join(args.save_dir, f"gear_seg_{args.model}_{stamp}")
+    dirs = create_output_dirs(exp_dir)
+    print(f"Using device: {device}\nExperiment directory: {exp_dir}")
+    with open(os.path.join(exp_dir, "args.json"), "w") as f:
+        json.dump(vars(args), f, indent=2)
+
+    size = (args.image_size, args.image_size)
+    train_loader, val_loader, _test_loader, num_classes = get_gear_dataloaders(
+        args.data_root, args.batch_size, size, args.num_workers, seed=args.seed)
+    if args.debug:
+        from torch.utils.data import DataLoader, Subset
+
+        def limit(loader, shuffle):
+            idx = random.sample(range(len(loader.dataset)), min(args.debug_samples, len(loader.dataset)))
+            return DataLoader(Subset(loader.dataset, idx), batch_size=args.batch_size, shuffle=shuffle,
+                              num_workers=args.num_workers, pin_memory=True, collate_fn=collate_raw)
+        train_loader, val_loader = limit(train_loader, True), limit(val_loader, False)
+    print(f"Number of classes: {num_classes}\nTrain samples: {len(train_loader.dataset)}\n"
+          f"Val samples: {len(val_loader.dataset)}")
+
+    model = build_seg_model(args, num_classes, device)
+    train_pre = GearPreprocess(size, train=True, sync_mask=args.sync_mask, seed=args.seed)
+    eval_pre = GearPreprocess(size, train=False)
+    return fit_segmentation(args, exp_dir, dirs, model, train_loader, val_loader, num_classes, device,
+                            lambda loader: _seg_batches(loader, train_pre, device),
+                            lambda loader: _seg_batches(loader, eval_pre, device))
 
 
 if __name__ == "__main__":
