@@ -55,10 +55,6 @@ typedef struct unet_view {
 int32_t unet_abi_version(void);
 const char* unet_last_error(void);
 
-/* The UNET_* tuning variables are read once, at the first launch that consults them; this re-reads
- * them (same-process A/B tools such as tools/bench_layer.py --ab). */
-int32_t unet_tuning_reload(void);
-
 /* Data parallelism (no reference counterpart): CUs the persistent one-block-per-CU kernels leave free for
  * the RCCL all-reduce kernels that overlap the backward pass.  The statically partitioned conv / weight-gradient /
  * transposed-conv launchers size their grids by unet_get_cu_budget() = (multiprocessor count - reserved) rounded down

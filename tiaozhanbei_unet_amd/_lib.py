@@ -45,7 +45,6 @@ _i, _l, _f, _p, _z, _d = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 SIGNATURES = {
     "unet_abi_version": (_i, []),
     "unet_last_error": (C.c_char_p, []),
-    "unet_tuning_reload": (_i, []),
     "unet_set_reserved_cus": (_i, [_i]),
     "unet_get_cu_budget": (_i, []),
     "unet_debug_spin": (_i, [_i, _i, _i, _p]),

@@ -227,7 +227,7 @@ __global__ __launch_bounds__(512, 1) void convt_gemm_kernel(const GemmTParams P)
 }  // namespace
 
 bool unet_internal_convt_gemm_ok(int mode, int dtype, int n, int h, int w, int c_in, int c_out) {
-  if (dtype != UNET_BF16 || unet_tuning().convt_impl == '0' || unet_tuning().convt_impl == '2') return false;
+  if (dtype != UNET_BF16) return false;
   const long long M = (long long)n * h * w;
   const long long big = std::max(M * c_in * 2, M * 4 * c_out * 2);
   if (big >= 0x7FFFFFFFLL || (long long)c_in * 4 * c_out * 2 >= 0x7FFFFFFFLL) return false;

@@ -54,9 +54,9 @@ struct IgemmParams {
   const float* bn_scale;
   const float* bn_shift;
   const float* bn_mean;
-  int ws_stagger;   // conv3_ws16_kernel: the two waves of a SIMD issue their patch DMAs at opposite ends of a tile (UNET_WS_STG=0: off, 1: without the deferred stores)
   int co_il;        // conv3_pdma: channel tiles interleaved per pixel tile in the work order (1, 2 or 4; see pdma_item)
-  int pdma_stagger; // conv3_pdma (lock-step): DMA issues of a SIMD's two waves at opposite ends of a tap
+  int pdma_stagger; // conv3_pdma (lock-step): DMA issues of a SIMD's two waves at opposite ends of a tap; always 1 (a
+                    // run-time value on purpose: as a constant, hipcc gives conv3_pdma64x2_kernel 181 instead of 177 VGPRs)
   int pdma_dense;   // conv3_pdma: every destination view covers the frame at offset 0 (scalar output addressing)
   int pdma_dense_src; // conv3_pdma: every source view covers the frame at offset 0, one channel stride (scalar patch addressing)
 };
@@ -836,28 +836,27 @@ template <typename T, int BN, int KG>
 int32_t launch3(const IgemmParams& Pin, int kclass, hipStream_t s, int* stat_parts) {
   using C = Cfg3<T, BN, KG>;
   IgemmParams P = Pin;
-  auto kern = conv3_kernel<T, BN, KG>;
-  unet_set_max_lds(reinterpret_cast<const void*>(kern), C::LDS);
   const long long blocks = (long long)P.N * P.tilesY * P.tilesX * P.nCo;
   UNET_REQUIRE(blocks > 0 && blocks < (1LL << 31), UNET_ERR_UNSUPPORTED, "conv3: grid of %lld blocks", blocks);
   const double flops = 2.0 * P.N * P.H * P.W * (double)P.Cout * P.Ctot * 9;
   if constexpr (sizeof(T) == 2 && BN == 128 && KG == 4) {
-    // default: the 16x16x32 MFMA variant (up to 7 % faster in interleaved A/B runs: the chip holds a
-    // higher clock on that shape); UNET_CONV_VAR=0 selects the 32x32x16 kernel (tuning hook)
-    if (unet_tuning().conv_var != '0') {
-      using CM = Cfg3M<T, BN, KG>;
-      auto km = conv3m16_kernel<T, BN, KG>;
-      unet_set_max_lds(reinterpret_cast<const void*>(km), CM::LDS);
-      if (P.stats && stat_parts) *stat_parts = P.N * P.tilesY * P.tilesX;   // epilogue writes the BN partials
-      ProfScope prof(kclass, flops, s, "conv3m16_kernel");
-      hipLaunchKernelGGL(km, dim3((unsigned)blocks), dim3(256), CM::LDS, s, P);
-      return unet_check_launch("conv3m16_kernel");
-    }
+    // the 16x16x32 MFMA variant (up to 7 % faster than the 32x32x16 conv3_kernel in interleaved A/B runs: the chip
+    // holds a higher clock on that shape)
+    using CM = Cfg3M<T, BN, KG>;
+    auto km = conv3m16_kernel<T, BN, KG>;
+    unet_set_max_lds(reinterpret_cast<const void*>(km), CM::LDS);
+    if (P.stats && stat_parts) *stat_parts = P.N * P.tilesY * P.tilesX;   // epilogue writes the BN partials
+    ProfScope prof(kclass, flops, s, "conv3m16_kernel");
+    hipLaunchKernelGGL(km, dim3((unsigned)blocks), dim3(256), CM::LDS, s, P);
+    return unet_check_launch("conv3m16_kernel");
+  } else {
+    auto kern = conv3_kernel<T, BN, KG>;
+    unet_set_max_lds(reinterpret_cast<const void*>(kern), C::LDS);
+    P.stats = nullptr;
+    ProfScope prof(kclass, flops, s, "conv3_kernel");
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), C::LDS, s, P);
+    return unet_check_launch("conv3_kernel");
   }
-  P.stats = nullptr;
-  ProfScope prof(kclass, flops, s, "conv3_kernel");
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), C::LDS, s, P);
-  return unet_check_launch("conv3_kernel");
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -916,7 +915,7 @@ __device__ __forceinline__ void pdma_item(int wk, int n_tiles, int c, int& cot, 
   cot = sg * c + (rem - tile * c);
 }
 
-template <int BN, bool PAIR = false, bool ROW3 = false>
+template <int BN, bool PAIR = false>
 struct CfgP {
   static constexpr int TH = 16, TW = 16, HH = 18, HW = 18;
   static constexpr int PSTR = 160, PPP = 10, RS = HW * PSTR;
@@ -924,10 +923,8 @@ struct CfgP {
   static constexpr int A_BYTES = A_INSTR * 1024;
   static constexpr int NDA = (A_INSTR + 7) / 8;                      // 7 per wave
   // PAIR (BN = 64): a ring slot holds the slabs of TWO consecutive taps (a step = two taps between barriers)
-  // ROW3 (BN = 64): a slot holds the three slabs of a tap ROW, and the ring has two slots (the next step's slabs are fetched
-  // during the current step)
-  static constexpr int W_BYTES = (ROW3 ? 3 : (PAIR ? 2 : 1)) * BN * 128, NDW = W_BYTES / 1024 / 8; // 2 (BN 128, PAIR), 3 (ROW3) or 1 (BN 64) per wave
-  static constexpr int NSLOT = ROW3 ? 2 : 3;
+  static constexpr int W_BYTES = (PAIR ? 2 : 1) * BN * 128, NDW = W_BYTES / 1024 / 8; // 2 (BN 128, PAIR) or 1 (BN 64) per wave
+  static constexpr int NSLOT = 3;
   // the weight ring sits FIRST: slot * W_BYTES (<= 32 KiB) then folds into the 16-bit offset field of the fragment
   // ds_reads (behind the patches, at 102 KiB, every read cost a v_add and the tap a spilled-SGPR v_readlane)
   static constexpr int W_BASE = 0;
@@ -958,14 +955,10 @@ struct CfgP {
 // (9 steps; step 4 straddles the chunks): one barrier, one counted wait and one DMA burst per 32 MFMAs, as in the
 // 128-channel kernel; a ring slot holds both taps' weight slabs (16 KiB, the 128-channel ring), the second tap's
 // fragments are fetched behind the first tap's MFMAs.  Same accumulation order, bit-identical outputs.
-// ROW3 (BN = 64, any number of chunks): a step = the three taps of one tap ROW (48 MFMAs per wave between barriers, three
-// steps per chunk); a two-slot weight ring, every wave issues its DMAs in front of its MFMAs (with this much work per step
-// the placement of the burst no longer matters: UNET_PDMA_STG 0 / 1 are +-0 on the pair kernel).
-template <int BN, bool BNBWD = false, bool PP = false, bool PAIR = false, bool ROW3 = false>
+template <int BN, bool BNBWD = false, bool PP = false, bool PAIR = false>
 __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
   static_assert(!PAIR || (BN == 64 && !PP), "pair steps: the lock-step 64-channel kernel");
-  static_assert(!ROW3 || (BN == 64 && !PP && !PAIR), "row steps: the lock-step 64-channel kernel");
-  using C = CfgP<BN, PAIR, ROW3>;
+  using C = CfgP<BN, PAIR>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef __attribute__((address_space(3))) void lds_void;
   constexpr unsigned OOB = 0xFFFFFFF0u;
@@ -1205,43 +1198,6 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
     mm(1, c3, g1);
   };
 
-  // ROW3: the slabs of taps 3r .. 3r+2 of `chunk` into ring slot `slot`; the three taps back to back, fragments two
-  // half-steps ahead of their MFMAs
-  auto dma_w3 = [&](unsigned wbase, int chunk, int r, int slot, bool live) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const unsigned soff = live ? wbase + (unsigned)(3 * r + j) * w_tap_stride + (unsigned)chunk * 128 : 0u;
-      char* dst = live ? smem + C::W_BASE + slot * C::W_BYTES + j * (BN * 128) + wave * 1024 : smem + C::DUMMY;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_void*)dst, 16, live ? w_g[0] : OOB, soff, 0, 0);
-    }
-  };
-  auto compute3 = [&](int pbuf, int r, int slot) {
-    const char* pa = smem + C::W_BASE + slot * C::W_BYTES;
-    const char* pb = smem + pbuf + r * C::RS;
-    bf16x8 fbq[3][4], faq[3][2];
-    auto load = [&](int h, int q) {              // half-step h = 2 * tap + ks into fragment set q
-      const int tj = h >> 1, ks = h & 1;
-#pragma unroll
-      for (int pt = 0; pt < 4; ++pt) fbq[q][pt] = *reinterpret_cast<const bf16x8*>(pb + tj * C::PSTR + boff[pt] + ks * 64);
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct) faq[q][ct] = *reinterpret_cast<const bf16x8*>(pa + tj * (BN * 128) + aoff[ct][ks]);
-    };
-    load(0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    load(1, 1);
-#pragma unroll
-    for (int h = 0; h < 6; ++h) {
-      const int q = h % 3;
-      if (h + 2 < 6) load(h + 2, (h + 2) % 3);
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int pt = 0; pt < 4; ++pt)
-          acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(faq[q][ct], fbq[q][pt], acc[ct][pt], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-
   // PP: the same tap as two halves -- every fragment of the tap into registers, then nothing but MFMAs
   bf16x8 fa[2][C::CT], fb[2][4];
   auto load_frags = [&](int pbuf, int toff, int slot) {
@@ -1269,9 +1225,7 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
   setup_dma(logical);
 #pragma unroll
   for (int j = 0; j < C::NDA; ++j) dma_patch(0, j, 0, true);
-  if constexpr (ROW3) {
-    dma_w3(d_wbase, 0, 0, 0, true);
-  } else if constexpr (PAIR) {
+  if constexpr (PAIR) {
     dma_w2(d_wbase, 0, 0, true);
     dma_w2(d_wbase, 2, 1, true);
   } else {
@@ -1290,7 +1244,6 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
   const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
   int pbuf_i = 0;                                 // patch buffer of the chunk being computed
-  int wslot = 0;                                  // ROW3: ring slot of the step being computed
   bool after_epilogue = false;
   const bool late_dma = !PP && P.pdma_stagger && __builtin_amdgcn_readfirstlane(wave) < 4;
   // BatchNorm partial sums of this lane's outputs (4 channels x CT tiles, 2 statistics).  Block mode (P.zdiv: every
@@ -1334,38 +1287,7 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[a][b][q] = 0.f;
 
-    if constexpr (ROW3) {
-      // three steps (tap rows) per chunk.  W(step) was issued during the previous step, behind that step's patch pieces: the
-      // youngest operations in flight [+ the output stores of the previous item's epilogue] -> wait for everything older
-      for (int c = 0; c < nchunks; ++c) {
-        const bool last = c + 1 == nchunks;
-        if (last) {                                // from here on the DMA stream belongs to the next work item
-          d_live = has_next;
-          if (has_next) setup_dma(wk + G);
-        }
-        const int pbuf = C::A_BASE + pbuf_i * C::A_BYTES;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          if (r == 0 && c == 0 && after_epilogue) {
-            if (P.stats) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::NST + 1) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::NST) : "memory");
-          } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          }
-          __builtin_amdgcn_s_barrier();
-          const int j0 = r == 0 ? 0 : (r == 1 ? 3 : 5), nj = r == 0 ? 3 : 2;       // patch pieces 0-2 | 3,4 | 5,6 of the next chunk
-#pragma unroll
-          for (int q = 0; q < 3; ++q)
-            if (q < nj) dma_patch(last ? 0 : c + 1, j0 + q, pbuf_i ^ 1, last ? d_live : true);
-          if (r < 2) dma_w3(c_wbase, c, r + 1, wslot ^ 1, true);
-          else if (!last) dma_w3(c_wbase, c + 1, 0, wslot ^ 1, true);
-          else dma_w3(d_wbase, 0, 0, wslot ^ 1, d_live);
-          compute3(pbuf, r, wslot);
-          wslot ^= 1;
-        }
-        pbuf_i ^= 1;
-      }
-    } else if constexpr (PAIR) {
+    if constexpr (PAIR) {
       // 9 steps of two taps; chunk 0 lives in patch buffer 0, chunk 1 in buffer 1 (nchunks == 2: the launcher's condition).
       // Patch pieces: steps 0-3 bring THIS item's chunk 1 (2, 2, 2, 1 pieces per wave), steps 5-8 the NEXT item's chunk 0
       // (buffer 0 is read for the last time by step 4); the weights of step d + 2 follow the pieces of step d.
@@ -1503,9 +1425,9 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
 #endif
         // This tap's DMA issues (a patch piece of the next chunk, the weight slab two taps ahead).  The two waves of a SIMD
         // (w, w + 4) issue at opposite ends of the tap -- waves 4-7 here, waves 0-3 behind their MFMAs -- so that one of
-        // them has MFMAs to issue while the other sits in its burst (UNET_PDMA_STG=0: all eight behind the barrier, as in
-        // round 2).  The per-wave ORDER of vector-memory operations is unchanged, so every counted vmcnt above still holds;
-        // a slot is refilled after the barrier that follows its last reads either way.
+        // them has MFMAs to issue while the other sits in its burst (+3..8 % on these layers over all eight behind the
+        // barrier, profiles/r03_pdma_stagger.txt).  The per-wave ORDER of vector-memory operations is unchanged, so every
+        // counted vmcnt above still holds; a slot is refilled after the barrier that follows its last reads either way.
         auto issue_dma = [&]() {
           if (tap < C::NDA) dma_patch(last ? 0 : c + 1, tap, pbuf_i ^ 1, last ? d_live : true);
           if (tap + 2 < 9) dma_w(c_wbase, c, tap + 2, (tap + 2) % 3, true);
@@ -1779,8 +1701,6 @@ __global__ __launch_bounds__(512, 1) void conv3_pp128_bnbwd_kernel(const IgemmPa
 __global__ __launch_bounds__(512, 1) void conv3_pp64_bnbwd_kernel(const IgemmParams P) { conv3_pdma_body<64, true, true>(P); }
 __global__ __launch_bounds__(512, 1) void conv3_pdma64x2_kernel(const IgemmParams P) { conv3_pdma_body<64, false, false, true>(P); }
 __global__ __launch_bounds__(512, 1) void conv3_pdma64x2_bnbwd_kernel(const IgemmParams P) { conv3_pdma_body<64, true, false, true>(P); }
-__global__ __launch_bounds__(512, 1) void conv3_pdma64x3_kernel(const IgemmParams P) { conv3_pdma_body<64, false, false, false, true>(P); }
-__global__ __launch_bounds__(512, 1) void conv3_pdma64x3_bnbwd_kernel(const IgemmParams P) { conv3_pdma_body<64, true, false, false, true>(P); }
 
 #ifdef PDMA_STAMPS
 void* g_pdma_debug = nullptr;      // (also read by wgrad.hip)
@@ -1794,30 +1714,26 @@ int32_t launch_pdma(const IgemmParams& Pin, int kclass, hipStream_t s, int* stat
   P.tilesX = cdiv(P.W, C::TW);
   P.tilesY = cdiv(P.H, C::TH);
   const bool bnbwd = P.bn_y != nullptr;
-  // the ping-pong schedule wins where a work item is long (>= 8 chunks: +2 % at 512, +6 % at 1024 input channels) and
-  // loses where the epilogue -- run once per half, each exposed -- is a large part of an item (-10 % at 128 channels);
-  // UNET_PDMA_PP=0 / 1 force lock-step / ping-pong
-  P.pdma_dense = unet_tuning().pdma_stg != '2';             // (UNET_PDMA_STG=2: the per-lane output geometry, for A/B)
-  P.pdma_dense_src = unet_tuning().pdma_stg != '2' && unet_tuning().pdma_stg != '4';      // (4: per-lane patch geometry only)
+  P.pdma_stagger = 1;
+  P.pdma_dense = 1;
+  P.pdma_dense_src = 1;
   for (int k = 0; k < 2; ++k)
     if (P.src[k].p && P.src[k].C > 0 &&
         (P.src[k].oy || P.src[k].ox || P.src[k].H != P.H || P.src[k].W != P.W || P.src[k].C != P.src[0].C))
       P.pdma_dense_src = 0;
   for (int q = 0; q < 2; ++q)
     if (P.dst[q].p && (P.dst[q].oy || P.dst[q].ox || P.dst[q].H != P.H || P.dst[q].W != P.W)) P.pdma_dense = 0;
-  P.pdma_stagger = unet_tuning().pdma_stg != '0';           // default on: +3..8 % on the lock-step layers (profiles/r03_pdma_stagger.txt)
-  const char ppv = unet_tuning().pdma_pp;
-  const bool pp = ppv == '1' || (ppv != '0' && BN == 128 && P.Ctot >= 512);
-  // two taps per step for 64-channel tiles over exactly two chunks (UNET_PDMA_PAIR=0: one tap per step, for A/B)
-  const bool row3 = BN == 64 && !pp && unet_tuning().pdma_pair == '3';          // UNET_PDMA_PAIR=3: a tap row per step (A/B)
-  const bool pair = BN == 64 && !pp && !row3 && P.Ctot == 128 && unet_tuning().pdma_pair != '0';
-  auto kern = row3 ? (bnbwd ? conv3_pdma64x3_bnbwd_kernel : conv3_pdma64x3_kernel)
-              : pair ? (bnbwd ? conv3_pdma64x2_bnbwd_kernel : conv3_pdma64x2_kernel)
+  // the ping-pong schedule wins where a work item is long (>= 8 chunks: +2 % at 512, +6 % at 1024 input channels) and
+  // loses where the epilogue -- run once per half, each exposed -- is a large part of an item (-10 % at 128 channels)
+  const bool pp = BN == 128 && P.Ctot >= 512;
+  // two taps per step for 64-channel tiles over exactly two chunks
+  const bool pair = BN == 64 && P.Ctot == 128;
+  auto kern = pair ? (bnbwd ? conv3_pdma64x2_bnbwd_kernel : conv3_pdma64x2_kernel)
               : pp ? (bnbwd ? (BN == 128 ? conv3_pp128_bnbwd_kernel : conv3_pp64_bnbwd_kernel)
                             : (BN == 128 ? conv3_pp128_kernel : conv3_pp64_kernel))
                    : (bnbwd ? (BN == 128 ? conv3_pdma128_bnbwd_kernel : conv3_pdma64_bnbwd_kernel)
                             : (BN == 128 ? conv3_pdma128_kernel : conv3_pdma64_kernel));
-  const int lds_bytes = row3 ? CfgP<64, false, true>::LDS : (pair ? CfgP<64, true>::LDS : C::LDS);
+  const int lds_bytes = pair ? CfgP<64, true>::LDS : C::LDS;
   unet_set_max_lds(reinterpret_cast<const void*>(kern), lds_bytes);
   const long long work = (long long)P.N * P.tilesY * P.tilesX * P.nCo;
   UNET_REQUIRE(work > 0 && work < (1LL << 30), UNET_ERR_UNSUPPORTED, "conv3_pdma: %lld work items", work);
@@ -1829,13 +1745,9 @@ int32_t launch_pdma(const IgemmParams& Pin, int kclass, hipStream_t s, int* stat
   const int blocks = (int)std::min<long long>(unet_cu_budget(), cdiv64(work, 8) * 8);   // one per (non-reserved) CU, a multiple of 8 (XCDs)
   const double flops = 2.0 * P.N * P.H * P.W * (double)P.Cout * P.Ctot * 9;
   const long long n_tiles = (long long)P.N * P.tilesY * P.tilesX;
-  // UNET_CONV_XCD: channel tiles interleaved per pixel tile (default: up to 4; 1 = channel-tile-major as in round 2)
-  {
-    const char xv = unet_tuning().conv_xcd;
-    const int want = xv == '1' ? 1 : (xv == '2' ? 2 : 4);
-    P.co_il = 1;
-    while (P.co_il * 2 <= want && P.nCo % (P.co_il * 2) == 0 && blocks % (P.co_il * 2 * 8) == 0) P.co_il *= 2;
-  }
+  // channel tiles interleaved per pixel tile: up to 4
+  P.co_il = 1;
+  while (P.co_il * 2 <= 4 && P.nCo % (P.co_il * 2) == 0 && blocks % (P.co_il * 2 * 8) == 0) P.co_il *= 2;
   // block-mode statistics: a block stays on one channel tile for whole super-groups and the co_il blocks of a row cover them all
   P.zdiv = (P.stats && (n_tiles * P.co_il) % blocks == 0) ? 1 : 0;
   if (P.stats && stat_parts) *stat_parts = P.zdiv ? blocks / P.co_il : (int)n_tiles;
@@ -1887,15 +1799,17 @@ struct CfgWS {
 // sums next to its 144 weight registers, so every tile's 2 x 16 per-lane values are reduced over the 16 lanes of a DPP
 // row at once (4 VALU adds each), the four row leaders leave them in an LDS slot, and 128 threads keep the block's
 // running total of their (statistic, channel) -- one ordered partial per block: deterministic.
-// ST ("stagger"): a tile is two phases with a barrier after each -- M: the DMA issue of the tile two ahead + the 72
-// MFMAs (+ the counted wait for the NEXT tile's patch), E: the tile's epilogue (pack, statistics, stores) + the next
-// tile's output geometry -- and waves 4-7 run one barrier behind waves 0-3, so on every SIMD one wave's MFMA phase
+// ST ("stagger", the statistics form STATS == 1): a tile is two phases with a barrier after each -- M: the DMA issue of
+// the tile two ahead + the 72 MFMAs (+ the counted wait for the NEXT tile's patch), E: the tile's epilogue (pack,
+// statistics, stores) + the next tile's output geometry -- and waves 4-7 run one barrier behind waves 0-3, so on every SIMD one wave's MFMA phase
 // covers its partner's VALU/store phase (in lock-step all eight did their epilogues together, then fought over the
 // matrix pipe: 40 % MFMA busy).  Waves 0-3 own output channels 0-31, waves 4-7 channels 32-63 (a half's statistics
-// stay inside the half).
-template <bool ACC, int STATS = 0, bool ST = false>
+// stay inside the half).  It pays where the epilogue is long (+3.5 % on 64 -> 64 @256x256) and costs 20 % where it is
+// short (plain forward / data gradient: the DMA burst of a half then lands inside the other half's MFMA phase).
+template <bool ACC, int STATS = 0>
 __global__ __launch_bounds__(512, 1) void conv3_ws_kernel(const IgemmParams P, int tiles_per_block) {
   using C = CfgWS;
+  constexpr bool ST = STATS == 1;
   static_assert(!(ACC && STATS), "the gradient fan-in form carries no statistics");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2077,13 +1991,6 @@ __global__ __launch_bounds__(512, 1) void conv3_ws_kernel(const IgemmParams P, i
     __builtin_amdgcn_s_barrier();
     if (grp) __builtin_amdgcn_s_barrier();                                  // the stagger
   }
-#ifdef PDMA_STAMPS
-  unsigned long long ws_st[5] = {0, 0, 0, 0, 0}, ws_prev = __builtin_amdgcn_s_memtime(), ws_dma_sum = 0;
-  const unsigned long long ws_t0 = ws_prev, ws_r0 = __builtin_amdgcn_s_memrealtime();
-#define WS_STAMP(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ws_st[i] += t_ - ws_prev; ws_prev = t_; }
-#else
-#define WS_STAMP(i)
-#endif
   for (int tile = t_begin; tile < t_end; ++tile) {
     const int k = tile - t_begin;
     const int cur = k % C::NBUF;
@@ -2155,10 +2062,6 @@ __global__ __launch_bounds__(512, 1) void conv3_ws_kernel(const IgemmParams P, i
       return *reinterpret_cast<const bf16x8*>(pb + boff[pt] + (tap / 3) * C::RS + (tap % 3) * C::PSTR + kg * 32);
     };
     bf16x8 ring[DEPTH + 1][C::PXT];
-#ifdef PDMA_STAMPS
-    unsigned long long ws_dma = 0;
-    if (ST) ws_dma = __builtin_amdgcn_s_memtime() - ws_prev;
-#endif
 #pragma unroll
     for (int i = 0; i < DEPTH; ++i)
 #pragma unroll
@@ -2182,19 +2085,13 @@ __global__ __launch_bounds__(512, 1) void conv3_ws_kernel(const IgemmParams P, i
       asm volatile("s_waitcnt vmcnt(%4)" : "+v"(yv[0][0]), "+v"(yv[0][1]), "+v"(yv[1][0]), "+v"(yv[1][1]) : "n"(C::NDMA));
     }
     if constexpr (ST) {
-#ifdef PDMA_STAMPS
-      ws_dma_sum += ws_dma;
-#endif
       // end of the M phase: the NEXT tile's patch (issued one tile ago) has landed; younger than it: the previous
       // tile's stores, this tile's y loads and the patch just issued
-      WS_STAMP(0)
       if (k >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST + NY + C::NDMA) : "memory");
       else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NY + C::NDMA) : "memory");
-      WS_STAMP(1)
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      WS_STAMP(2)
     }
     // ---- epilogue for this tile: exactly NST buffer stores per wave (OOB offset = dropped).  Per 16-channel group gp
     // the two 4-row runs of a lane (t = 0: rows 16gp+4hh.., t = 1: +8) are finished one after the other so that only
@@ -2293,22 +2190,11 @@ __global__ __launch_bounds__(512, 1) void conv3_ws_kernel(const IgemmParams P, i
       if (k >= 1) take_slots(k - 1);
       if (next_in_flight) geometry();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this tile's slot writes, before the half's barrier
-      WS_STAMP(3)
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      WS_STAMP(4)
     }
   }
-#ifdef PDMA_STAMPS
-  if (ST && STATS != 2 && P.bn_mean && lane == 0) {
-    unsigned long long* o = (unsigned long long*)P.bn_mean + ((size_t)(blockIdx.x & 255) * 8 + wave) * 8;
-    for (int i = 0; i < 5; ++i) o[i] = ws_st[i];
-    o[5] = (unsigned long long)(t_end - t_begin);
-    o[7] = ws_dma_sum;
-    o[6] = ((__builtin_amdgcn_s_memtime() - ws_t0) << 20) / (__builtin_amdgcn_s_memrealtime() - ws_r0 + 1);
-  }
-#endif
   if constexpr (ST) { if (!grp) __builtin_amdgcn_s_barrier(); }    // pairs with the stagger barrier of waves 4-7
   if constexpr (STATS != 0) {
     // the last tile's slots, then ONE partial per block
@@ -2385,12 +2271,12 @@ __global__ __launch_bounds__(512, 1) void conv3_ws16_kernel(const IgemmParams P,
   // (the gradient fan-in form keeps every wave's DMAs in front: its old-value loads are builtin loads, whose
   //  compiler-placed wait would drain DMAs issued behind them; the fused BatchNorm-backward form too: its y loads would
   //  need a vmcnt(0) in front of the late burst and the extra code path costs it 6 more spills -- measured 605 -> 828 us/step)
-  const bool late = !ACC && STATS != 2 && P.ws_stagger && __builtin_amdgcn_readfirstlane(wave) < 4;
+  const bool late = !ACC && STATS != 2 && __builtin_amdgcn_readfirstlane(wave) < 4;
   // ... and the other half (waves 4-7) keeps a tile's packed results in registers across the barrier and stores them at
   // the top of the NEXT tile, behind its DMA burst: every vector-memory instruction of a wave is then issued while its
   // SIMD partner runs MFMAs (a store or DMA that waits for a queue slot stalls the wave that issues it, and at the old
-  // tile end both waves of a SIMD stalled together).  UNET_WS_STG=1: the DMA placement without the deferred stores.
-  const bool defer = !ACC && STATS != 2 && P.ws_stagger >= 2 && __builtin_amdgcn_readfirstlane(wave) >= 4;
+  // tile end both waves of a SIMD stalled together).
+  const bool defer = !ACC && STATS != 2 && __builtin_amdgcn_readfirstlane(wave) >= 4;
 
   // ---- this wave's weights -> registers: A fragment (tile ct, tap, ks) = W[ch0 + 16ct + l15][tap][32ks + 8kb .. +7]
   bf16x8 wreg[2][18];
@@ -2806,23 +2692,16 @@ __global__ __launch_bounds__(512, 1) void conv3_ws16_kernel(const IgemmParams P,
 
 int32_t launch_ws(IgemmParams P, int kclass, hipStream_t s, int* stat_parts) {
   using C = CfgWS;
-  // (UNET_WS_STATS=0: statistics by the streaming pass)
-  const bool stats_ok = unet_tuning().ws_stats != '0' && !P.accumulate && P.dst_split == P.Cout &&
+  const bool stats_ok = !P.accumulate && P.dst_split == P.Cout &&
                         P.dst[0].oy == 0 && P.dst[0].ox == 0 && P.dst[0].H == P.H && P.dst[0].W == P.W;
   const int mode = P.bn_y ? 2 : ((P.stats && stats_ok) ? 1 : 0);
   UNET_REQUIRE(mode != 2 || stats_ok, UNET_ERR_UNSUPPORTED, "conv3_ws: fused BatchNorm backward needs one dense destination");
-  // the staggered schedule pays where the epilogue is long (the statistics forms: +3.5 % on 64 -> 64 @256x256) and costs
-  // 20 % where it is short (plain forward / data gradient: the DMA burst of a half then lands inside the other half's
-  // MFMA phase); UNET_WS_ST=0 / 1 force lock-step / staggered, 3 = staggered for the BatchNorm-backward form too
-  const char stv = unet_tuning().ws_st;
-  // default: the 16x16x32 kernel (conv3_ws16_kernel); UNET_WS_MFMA=3 selects the 32x32x16 one (and its staggered forms)
-  // (every form of it is spill-free -- tools/check_dpp_hazards.py asserts that; 18.87 -> 18.71 ms per step when it came in)
-  P.ws_stagger = unet_tuning().ws_stg == '0' ? 0 : (unet_tuning().ws_stg == '1' ? 1 : 2);
-  const bool old32 = unet_tuning().ws_mfma == '3';
+  // dense 16-aligned frames: the 16x16x32 kernel (conv3_ws16_kernel; every form of it is spill-free --
+  // tools/check_dpp_hazards.py asserts that; 18.87 -> 18.71 ms per step when it came in)
   bool dense16 = P.H % 16 == 0 && P.W % 16 == 0;
   for (int q = 0; q < 2; ++q)
     if (P.dst[q].p && (P.dst[q].oy || P.dst[q].ox || P.dst[q].H != P.H || P.dst[q].W != P.W)) dense16 = false;
-  if (!old32 && dense16) {          // (ragged frames / offset views: conv3_ws_kernel's per-lane geometry)
+  if (dense16) {          // (ragged frames / offset views: conv3_ws_kernel's per-lane geometry)
     if (!P.dst[1].p) P.dst[1] = P.dst[0];         // no lane stores to it (dst_split == Cout); saves the kernel a select per tile
     auto k16 = P.accumulate ? conv3_ws16_kernel<true, 0>
                             : (mode == 2 ? conv3_ws16_kernel<false, 2> : (mode == 1 ? conv3_ws16_kernel<false, 1> : conv3_ws16_kernel<false, 0>));
@@ -2846,13 +2725,8 @@ int32_t launch_ws(IgemmParams P, int kclass, hipStream_t s, int* stat_parts) {
     hipLaunchKernelGGL(k16, dim3((unsigned)(ranges * nCg16)), dim3(512), CfgWS16::LDS, s, P, tpb16);
     return unet_check_launch("conv3_ws16_kernel");
   }
-  const bool st = stv == '1' || (stv != '0' && (mode == 1 || (mode == 2 && stv == '3')));
-  auto kern = st ? (P.accumulate ? conv3_ws_kernel<true, 0, true>
-                                 : (mode == 2 ? conv3_ws_kernel<false, 2, true>
-                                              : (mode == 1 ? conv3_ws_kernel<false, 1, true> : conv3_ws_kernel<false, 0, true>)))
-                 : (P.accumulate ? conv3_ws_kernel<true, 0>
-                                 : (mode == 2 ? conv3_ws_kernel<false, 2>
-                                              : (mode == 1 ? conv3_ws_kernel<false, 1> : conv3_ws_kernel<false, 0>)));
+  auto kern = P.accumulate ? conv3_ws_kernel<true, 0>
+                           : (mode == 2 ? conv3_ws_kernel<false, 2> : (mode == 1 ? conv3_ws_kernel<false, 1> : conv3_ws_kernel<false, 0>));
   P.tilesX = cdiv(P.W, C::WTW);
   P.tilesY = cdiv(P.H, C::WTH);
   const long long tiles = (long long)P.N * P.tilesY * P.tilesX;
@@ -2864,9 +2738,6 @@ int32_t launch_ws(IgemmParams P, int kclass, hipStream_t s, int* stat_parts) {
   const double flops = 2.0 * P.N * P.H * P.W * (double)P.Cout * P.Ctot * 9;
   if (mode == 0) P.stats = nullptr;               // (statistics, if wanted, by the caller's streaming pass)
   if (stat_parts) *stat_parts = mode ? (int)ranges8 : 0;          // one ordered partial per tile range
-#ifdef PDMA_STAMPS
-  if (mode != 2) P.bn_mean = (const float*)g_pdma_debug;
-#endif
   ProfScope prof(kclass, flops, s, mode == 2 ? "conv3_ws_bnbwd_kernel" : "conv3_ws_kernel");
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), C::LDS, s, P, tpb);
   return unet_check_launch("conv3_ws_kernel");
@@ -3377,22 +3248,17 @@ int32_t dispatch(IgemmParams& P, int kclass, hipStream_t s, int* stat_parts = nu
   P.nCo = P.Cout / (big ? 128 : 64);
   P.tilesX = cdiv(P.W, TW);
   P.tilesY = cdiv(P.H, TH);
-  const char impl = unet_tuning().conv_impl;    // UNET_CONV_IMPL: '0' = generic igemm_kernel, '2' no weight-stationary, '3' register-staged
   const bool small = planes_fit_32bit<T>(P);
-  const bool use3 = small && impl != '0';
   if constexpr (TAPS == 9 && sizeof(T) == 2) {
-    // 64-channel inputs: weight-stationary streaming kernel (impl "2" forces it off)
-    const bool ws_ok = small && P.Ctot == 64 && P.src[1].C == 0 && impl != '0' && impl != '2';
-    if (ws_ok) return launch_ws(P, kclass, s, stat_parts);
-  }
-  if constexpr (TAPS == 9 && sizeof(T) == 2) {
+    // 64-channel inputs: weight-stationary streaming kernel
+    if (small && P.Ctot == 64 && P.src[1].C == 0) return launch_ws(P, kclass, s, stat_parts);
     // deep layers (>= 4 input chunks: below that the un-overlapped prologue of the one block per CU costs more
-    // than it saves): both operands by LDS-DMA, 512-thread blocks (impl "3" = the register-staged kernels)
-    const bool dma_ok = small && k4 && P.Ctot >= 128 && P.H % 16 == 0 && P.W % 16 == 0 && impl != '0' && impl != '3';
+    // than it saves): both operands by LDS-DMA, 512-thread blocks
+    const bool dma_ok = small && k4 && P.Ctot >= 128 && P.H % 16 == 0 && P.W % 16 == 0;
     if (dma_ok) return big ? launch_pdma<128>(P, kclass, s, stat_parts) : launch_pdma<64>(P, kclass, s, stat_parts);
   }
   if constexpr (TAPS == 9) {
-    if (!use3 || P.Ctot < 2 * CK4) {
+    if (!small || P.Ctot < 2 * CK4) {
       if (big) return k4 ? launch<T, TAPS, 128, 4>(P, kclass, s) : launch<T, TAPS, 128, 1>(P, kclass, s);
       return k4 ? launch<T, TAPS, 64, 4>(P, kclass, s) : launch<T, TAPS, 64, 1>(P, kclass, s);
     }
@@ -3488,7 +3354,7 @@ extern "C" int32_t unet_conv3x3_stats(int32_t dtype, int32_t n, int32_t h, int32
   P.w = (const char*)w_packed;
   P.dst_split = c_out;
   P.imul = 1; P.gtaps = 1; P.omul = 1; P.nZ = 1;
-  P.stats = unet_tuning().fused_stats == '0' ? nullptr : partial;      // (UNET_FUSED_STATS=0: always the streaming pass)
+  P.stats = partial;
   hipStream_t s = (hipStream_t)stream;
   int parts = 0;
   int32_t rc;
@@ -3513,14 +3379,12 @@ inline bool dgrad_bnrelu_pdma_ok(int dtype, int n, int h, int w, int c_in_gemm, 
 // 64 -> 64 (the full-resolution level): the weight-stationary streaming kernel, any frame size
 inline bool dgrad_bnrelu_ws_ok(int dtype, int n, int h, int w, int c_in_gemm, int c_out_gemm) {
   (void)n;
-  return dtype == UNET_BF16 && c_in_gemm == 64 && c_out_gemm == 64 && (long long)h * w * 64 * 2 < 0x7FFFFFFFLL &&
-         unet_tuning().ws_stats != '0';
+  return dtype == UNET_BF16 && c_in_gemm == 64 && c_out_gemm == 64 && (long long)h * w * 64 * 2 < 0x7FFFFFFFLL;
 }
 }  // namespace
 
 extern "C" int32_t unet_conv3x3_dgrad_bnrelu_supported(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c_dy,
                                                        int32_t c_dx) {
-  if (unet_tuning().dgrad_bn == '0') return 0;            // (UNET_DGRAD_BN=0: never)
   return (dgrad_bnrelu_pdma_ok(dtype, n, h, w, c_dy, c_dx) || dgrad_bnrelu_ws_ok(dtype, n, h, w, c_dy, c_dx)) ? 1 : 0;
 }
 
@@ -3567,8 +3431,7 @@ extern "C" int32_t unet_convt2x2_fwd(int32_t dtype, int32_t n, int32_t h, int32_
   UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_convt2x2_fwd: bad dims");
   {
     const long long out_bytes = (long long)n * 4 * h * w * c_out * 2;
-    if (dtype == UNET_BF16 && c_in == 2 * c_out && (c_in == 128 || c_in == 256) && out_bytes < 0x7FFFFFFFLL &&
-        unet_tuning().convt_impl != '0') {                     // (UNET_CONVT_IMPL=0: generic igemm path)
+    if (dtype == UNET_BF16 && c_in == 2 * c_out && (c_in == 128 || c_in == 256) && out_bytes < 0x7FFFFFFFLL) {
       ConvTParams T{(const char*)x, (char*)y, (const char*)w_packed, bias, n, h, w, c_out, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
       return c_in == 128 ? launch_convt_ws<128>(T, (hipStream_t)stream) : launch_convt_ws<256>(T, (hipStream_t)stream);
     }
@@ -3600,8 +3463,7 @@ extern "C" int32_t unet_convt2x2_dgrad(int32_t dtype, int32_t n, int32_t h, int3
   UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_convt2x2_dgrad: bad dims");
   {
     const long long in_bytes = (long long)n * 4 * h * w * c_out * 2;
-    if (dtype == UNET_BF16 && c_in == 2 * c_out && (c_out == 64 || c_out == 128) && in_bytes < 0x7FFFFFFFLL &&
-        unet_tuning().convt_impl != '0') {
+    if (dtype == UNET_BF16 && c_in == 2 * c_out && (c_out == 64 || c_out == 128) && in_bytes < 0x7FFFFFFFLL) {
       ConvTParams T{(const char*)dy, (char*)dx, (const char*)w_packed, nullptr, n, h, w, c_out, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
       return c_out == 64 ? launch_convt_dgrad_ws<64>(T, (hipStream_t)stream)
                          : launch_convt_dgrad_ws<128>(T, (hipStream_t)stream);
@@ -3631,8 +3493,7 @@ extern "C" int32_t unet_convt2x2_dgrad_bnrelu_supported(int32_t dtype, int32_t n
                                                         int32_t c_out) {
   const long long in_bytes = (long long)n * 4 * h * w * c_out * 2;
   // (c_out == 128 -- 128 weight registers per lane -- has no room for the running sums: 78 spills; not offered)
-  return (dtype == UNET_BF16 && c_in == 2 * c_out && c_out == 64 && in_bytes < 0x7FFFFFFFLL &&
-          unet_tuning().convt_impl != '0' && unet_tuning().dgrad_bn != '0') ? 1 : 0;
+  return (dtype == UNET_BF16 && c_in == 2 * c_out && c_out == 64 && in_bytes < 0x7FFFFFFFLL) ? 1 : 0;
 }
 
 extern "C" size_t unet_convt2x2_dgrad_bnrelu_max_parts(void) { return 256; }

@@ -30,45 +30,10 @@ int32_t unet_check_launch(const char* what) {
 extern "C" int32_t unet_abi_version(void) { return UNET_ABI_VERSION; }
 extern "C" const char* unet_last_error(void) { return g_err; }
 
-// ------------------------------------------------------------------------------ tuning hooks, LDS opt-in
+// ------------------------------------------------------------------------------ CU budget, LDS opt-in
 namespace {
-UnetTuning g_tuning{};
-std::once_flag g_tuning_once;
-void read_tuning() {
-  auto first = [](const char* name) -> char { const char* v = getenv(name); return (v && v[0]) ? v[0] : (char)0; };
-  g_tuning.conv_impl = first("UNET_CONV_IMPL");
-  g_tuning.conv_var = first("UNET_CONV_VAR");
-  g_tuning.fused_stats = first("UNET_FUSED_STATS");
-  g_tuning.convt_impl = first("UNET_CONVT_IMPL");
-  g_tuning.wgrad_impl = first("UNET_WGRAD_IMPL");
-  g_tuning.ws_stats = first("UNET_WS_STATS");
-  g_tuning.dgrad_bn = first("UNET_DGRAD_BN");
-  g_tuning.pdma_pp = first("UNET_PDMA_PP");
-  g_tuning.ws_st = first("UNET_WS_ST");
-  g_tuning.ws_mfma = first("UNET_WS_MFMA");
-  g_tuning.wgrad_xcd = first("UNET_WGRAD_XCD");
-  g_tuning.conv_xcd = first("UNET_CONV_XCD");
-  g_tuning.ws_stg = first("UNET_WS_STG");
-  g_tuning.pdma_stg = first("UNET_PDMA_STG");
-  g_tuning.ew_var = first("UNET_EW_VAR");
-  g_tuning.pdma_pair = first("UNET_PDMA_PAIR");
-}
 std::mutex g_lds_mu;
 std::vector<std::pair<int, const void*>> g_lds_done;
-}  // namespace
-
-const UnetTuning& unet_tuning() {
-  std::call_once(g_tuning_once, read_tuning);
-  return g_tuning;
-}
-
-extern "C" int32_t unet_tuning_reload(void) {
-  (void)unet_tuning();
-  read_tuning();
-  return UNET_OK;
-}
-
-namespace {
 std::atomic<int> g_reserved_cus{-1};             // -1: not set -> UNET_RESERVED_CUS (default 0)
 int g_dev_cus[64] = {0};
 }  // namespace

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 
 // ------------------------------------------------------------------------------------------------------
 // wgrad_dma_kernel: bf16 conv3x3 weight gradient with LDS-DMA staging (buffer_load ... lds).
-// Same math and tiling as wgrad_kernel<bf16,9>; differences:
+// Same math and tiling as wgrad_kernel<T, 9>; differences:
 //  * the dY tile and the halo'd X patch of tile t+1 are DMA'd into the second LDS buffer while tile t runs
 //    its 72 MFMAs per wave -- no staging registers (180 instead of 220 VGPRs), global latency hidden;
 //  * LDS rows are the natural 128 B (64 channels) with a 16-byte-piece XOR swizzle, piece ^= ((row>>1)&1)<<2,
@@ -295,7 +295,6 @@ __device__ inline bf16x8 tr_frag2(const char* base, int off0, int off1) {
 #define WG_STAMP(i)
 #endif
 
-template <bool REUSE>
 __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(const WgradParams P) {
   using C = WDma;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -405,44 +404,28 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(const WgradParams P) 
     WG_STAMP(2)
     const char* sR = smem + buf * C::BUF;
     const char* sC = sR + C::R_BYTES;
-    if constexpr (REUSE) {
-      // the X fragment of (tile row ty, tap row r, tap column s) is the fragment of (ty+1, r-1, s): keep the
-      // three live patch rows x three column shifts in registers and fetch only the new patch row per ty
-      // (30 + 8 instead of 72 + 8 transposed fragment reads per tile: the LDS array was the limiter)
-      // patch row stride 18 is even, so the swizzle bit of row prow*18 + kq + sx is ((kq+sx)>>1 ^ prow) & 1:
-      // two lane addresses per column shift (even / odd patch row), the row itself is an immediate offset
-      auto load_c = [&](int prow, int sx) {
-        const int cp = c_base[prow & 1][sx] + prow * (C::HW * 128);
-        return tr_frag2(sC, cp, cp + 4 * 128);                  // rows +4: same swizzle bit
-      };
-      bf16x8 fb[3][3];
+    // the X fragment of (tile row ty, tap row r, tap column s) is the fragment of (ty+1, r-1, s): keep the
+    // three live patch rows x three column shifts in registers and fetch only the new patch row per ty
+    // (30 + 8 instead of 72 + 8 transposed fragment reads per tile: the LDS array was the limiter)
+    // patch row stride 18 is even, so the swizzle bit of row prow*18 + kq + sx is ((kq+sx)>>1 ^ prow) & 1:
+    // two lane addresses per column shift (even / odd patch row), the row itself is an immediate offset
+    auto load_c = [&](int prow, int sx) {
+      const int cp = c_base[prow & 1][sx] + prow * (C::HW * 128);
+      return tr_frag2(sC, cp, cp + 4 * 128);                  // rows +4: same swizzle bit
+    };
+    bf16x8 fb[3][3];
 #pragma unroll
-      for (int sx = 0; sx < 3; ++sx) { fb[0][sx] = load_c(0, sx); fb[1][sx] = load_c(1, sx); }
+    for (int sx = 0; sx < 3; ++sx) { fb[0][sx] = load_c(0, sx); fb[1][sx] = load_c(1, sx); }
 #pragma unroll
-      for (int ty = 0; ty < C::TH; ++ty) {
+    for (int ty = 0; ty < C::TH; ++ty) {
 #pragma unroll
-        for (int sx = 0; sx < 3; ++sx) fb[(ty + 2) % 3][sx] = load_c(ty + 2, sx);
-        const int rrow = ty * C::TW + kq;
-        const int rp = rrow * 128 + ((r_piece ^ r_swz) << 4) + r_sub;
-        const bf16x8 fa = tr_frag2(sR, rp, rp + 4 * 128);
+      for (int sx = 0; sx < 3; ++sx) fb[(ty + 2) % 3][sx] = load_c(ty + 2, sx);
+      const int rrow = ty * C::TW + kq;
+      const int rp = rrow * 128 + ((r_piece ^ r_swz) << 4) + r_sub;
+      const bf16x8 fa = tr_frag2(sR, rp, rp + 4 * 128);
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
-          acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb[(ty + tap / 3) % 3][tap % 3], acc[tap], 0, 0, 0);
-      }
-    } else {
-#pragma unroll 4
-      for (int ty = 0; ty < C::TH; ++ty) {
-        const int rrow = ty * C::TW + kq;
-        const int rp = rrow * 128 + ((r_piece ^ r_swz) << 4) + r_sub;
-        const bf16x8 fa = tr_frag2(sR, rp, rp + 4 * 128);
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-          const int crow = (ty + tap / 3) * C::HW + kq + tap % 3;
-          const int cp = crow * 128 + ((c_piece ^ (((crow >> 1) & 1) << 2)) << 4) + c_sub;
-          const bf16x8 fb = tr_frag2(sC, cp, cp + 4 * 128);       // rows +4: same swizzle bit
-          acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc[tap], 0, 0, 0);
-        }
-      }
+      for (int tap = 0; tap < 9; ++tap)
+        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb[(ty + tap / 3) % 3][tap % 3], acc[tap], 0, 0, 0);
     }
   }
 
@@ -468,13 +451,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(const WgradParams P) 
 }
 
 // ------------------------------------------------------------------------------------------------------
-// wgrad16_kernel<NRH, NCH, PAIRED> (round 3): the bf16 conv3x3 weight gradient on v_mfma_f32_16x16x32_bf16.
+// wgrad16_kernel<PAIRED> (round 3): the bf16 conv3x3 weight gradient on v_mfma_f32_16x16x32_bf16.
 //
 // Why: the 32x32x16 kernel above ran at 1.23-1.58 GHz in-kernel (profiles/r02_wgrad_stamps.txt) -- the chip holds a
 // higher clock on the 16x16x32 shape (MI355X_MICROARCH.md, DVFS give-back item 7; stamped here: 1.76-1.90 GHz) -- and
 // ~36 % of a tile went to its ten one-KiB LDS-DMA issues per wave.  Here:
-//  * one 512-thread block per CU owns 128 x 64 (NRH=2, NCH=1) or 64 x 128 (1, 2) gradient channels x 9 taps: the X patch
-//    (or the dY tile) is staged once for twice the MFMAs -- 62 instead of 78 KiB of LDS-DMA per 18.9 MFLOP;
+//  * one 512-thread block per CU owns 128 x 64 gradient channels x 9 taps: the X patch is staged once for twice the
+//    MFMAs -- 62 instead of 78 KiB of LDS-DMA per 18.9 MFLOP;
 //  * K = 32 pixels per MFMA = one 32-pixel tile ROW (tile 4 x 32; PAIRED, W <= 16: 16 pixels of image n + 16 of image
 //    n+1), so the X fragment of (patch row p, column shift s) still serves the three (tile row, tap row) pairs with
 //    ty + r = p; the loop walks PATCH rows: per row 6 X fragments + 2 dY fragments (a 4-slot ring of dY rows), 12..36
@@ -490,26 +473,26 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(const WgradParams P) 
 //  * the two waves of a SIMD issue their LDS-DMAs at opposite ends of a tile (see the loop).
 // Same split-K slabs / ordered reduction as above: bitwise reproducible, and bit-identical to the 32x32x16 kernel's sums
 // only up to fp32 summation order (K is walked in a different order).
-template <int NRH, int NCH, bool PAIRED>
+template <bool PAIRED>
 struct W16 {
-  static constexpr int PW = PAIRED ? 32 : (NCH == 1 ? 48 : 40); // LDS rows per patch row (18 / 34 of them used)
+  static constexpr int PW = PAIRED ? 32 : 48;                   // LDS rows per patch row (18 / 34 of them used)
   static constexpr bool PX = ((PW / 8) & 1) != 0;               // bit 3 of the LDS row flips with the patch row
   static constexpr int IMGROWS = 6 * PW;                        // LDS rows of one image's patch
   static constexpr int XROWS = (PAIRED ? 2 : 1) * IMGROWS;
   static constexpr int R_HALF = 128 * 128, C_HALF = XROWS * 128;
   static constexpr int IPR = PAIRED ? 3 : 5;                    // DMA pieces (8 LDS rows) per patch row that hold data
   static constexpr int R_INSTR = 16, C_INSTR = (PAIRED ? 2 : 1) * 6 * IPR;   // one-KiB DMA instructions per half
-  static constexpr int BUF = NRH * R_HALF + NCH * C_HALF;
+  static constexpr int BUF = 2 * R_HALF + C_HALF;              // two 64-channel halves of dY, one of X
   static constexpr int LDS = 2 * BUF;                           // (paired: exactly the CU's 160 KiB)
-  static constexpr int WR = 2 * NRH, WC = 2 * NCH;              // waves along gradient rows / columns (32 channels each)
+  static constexpr int WR = 4, WC = 2;                          // waves along gradient rows / columns (32 channels each)
   static_assert(WR * WC == 8, "eight waves");
   static_assert(LDS <= 160 * 1024, "LDS");
   static_assert(5 * PW * 128 + 12 * 128 + 512 < 65536, "fragment offsets are 16-bit immediates");
 };
 
-template <int NRH, int NCH, bool PAIRED>
+template <bool PAIRED>
 __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
-  using C = W16<NRH, NCH, PAIRED>;
+  using C = W16<PAIRED>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef __attribute__((address_space(3))) void lds_void;
   constexpr unsigned OOB = 0xFFFFFFF0u;
@@ -522,16 +505,10 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
   sp = __builtin_amdgcn_readfirstlane(sp);
   rtile = __builtin_amdgcn_readfirstlane(rtile);
   ctile = __builtin_amdgcn_readfirstlane(ctile);
-  const int rch = rtile * 64 * NRH;
-  WView CS[NCH];
-  int cch[NCH];
-#pragma unroll
-  for (int h = 0; h < NCH; ++h) {
-    const int c = (ctile * NCH + h) * 64;
-    const bool first = c < P.ct[0].C;
-    CS[h] = first ? P.ct[0] : P.ct[1];
-    cch[h] = first ? c : c - P.ct[0].C;
-  }
+  const int rch = rtile * 128;
+  const bool first = ctile * 64 < P.ct[0].C;
+  const WView CS = first ? P.ct[0] : P.ct[1];
+  const int cch = first ? ctile * 64 : ctile * 64 - P.ct[0].C;
 
   f32x4 acc[9][2][2];
 #pragma unroll
@@ -566,7 +543,7 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
           const int t = sx + 4 * j + q;
           const int f = ((t >> 1) & 1) | ((((gp & 1) ^ (t >> 3) ^ par) & 1) << 1);
           const int cg = (wc & 1) * 2 + nb;
-          b_off[par][sx][j][nb] = NRH * C::R_HALF + (wc >> 1) * C::C_HALF +
+          b_off[par][sx][j][nb] = 2 * C::R_HALF +
                                   ((PAIRED ? (g >> 1) * C::IMGROWS : 0) + 8 * gp + t) * 128 + ((cg ^ f) << 5) + cq;
         }
 
@@ -581,16 +558,14 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
 #ifndef W16_NE
 #define W16_NE 8
 #endif
-  constexpr int NT = NRH * C::R_INSTR + NCH * C::C_INSTR;      // pieces per tile: 62 (128x64 wide), 68 (paired), 76 (64x128)
+  constexpr int NT = 2 * C::R_INSTR + C::C_INSTR;              // pieces per tile: 62 (wide), 68 (paired)
   constexpr int NE = W16_NE;
   constexpr int NLATE = (NT - 4 * NE + 3) / 4;
   // (measured: the waves that compute FIRST must be the ones that win the SIMD's issue arbitration -- the older waves
   //  0-3; the roles swapped, or the early waves raised with s_setprio, cost 8-13 %)
   const bool late_wave = wave < 4;
   const unsigned r_img = (unsigned)P.rt.H * P.rt.W * P.rt.C * 2u;
-  unsigned c_img[NCH];
-#pragma unroll
-  for (int h = 0; h < NCH; ++h) c_img[h] = (unsigned)CS[h].H * CS[h].W * CS[h].C * 2u;
+  const unsigned c_img = (unsigned)CS.H * CS.W * CS.C * 2u;
 
   // the tile being FETCHED: (image [pair], tile row, tile column), advanced by scalar compares -- no divisions in the loop
   int d_txi, d_tyi, d_n;
@@ -615,28 +590,20 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
     asm volatile("" : "+v"(ln));
     const int lx = ln >> 3;
     const int pz = (ln & 7) ^ (((ln >> 4) & 1) << 1);           // piece ^ (bit 1 of the row) << 1
-    auto x_piece = [&](int i2) {                                // piece i2 of the X patch (both halves counted through)
-      const int h = NCH == 1 ? 0 : i2 / C::C_INSTR, li = NCH == 1 ? i2 : i2 % C::C_INSTR;
-      // (scalar selects: indexing CS[] with the run-time h would put the view into scratch memory)
-      const bool h1 = NCH > 1 && h == 1;
-      WView S;
-      S.p = h1 ? CS[NCH - 1].p : CS[0].p;  S.C = h1 ? CS[NCH - 1].C : CS[0].C;  S.H = h1 ? CS[NCH - 1].H : CS[0].H;
-      S.W = h1 ? CS[NCH - 1].W : CS[0].W;  S.oy = h1 ? CS[NCH - 1].oy : CS[0].oy;  S.ox = h1 ? CS[NCH - 1].ox : CS[0].ox;
-      const unsigned cimg = h1 ? c_img[NCH - 1] : c_img[0];
-      const int cchh = h1 ? cch[NCH - 1] : cch[0];
+    auto x_piece = [&](int li) {                                // piece li of the X patch
       const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)(S.p + (size_t)n0 * cimg), (short)0, (int)(cimg * nimg), 0x00020000);
+          (void*)(CS.p + (size_t)n0 * c_img), (short)0, (int)(c_img * nimg), 0x00020000);
       const int img = PAIRED ? li / (6 * C::IPR) : 0, lr = PAIRED ? li % (6 * C::IPR) : li;
       const int prow = lr / C::IPR, pc0 = (lr % C::IPR) * 8;    // patch row, first of the 8 patch columns
       const int row0 = img * C::IMGROWS + prow * C::PW + pc0;   // first LDS row of the piece
-      const int y = ty0 + prow - 1 - S.oy, x0 = tx0 + pc0 - 1 - S.ox;
-      const bool rowok = y >= 0 && y < S.H && img < nimg;
+      const int y = ty0 + prow - 1 - CS.oy, x0 = tx0 + pc0 - 1 - CS.ox;
+      const bool rowok = y >= 0 && y < CS.H && img < nimg;
       // scalar part: the image row (never negative once rowok); the column (x0 may be -1) stays in the lane part
-      const unsigned so = (unsigned)img * cimg + (unsigned)((y * S.W * S.C + cchh) * 2);
-      const unsigned lane_off = (unsigned)(x0 + lx) * (unsigned)(S.C * 2) + (unsigned)((pz ^ (((row0 >> 3) & 1) << 2)) << 4);
-      const bool colok = (unsigned)(x0 + lx) < (unsigned)S.W && pc0 + lx < (PAIRED ? 18 : 34);
+      const unsigned so = (unsigned)img * c_img + (unsigned)((y * CS.W * CS.C + cch) * 2);
+      const unsigned lane_off = (unsigned)(x0 + lx) * (unsigned)(CS.C * 2) + (unsigned)((pz ^ (((row0 >> 3) & 1) << 2)) << 4);
+      const bool colok = (unsigned)(x0 + lx) < (unsigned)CS.W && pc0 + lx < (PAIRED ? 18 : 34);
       const unsigned vo = (rowok && colok) ? lane_off : OOB;
-      char* dst = smem + buf * C::BUF + NRH * C::R_HALF + h * C::C_HALF + row0 * 128;
+      char* dst = smem + buf * C::BUF + 2 * C::R_HALF + row0 * 128;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rc, (lds_void*)dst, 16, vo, rowok ? so : 0u, 0, 0);
     };
     const __amdgpu_buffer_rsrc_t rr =
@@ -660,15 +627,15 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
       for (int j = 0; j < NLATE; ++j) {
         const int idx = (wave & 3) * NLATE + j;
         if (idx >= NT - 4 * NE) break;
-        if (idx < NRH * C::R_INSTR) y_piece(idx);
-        else x_piece(idx - NRH * C::R_INSTR);
+        if (idx < 2 * C::R_INSTR) y_piece(idx);
+        else x_piece(idx - 2 * C::R_INSTR);
       }
     } else {
 #pragma unroll
       for (int j = 0; j < NE; ++j) {
         const int idx = NT - 4 * NE + (wave & 3) * NE + j;
-        if (idx < NRH * C::R_INSTR) y_piece(idx);
-        else x_piece(idx - NRH * C::R_INSTR);
+        if (idx < 2 * C::R_INSTR) y_piece(idx);
+        else x_piece(idx - 2 * C::R_INSTR);
       }
     }
   };
@@ -798,7 +765,7 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
         const int row = rch + wr * 32 + cb * 16 + i16;
-        const int col = ctile * 64 * NCH + wc * 32 + nb * 16 + g * 4;
+        const int col = ctile * 64 + wc * 32 + nb * 16 + g * 4;
         *reinterpret_cast<f32x4*>(o + (size_t)row * P.Ccol + col) = acc[tap][cb][nb];
       }
   }
@@ -865,21 +832,16 @@ Plan make_plan(int n, int h, int w, int crow, int ccol) {
   return p;
 }
 
-// wgrad16_kernel: 128 x 64 (crow % 128 == 0) or 64 x 128 (crow == 64, ccol % 128 == 0, wide frames) channel tiles, 4 x 32
-// pixel tiles (PAIRED: two 16-wide images), one block per CU -> 256 blocks
-inline int wgrad16_variant(int w, int crow, int ccol) {          // 0: not served; 1: <2,1,wide>; 2: <2,1,paired>; 3: <1,2,wide>
-  if (crow % 128 == 0) return w <= 16 ? 2 : 1;
-  if (crow == 64 && ccol % 128 == 0 && w > 16) return 3;
-  return 0;
-}
+// wgrad16_kernel: 128 x 64 channel tiles (crow % 128 == 0), 4 x 32 pixel tiles (PAIRED, w <= 16: two 16-wide images),
+// one block per CU -> 256 blocks
 inline Plan make_plan16(int n, int h, int w, int crow, int ccol) {
   Plan p;
-  const int v = wgrad16_variant(w, crow, ccol);
-  p.tilesX = v == 2 ? 1 : cdiv(w, 32);
+  const bool paired = w <= 16;
+  p.tilesX = paired ? 1 : cdiv(w, 32);
   p.tilesY = cdiv(h, 4);
-  p.nR = v == 3 ? crow / 64 : crow / 128;
-  p.nC = v == 3 ? ccol / 128 : ccol / 64;
-  const long long ntiles = (long long)(v == 2 ? (n + 1) / 2 : n) * p.tilesY * p.tilesX;
+  p.nR = crow / 128;
+  p.nC = ccol / 64;
+  const long long ntiles = (long long)(paired ? (n + 1) / 2 : n) * p.tilesY * p.tilesX;
   long long want = (long long)unet_cu_budget() / ((long long)p.nR * p.nC);   // one 512-thread block per CU
   if (want < 1) want = 1;
   if (want > ntiles) want = ntiles;
@@ -889,45 +851,37 @@ inline Plan make_plan16(int n, int h, int w, int crow, int ccol) {
   return p;
 }
 
-template <int NRH, int NCH, bool PAIRED>
+template <bool PAIRED>
 void launch16(const WgradParams& P, long long blocks, hipStream_t s) {
-  using C = W16<NRH, NCH, PAIRED>;
-  auto kern = wgrad16_kernel<NRH, NCH, PAIRED>;
+  using C = W16<PAIRED>;
+  auto kern = wgrad16_kernel<PAIRED>;
   unet_set_max_lds(reinterpret_cast<const void*>(kern), C::LDS);
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), C::LDS, s, P);
 }
 
 template <typename T, int TAPS>
 int32_t run(WgradParams& P, const Plan& pl, float* out, int rows_out, int cols_out, int kclass, hipStream_t s) {
-  using C = WCfg<T, TAPS>;
-  auto kern = wgrad_kernel<T, TAPS>;
-  unet_set_max_lds(reinterpret_cast<const void*>(kern), C::LDS);
   P.tilesX = pl.tilesX; P.tilesY = pl.tilesY; P.nR = pl.nR; P.nC = pl.nC;
   P.split = pl.split; P.tilesPerSplit = pl.tilesPerSplit;
   long long blocks = (long long)pl.split * pl.nR * pl.nC;
   P.xcd_chunk = 0;
-  if (unet_tuning().wgrad_xcd != '0' && blocks >= 16) {         // UNET_WGRAD_XCD=0: plain block order
+  if (blocks >= 16) {                                           // XCD-aware block order
     P.xcd_chunk = (int)cdiv64(blocks, 8);
     blocks = 8LL * P.xcd_chunk;
   }
   const double flops = 2.0 * P.N * P.H * P.W * (double)P.Crow * P.Ccol * TAPS;
-  const char impl = unet_tuning().wgrad_impl;   // UNET_WGRAD_IMPL: 0 register-staged, 1 the 32x32x16 LDS-DMA kernel, 2 that without reuse
   int split_used = pl.split;
   {
     // algorithmic bytes: both activation tensors once + the fp32 gradient once (split-K slabs are overhead, not counted)
     const double alg_bytes = (double)P.N * P.H * P.W * ((double)P.Crow + P.Ccol * (TAPS == 9 ? 1.0 : 4.0)) * sizeof(T) +
                              4.0 * TAPS * rows_out * cols_out;
-    // wgrad16_kernel: default for the forms it wins on (A/B per shape, profiles/r03_wgrad16.txt); UNET_WGRAD_IMPL=3
-    // forces it wherever it applies, 1 / 2 select the 32x32x16 kernel
-    int v16 = 0;
-    if constexpr (sizeof(T) == 2 && TAPS == 9) {
-      v16 = (impl == 0 || impl == '3') ? wgrad16_variant(P.W, P.Crow, P.Ccol) : 0;
-      if (impl == 0 && v16 == 3) v16 = 0;
-    }
+    // bf16 3x3: wgrad16_kernel for the 128-row forms (it wins there, A/B per shape, profiles/r03_wgrad16.txt), the
+    // 32x32x16 LDS-DMA kernel for the rest
+    constexpr bool DMA = sizeof(T) == 2 && TAPS == 9;
+    const bool v16 = DMA && P.Crow % 128 == 0;
     ProfScope prof(kclass, flops, s,
-                   v16 ? "wgrad16_kernel (+ reduce)"
-                       : ((sizeof(T) == 2 && TAPS == 9) ? "wgrad_dma_kernel (+ reduce)" : "wgrad_kernel (+ reduce)"), alg_bytes);
-    if constexpr (sizeof(T) == 2 && TAPS == 9) {
+                   v16 ? "wgrad16_kernel (+ reduce)" : (DMA ? "wgrad_dma_kernel (+ reduce)" : "wgrad_kernel (+ reduce)"), alg_bytes);
+    if constexpr (DMA) {
       if (v16) {
         const Plan p16 = make_plan16(P.N, P.H, P.W, P.Crow, P.Ccol);
         P.tilesX = p16.tilesX; P.tilesY = p16.tilesY; P.nR = p16.nR; P.nC = p16.nC;
@@ -935,21 +889,17 @@ int32_t run(WgradParams& P, const Plan& pl, float* out, int rows_out, int cols_o
         split_used = p16.split;
         long long b16 = (long long)p16.split * p16.nR * p16.nC;
         P.xcd_chunk = 0;
-        if (unet_tuning().wgrad_xcd != '0' && b16 >= 16) { P.xcd_chunk = (int)cdiv64(b16, 8); b16 = 8LL * P.xcd_chunk; }
-        if (v16 == 1) launch16<2, 1, false>(P, b16, s);
-        else if (v16 == 2) launch16<2, 1, true>(P, b16, s);
-        else launch16<1, 2, false>(P, b16, s);
-      } else if (impl != '0') {
-        unet_set_max_lds(reinterpret_cast<const void*>(wgrad_dma_kernel<true>), WDma::LDS);
-        unet_set_max_lds(reinterpret_cast<const void*>(wgrad_dma_kernel<false>), WDma::LDS);
-        if (impl == '2')                                        // "2": every tap re-reads its X fragment
-          hipLaunchKernelGGL(wgrad_dma_kernel<false>, dim3((unsigned)blocks), dim3(256), WDma::LDS, s, P);
-        else
-          hipLaunchKernelGGL(wgrad_dma_kernel<true>, dim3((unsigned)blocks), dim3(256), WDma::LDS, s, P);
+        if (b16 >= 16) { P.xcd_chunk = (int)cdiv64(b16, 8); b16 = 8LL * P.xcd_chunk; }
+        if (P.W <= 16) launch16<true>(P, b16, s);
+        else launch16<false>(P, b16, s);
       } else {
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), C::LDS, s, P);
+        unet_set_max_lds(reinterpret_cast<const void*>(wgrad_dma_kernel), WDma::LDS);
+        hipLaunchKernelGGL(wgrad_dma_kernel, dim3((unsigned)blocks), dim3(256), WDma::LDS, s, P);
       }
     } else {
+      using C = WCfg<T, TAPS>;
+      auto kern = wgrad_kernel<T, TAPS>;
+      unet_set_max_lds(reinterpret_cast<const void*>(kern), C::LDS);
       hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), C::LDS, s, P);
     }
     int32_t rc = unet_check_launch("wgrad_kernel");
@@ -974,7 +924,7 @@ inline int pad64(int c) { return (c + 63) / 64 * 64; }
 
 extern "C" size_t unet_conv3x3_wgrad_workspace(int32_t n, int32_t h, int32_t w, int32_t c_in, int32_t c_out) {
   size_t bytes = make_plan<9>(n, h, w, pad64(c_out), pad64(c_in)).bytes;
-  if (wgrad16_variant(w, pad64(c_out), pad64(c_in)))
+  if (pad64(c_out) % 128 == 0)
     bytes = std::max(bytes, make_plan16(n, h, w, pad64(c_out), pad64(c_in)).bytes);
   return bytes;
 }
@@ -1246,10 +1196,9 @@ int32_t launch_convt_wgrad_ws(const void* x, const void* dy, int n, int h, int w
 
 inline bool convt_wgrad_ws_ok(int dtype, int n, int h, int w, int c_in, int c_out) {
   const long long xb = (long long)n * h * w * c_in * 2;
-  const bool deep = (c_in == 512 || c_in == 1024) && unet_tuning().convt_impl != '3';   // (3: deep levels generic)
-  return dtype == UNET_BF16 && (c_in == 128 || c_in == 256 || deep) && c_out * 2 == c_in &&
+  return dtype == UNET_BF16 && (c_in == 128 || c_in == 256 || c_in == 512 || c_in == 1024) && c_out * 2 == c_in &&
          (w % 32 == 0 || (w == 16 && h % 2 == 0)) && ((long long)n * h * w) % 32 == 0 &&
-         2 * xb < 0x7FFFFFFFLL && unet_tuning().convt_impl != '0';      // (UNET_CONVT_IMPL=0: generic kernels)
+         2 * xb < 0x7FFFFFFFLL;
 }
 inline size_t convt_wgrad_ws_bytes(int n, int h, int w, int c_in) {
   const long long tiles = (long long)n * h * w / 32;

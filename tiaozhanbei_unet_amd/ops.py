@@ -57,7 +57,6 @@ def _as_nhwc(t: torch.Tensor, dtype) -> torch.Tensor:
 
 
 _workspaces = {}
-_helpers = {}
 
 # Data parallelism (ddp.GradientExchange) registers, per parameter, the slice of its flat all-reduce bucket: the
 # weight-gradient kernels then write the gradient THERE (autograd adopts the returned tensor as ``param.grad`` when
@@ -93,16 +92,6 @@ def grad_out(shape, device, key):
             _grad_taken.add(key)
             return view.detach()            # a fresh alias: autograd adopts a gradient only if nobody else holds the tensor
     return torch.empty(tuple(shape), dtype=torch.float32, device=device)
-WGRAD_SIDE_STREAM = __import__("os").environ.get("UNET_WGRAD_STREAM", "0") != "0"   # measured slower (-3 %): off
-
-
-def _helper_stream(device, cur):
-    """One helper stream per compute stream (weight gradients run beside data gradients)."""
-    key = (device.index, cur.cuda_stream)
-    if key not in _helpers:
-        _helpers[key] = torch.cuda.Stream(device=device)
-    return _helpers[key]
-
 
 
 def _workspace(nbytes: int, device) -> torch.Tensor:
@@ -748,32 +737,15 @@ class ConvBnRelu(torch.autograd.Function):
                                         frozen=not training, beta_key=bkey, gamma_key=gkey)
         src = _views([(x0, 0, 0), None if x1 is None else (x1, oy, ox)])
         dw = None
-        wgrad_done = None
         if ctx.needs_input_grad[2]:
-            # the weight gradient only depends on dy and the saved input: it runs on a helper stream, next to
-            # the data gradient (their ramp-up / tail phases overlap); joined before this node returns
-            cur = torch.cuda.current_stream(dev)
-            helper = _helper_stream(dev, cur) if WGRAD_SIDE_STREAM else None
-            if helper is not None:
-                helper.wait_stream(cur)
-                torch.cuda.set_stream(helper)
-            try:
-                # padded layer: the kernel writes dW of the padded one ([co][ctot] under a segment map, [co][ci] else)
-                ci_k = ctot if split else ci
-                dw = torch.empty((co, ci_k, 3, 3), dtype=torch.float32, device=dev) if (narrow or split) else \
-                    grad_out(weight.shape, dev, ctx.keys[0])
-                need = lib.unet_conv3x3_wgrad_workspace(n, h, w, ctot, co)
-                ws2 = _workspace(need, dev)
-                L.check(lib.unet_conv3x3_wgrad(dt, n, h, w, src, _ptr(dy), co, _ptr(dw), ci_k, _ptr(ws2), ws2.numel(),
-                                               _stream()), "unet_conv3x3_wgrad")
-                if helper is not None:
-                    wgrad_done = torch.cuda.Event()
-                    wgrad_done.record(helper)
-                    dw.record_stream(cur)
-                    dy.record_stream(helper)
-            finally:
-                if helper is not None:
-                    torch.cuda.set_stream(cur)
+            # padded layer: the kernel writes dW of the padded one ([co][ctot] under a segment map, [co][ci] else)
+            ci_k = ctot if split else ci
+            dw = torch.empty((co, ci_k, 3, 3), dtype=torch.float32, device=dev) if (narrow or split) else \
+                grad_out(weight.shape, dev, ctx.keys[0])
+            need = lib.unet_conv3x3_wgrad_workspace(n, h, w, ctot, co)
+            ws2 = _workspace(need, dev)
+            L.check(lib.unet_conv3x3_wgrad(dt, n, h, w, src, _ptr(dy), co, _ptr(dw), ci_k, _ptr(ws2), ws2.numel(), st),
+                    "unet_conv3x3_wgrad")
         dx0 = dx1 = None
         if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
             wp = packed(weight, L.PACK_CONV_DGRAD, ctot, co, dtype, split)
@@ -804,8 +776,6 @@ class ConvBnRelu(torch.autograd.Function):
                     sink.done(dx0, dev)
                     if fan_in:
                         dx0 = None              # already inside the buffer the first consumer returned
-        if wgrad_done is not None:
-            torch.cuda.current_stream(dev).wait_event(wgrad_done)
         if narrow or split:
             # padded gradients -> the parameters' shapes, one launch
             items = []

@@ -23,8 +23,6 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--op", default="fwd", choices=["fwd", "fwdstats", "dgrad", "wgrad"])
-    ap.add_argument("--ab", default="", help="comma list of values of --abvar to A/B interleaved in one process")
-    ap.add_argument("--abvar", default="UNET_CONV_IMPL")
     ap.add_argument("--acc", type=int, default=0, help="accumulate bit mask of the conv dgrad (dst += result)")
     a = ap.parse_args()
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
@@ -97,40 +95,17 @@ def main():
         else:
             run = lambda: L.check(lib.unet_convt2x2_wgrad(ops._DT[dt], n, h, w, p(x), ci, p(gy), co, p(dw), p(db),
                                                           p(ws), need, st), "convt wgrad")
-    variants = a.ab.split(",") if a.ab else [None]
-    best = {v: 1e9 for v in variants}
-    for rnd in range(4 if a.ab else 1):
-        for v in variants:
-            if v is not None:
-                os.environ[a.abvar] = v
-                lib.unet_tuning_reload()
-            for _ in range(3):
-                run()
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.iters):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
-            best[v] = min(best[v], e0.elapsed_time(e1) / a.iters)
-    if a.ab and a.kind != "first":
-        outs = {}
-        for v in variants:
-            os.environ[a.abvar] = v
-            lib.unet_tuning_reload()
-            tgt = {"fwd": y, "fwdstats": y, "dgrad": dx, "wgrad": dw}[a.op]
-            tgt.zero_()
-            run()
-            torch.cuda.synchronize()
-            outs[v] = tgt.float().clone()
-        ref = outs[variants[0]]
-        for v in variants[1:]:
-            print(f"   check {a.abvar}={v} vs {variants[0]}: max|diff| {float((outs[v] - ref).abs().max()):.3e} "
-                  f"(|ref|max {float(ref.abs().max()):.3e})", flush=True)
-    for v, ms in best.items():
-        tag = "" if v is None else f" impl={v}"
-        print(f"{a.kind} {a.op} n={n} {ci}->{co} {h}x{w} {a.dtype}{tag}: {ms * 1e3:.1f} us  {flops / ms / 1e9:.1f} TFLOP/s", flush=True)
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(a.iters):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / a.iters
+    print(f"{a.kind} {a.op} n={n} {ci}->{co} {h}x{w} {a.dtype}: {ms * 1e3:.1f} us  {flops / ms / 1e9:.1f} TFLOP/s", flush=True)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,9 @@
 """Micro-benchmark of the HBM-bound streaming passes of the step through the C-ABI, next to torch's own elementwise kernels on
 the same tensors (what this card gives a plain copy / add): achieved TB/s = algorithmic bytes / time.
 
-    python tools/bench_stream.py [--n 32] [--iters 30] [--ab 0,1 --abvar UNET_EW_VAR]
+    python tools/bench_stream.py [--n 32] [--iters 30] [--levels 0,1,2,3,4]
+
+Two builds of the library: run it once per build, with UNET_HIP_LIB=<path of the other one> for the second.
 """
 import argparse
 import ctypes as C
@@ -34,8 +36,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32)
     ap.add_argument("--iters", type=int, default=30)
-    ap.add_argument("--ab", default="")
-    ap.add_argument("--abvar", default="UNET_EW_VAR")
     ap.add_argument("--levels", default="0,1,2,3,4")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -43,7 +43,6 @@ def main():
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = lambda t: C.c_void_p(t.data_ptr())
     dt, DT = torch.bfloat16, L.UNET_BF16
-    variants = a.ab.split(",") if a.ab else [None]
     for li in [int(v) for v in a.levels.split(",")]:
         c, s = LEVELS[li]
         n, h, w = a.n, s, s
@@ -76,15 +75,8 @@ def main():
         }
         print(f"--- N={n} C={c} {h}x{w}: {2 * el / 2**20:.0f} MiB per bf16 tensor", flush=True)
         for name, (fn, nbytes) in cases.items():
-            best = {v: 1e9 for v in variants}
-            for rnd in range(3 if a.ab else 1):
-                for v in variants:
-                    if v is not None:
-                        os.environ[a.abvar] = v
-                        lib.unet_tuning_reload()
-                    best[v] = min(best[v], timeit(fn, a.iters))
-            txt = "  ".join((f"[{v}] " if v is not None else "") + f"{ms * 1e3:7.1f} us {nbytes / ms / 1e9:5.2f} TB/s" for v, ms in best.items())
-            print(f"  {name:38s} {txt}", flush=True)
+            ms = timeit(fn, a.iters)
+            print(f"  {name:38s} {ms * 1e3:7.1f} us {nbytes / ms / 1e9:5.2f} TB/s", flush=True)
 
 
 if __name__ == "__main__":

@@ -35,6 +35,6 @@ for k, p in m.named_parameters():
     g, w = p.grad.double().cpu(), ref[k].double()
     errs[k] = float((g - w).norm() / (w.norm() + 1e-30))
 worst = sorted(errs.items(), key=lambda kv: -kv[1])[:8]
-print(f"FUSE_BN_BWD={os.environ.get('UNET_FUSE_BN_BWD', '1')} FUSE_BN_HEAD={os.environ.get('UNET_FUSE_BN_HEAD', '1')} "
-      f"DGRAD_BN={os.environ.get('UNET_DGRAD_BN', '1')}: median {sorted(errs.values())[len(errs) // 2]:.3f}  worst: "
+print(f"FUSE_BN_BWD={os.environ.get('UNET_FUSE_BN_BWD', '1')} FUSE_BN_HEAD={os.environ.get('UNET_FUSE_BN_HEAD', '1')}: "
+      f"median {sorted(errs.values())[len(errs) // 2]:.3f}  worst: "
       + ", ".join(f"{k.replace('maxpool_conv.1.', '').replace('double_conv', 'dc')}={v:.3f}" for k, v in worst))

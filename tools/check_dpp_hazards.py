@@ -129,7 +129,8 @@ def scan_no_scratch(path, kernel_patterns):
     return n, bad
 
 
-NO_SPILL_KERNELS = ("conv3_ws16_kernel", "conv3_pdma", "conv3_pp", "wgrad16_kernelILi2ELi1E")
+# (convt_ws_kernel: its patch DMAs and output stores share one hand-counted vmcnt stream as well)
+NO_SPILL_KERNELS = ("conv3_ws16_kernel", "conv3_pdma", "conv3_pp", "convt_ws_kernel", "wgrad16_kernel")
 
 Y_LOAD_KERNELS = ("conv3_ws16_kernelILb0ELi2E", "conv3_ws_kernelILb0ELi2E", "convt_dgrad_ws_kernelILi64ELb1E")
 

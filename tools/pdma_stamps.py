@@ -44,7 +44,7 @@ def main():
     us = e0.elapsed_time(e1) * 100
     d = dbg.view(256, 8, 8).cpu().double()
     taps = d[:, :, 4].clamp(min=1)
-    pp = os.environ.get("UNET_PDMA_PP", "0") in "12"
+    pp = co % 128 == 0 and ci >= 512              # the dispatcher's choice: ping-pong for 128-channel tiles from 512 inputs
     names = ["reads+dma issue", "vmcnt+lgkm wait", "barrier(L)", "mfma", "barrier(C)"] if pp else \
         ["vmcnt wait", "barrier", "dma issue", "reads+mfma"]
     cols = [0, 1, 2, 3, 6] if pp else [0, 1, 2, 3]

@@ -38,7 +38,7 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 100
-    new = os.environ.get("UNET_WGRAD_IMPL", "") in ("", "3") and (co % 128 == 0 or (co == 64 and ci % 128 == 0 and w > 16))
+    new = co % 128 == 0                          # the dispatcher's choice: wgrad16_kernel for 128-row forms
     d = (dbg.view(256, 8, 8) if new else dbg.view(512, 4, 8)).cpu().double()
     d = d[d[:, 0, 4] > 0]
     tiles = d[:, :, 4].clamp(min=1)
@@ -47,8 +47,6 @@ def main():
     print(f"wgrad n={n} {ci}->{co} {h}x{w} ({'wgrad16_kernel' if new else 'wgrad_dma_kernel'}): {us:.1f} us/launch incl. reduce "
           f"(stamped), blocks {d.shape[0]}, tiles/block {float(tiles.mean()):.1f}, in-kernel clock {clock:.2f} GHz")
     groups = [("all waves", slice(None))] if not new else [("dY waves (DMA mid-tile)", slice(0, 4)), ("X waves (DMA at tile start)", slice(4, 8))]
-    if new and co == 64:
-        groups = [("dY waves", slice(0, 2)), ("X waves", slice(2, 8))]
     for label, sl in groups:
         per = [float((d[:, sl, i] / tiles[:, sl]).mean()) for i in range(4)]
         ideal = 2304

@@ -50,7 +50,7 @@ def main():
     tiles = d[:, :, 7].clamp(min=1)
     clock = float(d[:, :, 6].median()) / 2 ** 20 * 0.1
     names = ["vmcnt wait", "barrier", "top: dma / deferred stores / geometry", "mfma loop", "late dma", "epilogue + stores"]
-    print(f"conv {'fwd+stats' if stats else 'fwd'} n={n} {ci}->{co} {h}x{w} ws16 UNET_WS_STG={os.environ.get('UNET_WS_STG', 'default')}: "
+    print(f"conv {'fwd+stats' if stats else 'fwd'} n={n} {ci}->{co} {h}x{w} ws16: "
           f"{us:.1f} us/launch (stamped), tiles/block {float(tiles.mean()):.0f}, in-kernel clock {clock:.2f} GHz")
     for grp, sl in (("waves 0-3", slice(0, 4)), ("waves 4-7", slice(4, 8))):
         per = [float((d[:, sl, i] / tiles[:, sl]).mean()) for i in range(6)]
