@@ -413,6 +413,28 @@ int32_t unet_seg_image_stats(const float* logits, const int64_t* target, int32_t
 int32_t unet_threshold_confusion(const float* pred, const float* truth, const uint8_t* select, int64_t n_images,
                                  int64_t per_image, const float* thresholds, int32_t k, int64_t* counts, void* stream);
 
+/* Pixel-level AUROC and AUPRC of the anomaly branch (src/test.py:172-178 evaluate_results -> src/utils.py:97-108
+ * calculate_pixel_metrics -> :84-91 roc_auc_score, auc(precision_recall_curve) with the anomaly map as the scores),
+ * without copying the maps to the host.  Two steps:
+ * unet_rank_auc_append: over the images with select[n] != 0 (NULL: all) of pred / truth (fp32 [n_images][per_image]),
+ * every finite score becomes an order-preserving uint32 key (-0.0 == +0.0): the keys of positive pixels (truth > 0.5,
+ * as unet_threshold_confusion) are written to keys[counts[0] ...] upwards, those of negative pixels to
+ * keys[capacity - 1 - counts[1] ...] downwards, in no particular order; counts[3] = {positives, negatives, non-finite
+ * scores} (int64, device) is ADDED to: zero it first, and size capacity >= every selected pixel of every call that adds
+ * to the same counts.  Integer atomics only; allocates nothing, does not synchronise.
+ * unet_rank_auc: sorts pos_keys[n_pos] and neg_keys[n_neg] in place (LSD radix sort; 16-byte aligned arrays) and writes
+ * out[2] (fp64, device) = {AUROC, AUPRC}: AUROC = sum over distinct positive keys v of pos_v (2 #neg<v + neg_v) / (2 P N)
+ * (Mann-Whitney, ties counted half; the numerator in uint64, rounded once by the division), AUPRC = sum over v of
+ * pos_v / P (prec(>= v) + prec(> v)) / 2, prec(> v) = 1 when nothing lies above v (sklearn's (recall 0, precision 1)
+ * point).  n_pos == 0 or n_neg == 0: {0, 0}.  Non-finite scores are the caller's to handle (the reference's
+ * calculate_metrics returns 0 / 0 for them).  n_pos + n_neg >= 2^31 is UNET_ERR_UNSUPPORTED (and the workspace query
+ * returns 0).  Ordered reductions, no float atomics: the result depends only on the two key multisets. */
+int32_t unet_rank_auc_append(const float* pred, const float* truth, const uint8_t* select, int64_t n_images,
+                             int64_t per_image, uint32_t* keys, int64_t capacity, int64_t* counts, void* stream);
+size_t unet_rank_auc_workspace(int64_t n_pos, int64_t n_neg);
+int32_t unet_rank_auc(uint32_t* pos_keys, int64_t n_pos, uint32_t* neg_keys, int64_t n_neg, double* out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- nn.Dropout2d of SegmentationUNet's bottleneck (src/model.py:129,146): y = x * scale[n][c] on dense NHWC; the
  * caller draws scale = bernoulli(1-p)/(1-p) per (image, channel); the same call is the backward (dx = dy * scale). */
 int32_t unet_channel_scale(int32_t dtype, const void* x, const float* scale, int32_t n, int64_t hw, int32_t c, void* y,

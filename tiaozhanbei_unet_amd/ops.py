@@ -1219,6 +1219,79 @@ def threshold_confusion(pred, truth, thresholds, select=None, counts=None):
     return counts
 
 
+class BinaryAUC:
+    """Pixel-level AUROC / AUPRC accumulated over batches: the roc_auc_score and auc(precision_recall_curve) that
+    the reference src/utils.py:84-91 computes for calculate_pixel_metrics (:97-108), on the device.  A pixel is
+    positive iff truth > 0.5; ties are float equality (-0.0 == +0.0).  ``update`` appends the selected pixels' scores
+    as sort keys (unet_rank_auc_append) without synchronising; ``compute`` reads the counts once, sorts and ranks
+    (unet_rank_auc).  No positives, no negatives or any NaN / inf score give 0.0 / 0.0, as calculate_metrics does when
+    sklearn refuses.  The result depends only on the multiset of (score, label) pixels, bitwise."""
+
+    def __init__(self):
+        self._chunks = []                     # (keys, capacity, counts): one exactly-sized key chunk per update
+
+    def update(self, pred, truth, select=None):
+        """pred / truth: device tensors of equal shape [N, ...]; select: host or device bool per image (None: all)."""
+        _require_cuda(pred)
+        p = pred.detach().contiguous().float()
+        t = truth.detach().to(p.device).contiguous().float()
+        if p.shape != t.shape or p.dim() < 2:
+            raise ValueError("BinaryAUC.update: prediction / truth shapes differ")
+        n = p.shape[0]
+        per = p.numel() // n
+        runs, sel = [(0, n)], None
+        if select is not None:
+            sel = torch.as_tensor(select)
+            if sel.numel() != n:
+                raise ValueError("BinaryAUC.update: select needs one entry per image")
+            if sel.is_cuda:
+                sel = sel.to(torch.uint8).contiguous()
+            else:                             # host mask: one launch per run of selected images, nothing to copy
+                on = sel.reshape(-1).to(torch.bool).tolist() + [False]
+                runs, start = [], None
+                for i, v in enumerate(on):
+                    if v and start is None:
+                        start = i
+                    elif not v and start is not None:
+                        runs.append((start, i))
+                        start = None
+                sel = None
+        cap = sum(b - a for a, b in runs) * per
+        if cap == 0:
+            return
+        keys = torch.empty(cap, dtype=torch.int32, device=p.device)
+        counts = torch.zeros(3, dtype=torch.int64, device=p.device)
+        lib = L.lib()
+        for a, b in runs:
+            L.check(lib.unet_rank_auc_append(_ptr(p[a:b]), _ptr(t[a:b]), _ptr(sel), b - a, per, _ptr(keys), cap,
+                                             _ptr(counts), _stream()), "unet_rank_auc_append")
+        self._chunks.append((keys, cap, counts))
+
+    def compute(self):
+        """{"auroc", "auprc", "positives", "negatives", "nonfinite"} over every pixel passed to update."""
+        totals = [0, 0, 0]
+        if self._chunks:
+            per_chunk = torch.stack([c for _, _, c in self._chunks]).tolist()      # the one read of the counts
+            totals = [sum(c[i] for c in per_chunk) for i in range(3)]
+        n_pos, n_neg, nonfinite = totals
+        res = {"auroc": 0.0, "auprc": 0.0, "positives": n_pos, "negatives": n_neg, "nonfinite": nonfinite}
+        if nonfinite or not n_pos or not n_neg:
+            return res
+        lib = L.lib()
+        nbytes = lib.unet_rank_auc_workspace(n_pos, n_neg)
+        if nbytes == 0:
+            raise RuntimeError(f"BinaryAUC: {n_pos + n_neg} pixels, at most 2^31 - 1 are supported")
+        dev = self._chunks[0][0].device
+        pos = torch.cat([k[:c[0]] for (k, _, _), c in zip(self._chunks, per_chunk)])          # copies: the sort
+        neg = torch.cat([k[cap - c[1]:] for (k, cap, _), c in zip(self._chunks, per_chunk)])  # is in place
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+        L.check(lib.unet_rank_auc(_ptr(pos), n_pos, _ptr(neg), n_neg, _ptr(out), _ptr(ws), nbytes, _stream()),
+                "unet_rank_auc")
+        res["auroc"], res["auprc"] = out.tolist()
+        return res
+
+
 def preprocess_u8(images_u8, flips=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """uint8 [N, H, W, 3] device batch -> normalised fp32 NCHW (ToTensor + Normalize, optional per-sample horizontal
     flip): /root/reference/src/dataset.py:134-146, src/kolektorsdd_dataset.py:133-150, on the GPU."""

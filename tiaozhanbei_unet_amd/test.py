@@ -42,6 +42,7 @@ def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None
     out = {k: [] for k in ("images", "reconstructions", "anomaly_maps", "masks_true", "labels", "anomaly_types",
                            "image_paths", "anomaly_scores")}
     pix = None
+    pix_auc = ops.BinaryAUC()         # pixel AUROC / AUPRC of the anomalous images, ranked on the device (:172-178)
     with torch.no_grad():
         from .train_utils import _batches
         for batch, images, _ in _batches(test_loader, device):     # (raw uint8 batches are transformed on the device)
@@ -50,8 +51,9 @@ def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None
             else:
                 amap, recon = model(images, sigmoid=True), images      # sigmoid inside the head kernel
             if pixel_thresholds:          # pixel-level confusion counts of the anomalous images, on the device (:86-101)
-                pix = ops.threshold_confusion(amap, batch["mask"], pixel_thresholds,
-                                              select=torch.as_tensor(np.asarray(batch["label"]) == 1), counts=pix)
+                bad = torch.as_tensor(np.asarray(batch["label"]) == 1)
+                pix = ops.threshold_confusion(amap, batch["mask"], pixel_thresholds, select=bad, counts=pix)
+                pix_auc.update(amap, batch["mask"], select=bad)
             out["anomaly_scores"].extend(compute_anomaly_score(recon, images).cpu().numpy())
             out["images"].extend(images.cpu()); out["reconstructions"].extend(recon.cpu())
             out["anomaly_maps"].extend(amap.cpu().numpy()); out["masks_true"].extend(batch["mask"].cpu().numpy())
@@ -69,6 +71,7 @@ def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None
     out["threshold"] = threshold
     if pix is not None:
         out["pixel_counts"] = {float(t): c for t, c in zip(pixel_thresholds, pix.cpu().tolist())}
+        out["pixel_auc"] = pix_auc.compute()
     return out
 
 
@@ -82,13 +85,15 @@ def evaluate_results(results, pixel_thresholds):
         for t in pixel_thresholds:
             tp, fp, fn, tn = results["pixel_counts"][float(t)]
             if tp + fn > 0 and fp + tn > 0:
-                ev["pixel_metrics"][f"threshold_{t}"] = metrics_from_counts(tp, fp, fn, tn)
+                ev["pixel_metrics"][f"threshold_{t}"] = {**metrics_from_counts(tp, fp, fn, tn),
+                                                         "auroc": results["pixel_auc"]["auroc"],
+                                                         "auprc": results["pixel_auc"]["auprc"]}
     elif bad.sum() > 0:
         truth = (results["masks_true"][bad] > 0.5).astype(np.uint8).ravel()
         if len(np.unique(truth)) > 1:
             for t in pixel_thresholds:
                 pred = (results["anomaly_maps"][bad] > t).astype(np.uint8).ravel()
-                ev["pixel_metrics"][f"threshold_{t}"] = calculate_metrics(truth, pred)
+                ev["pixel_metrics"][f"threshold_{t}"] = calculate_metrics(truth, pred, results["anomaly_maps"][bad].ravel())
     for kind in sorted(set(results["anomaly_types"])):
         sel = np.array([k == kind for k in results["anomaly_types"]])
         ev["type_metrics"][kind] = {"count": int(sel.sum()),
