@@ -435,6 +435,45 @@ size_t unet_rank_auc_workspace(int64_t n_pos, int64_t n_neg);
 int32_t unet_rank_auc(uint32_t* pos_keys, int64_t n_pos, uint32_t* neg_keys, int64_t n_neg, double* out,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* Region labelling of ground-truth masks (no reference counterpart: the per-region-overlap metric of the MVTec AD
+ * evaluation needs the connected defects, which scipy.ndimage.label would find on the host).  truth: fp32 [n][h][w]; a
+ * pixel is defective iff truth > 0.5 (as unet_threshold_confusion); a region is an 8-connected component of defective
+ * pixels of one image.  Over the images with select[n] != 0 (NULL: all): labels[n][h][w] (int32) = 1 + the smallest
+ * linear index y * w + x of the pixel's region, sizes[n][h][w] (int32) = the region's pixel count at every one of its
+ * pixels; both 0 at pixels that are not defective and in images that are not selected.  counts[3] = {regions, defective
+ * pixels, ok pixels} (int64, device) is ADDED to: zero it first.  Tiled union-find (LDS tiles, integer atomicMin on the
+ * links across tile borders, integer atomicAdd for the sizes) in separate launches: the outputs are a function of the
+ * masks alone.  Any h, w >= 1; n < 65536 and n h w <= 2^31 - 1, else UNET_ERR_UNSUPPORTED (and the workspace query
+ * returns 0).  Allocates nothing, does not synchronise. */
+size_t unet_label_regions_workspace(int64_t n, int64_t h, int64_t w);
+int32_t unet_label_regions(const float* truth, const uint8_t* select, int64_t n, int64_t h, int64_t w, int32_t* labels,
+                           int32_t* sizes, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* AUPRO: the area below the per-region-overlap curve up to a false-positive rate of fpr_limit, divided by fpr_limit (the
+ * localisation metric of the MVTec AD evaluation; no reference counterpart).  With R regions and N ok pixels, walking
+ * the distinct scores v downwards from the point (0, 0): fpr = #{ok pixels >= v} / N, pro = sum over the defective
+ * pixels >= v of 1 / (R * size of the pixel's region); the curve is piecewise linear through these points and the
+ * segment that crosses fpr_limit is cut there by interpolation.  Two steps, as unet_rank_auc:
+ * unet_region_auc_append: over the images with select[n] != 0 (NULL: all) of pred (fp32) / sizes (int32, of
+ * unet_label_regions), both [n_images][per_image]: every finite score becomes an order-preserving uint32 key
+ * (-0.0 == +0.0).  slots is capacity 8-byte slots: a defective pixel (sizes > 0) is written as the uint64 element
+ * key << 32 | size to slot counts[0] ... upwards, an ok pixel as a uint32 key to the uint32 entry
+ * 2 capacity - 1 - counts[1] ... downwards, in no particular order; counts[3] = {defective, ok, non-finite scores}
+ * (int64, device) is ADDED to: zero it first, and size capacity >= every selected pixel of every call that adds to the
+ * same counts.  Integer atomics only; allocates nothing, does not synchronise.
+ * unet_region_auc: sorts pos_pairs[n_pos] (on all 64 bits: every size must be <= max_region) and neg_keys[n_neg] (LSD
+ * radix sort; 16-byte aligned arrays, contents destroyed) and writes out[2] (fp64, device) = {AUPRO, pro at fpr_limit}.
+ * regions = R; 0 < fpr_limit <= 1.  n_pos == 0, n_neg == 0 or regions == 0: {0, 0}.  Non-finite scores are the
+ * caller's to handle.  n_pos + n_neg >= 2^31 is UNET_ERR_UNSUPPORTED (and the workspace query returns 0).  Ordered
+ * fp64 sums over the sorted arrays, no float atomics: the result depends only on the multiset of (score, region size)
+ * pixels, bitwise. */
+int32_t unet_region_auc_append(const float* pred, const int32_t* sizes, const uint8_t* select, int64_t n_images,
+                               int64_t per_image, void* slots, int64_t capacity, int64_t* counts, void* stream);
+size_t unet_region_auc_workspace(int64_t n_pos, int64_t n_neg);
+int32_t unet_region_auc(uint64_t* pos_pairs, int64_t n_pos, uint32_t* neg_keys, int64_t n_neg, int64_t regions,
+                        int64_t max_region, double fpr_limit, double* out, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 /* ---- nn.Dropout2d of SegmentationUNet's bottleneck (src/model.py:129,146): y = x * scale[n][c] on dense NHWC; the
  * caller draws scale = bernoulli(1-p)/(1-p) per (image, channel); the same call is the backward (dx = dy * scale). */
 int32_t unet_channel_scale(int32_t dtype, const void* x, const float* scale, int32_t n, int64_t hw, int32_t c, void* y,

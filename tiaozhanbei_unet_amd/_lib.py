@@ -118,6 +118,11 @@ SIGNATURES = {
     "unet_rank_auc_append": (_i, [_p, _p, _p, _l, _l, _p, _l, _p, _p]),
     "unet_rank_auc_workspace": (_z, [_l, _l]),
     "unet_rank_auc": (_i, [_p, _l, _p, _l, _p, _p, _z, _p]),
+    "unet_label_regions_workspace": (_z, [_l, _l, _l]),
+    "unet_label_regions": (_i, [_p, _p, _l, _l, _l, _p, _p, _p, _p, _z, _p]),
+    "unet_region_auc_append": (_i, [_p, _p, _p, _l, _l, _p, _l, _p, _p]),
+    "unet_region_auc_workspace": (_z, [_l, _l]),
+    "unet_region_auc": (_i, [_p, _l, _p, _l, _l, _l, _d, _p, _p, _z, _p]),
     "unet_channel_scale": (_i, [_i, _p, _p, _i, _l, _i, _p, _p]),
     "unet_anomaly_score_workspace": (_z, [_i, _l]),
     "unet_anomaly_score": (_i, [_p, _p, _i, _i, _l, _i, _p, _p, _p, _z, _p]),

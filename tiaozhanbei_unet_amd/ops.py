@@ -1219,6 +1219,27 @@ def threshold_confusion(pred, truth, thresholds, select=None, counts=None):
     return counts
 
 
+def _select_runs(select, n, what):
+    """(runs, device mask) of a per-image selection: a device mask goes to the kernels as it is (one run, all images); a
+    host mask becomes one launch per run of selected images, so nothing is copied and nothing synchronises."""
+    if select is None:
+        return [(0, n)], None
+    sel = torch.as_tensor(select)
+    if sel.numel() != n:
+        raise ValueError(f"{what}: select needs one entry per image")
+    if sel.is_cuda:
+        return [(0, n)], sel.reshape(-1).to(torch.uint8).contiguous()
+    on = sel.reshape(-1).to(torch.bool).tolist() + [False]
+    runs, start = [], None
+    for i, v in enumerate(on):
+        if v and start is None:
+            start = i
+        elif not v and start is not None:
+            runs.append((start, i))
+            start = None
+    return runs, None
+
+
 class BinaryAUC:
     """Pixel-level AUROC / AUPRC accumulated over batches: the roc_auc_score and auc(precision_recall_curve) that
     the reference src/utils.py:84-91 computes for calculate_pixel_metrics (:97-108), on the device.  A pixel is
@@ -1239,23 +1260,7 @@ class BinaryAUC:
             raise ValueError("BinaryAUC.update: prediction / truth shapes differ")
         n = p.shape[0]
         per = p.numel() // n
-        runs, sel = [(0, n)], None
-        if select is not None:
-            sel = torch.as_tensor(select)
-            if sel.numel() != n:
-                raise ValueError("BinaryAUC.update: select needs one entry per image")
-            if sel.is_cuda:
-                sel = sel.to(torch.uint8).contiguous()
-            else:                             # host mask: one launch per run of selected images, nothing to copy
-                on = sel.reshape(-1).to(torch.bool).tolist() + [False]
-                runs, start = [], None
-                for i, v in enumerate(on):
-                    if v and start is None:
-                        start = i
-                    elif not v and start is not None:
-                        runs.append((start, i))
-                        start = None
-                sel = None
+        runs, sel = _select_runs(select, n, "BinaryAUC.update")
         cap = sum(b - a for a, b in runs) * per
         if cap == 0:
             return
@@ -1289,6 +1294,109 @@ class BinaryAUC:
         L.check(lib.unet_rank_auc(_ptr(pos), n_pos, _ptr(neg), n_neg, _ptr(out), _ptr(ws), nbytes, _stream()),
                 "unet_rank_auc")
         res["auroc"], res["auprc"] = out.tolist()
+        return res
+
+
+def _image_planes(t, what):
+    """[N, H, W] view of a [N, ..., H, W] tensor with one plane per image ([N, W]: one row)."""
+    if t.dim() < 2:
+        raise ValueError(f"{what}: needs [N, ...] maps")
+    n, w = t.shape[0], t.shape[-1]
+    h = t.shape[-2] if t.dim() >= 3 else 1
+    if n == 0 or t.numel() != n * h * w:
+        raise ValueError(f"{what}: one H x W plane per image, got {tuple(t.shape)}")
+    return t.reshape(n, h, w)
+
+
+def label_regions(truth, select=None, _runs=None):
+    """8-connected regions of the defective pixels (truth > 0.5) of each image of truth [N, (1,) H, W], over the images
+    with select[n] true (None: all): (labels, sizes, counts), all DEVICE tensors.  labels (int32, truth's shape) = 1 +
+    the smallest linear index y * W + x of the pixel's region, sizes (int32) = the region's pixel count at each of its
+    pixels, both 0 elsewhere; counts (int64 [3]) = {regions, defective pixels, ok pixels} of the selected images.
+    scipy.ndimage.label(mask, np.ones((3, 3))) on the device (unet_label_regions); does not synchronise."""
+    _require_cuda(truth)
+    t = _image_planes(truth.detach().contiguous().float(), "label_regions")
+    n, h, w = t.shape
+    runs, sel = _runs if _runs is not None else _select_runs(select, n, "label_regions")
+    lib = L.lib()
+    labels = torch.zeros((n, h, w), dtype=torch.int32, device=t.device)
+    sizes = torch.zeros((n, h, w), dtype=torch.int32, device=t.device)
+    counts = torch.zeros(3, dtype=torch.int64, device=t.device)
+    for a, b in runs:
+        nbytes = lib.unet_label_regions_workspace(b - a, h, w)
+        if nbytes == 0:
+            raise RuntimeError(f"label_regions: {b - a} x {h} x {w} is not supported (n < 65536, at most 2^31 - 1 pixels)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+        L.check(lib.unet_label_regions(_ptr(t[a:b]), _ptr(sel), b - a, h, w, _ptr(labels[a:b]), _ptr(sizes[a:b]),
+                                       _ptr(counts), _ptr(ws), nbytes, _stream()), "unet_label_regions")
+    return labels.reshape(truth.shape), sizes.reshape(truth.shape), counts
+
+
+class RegionOverlapAUC:
+    """AUPRO accumulated over batches: the area below the per-region-overlap curve of the MVTec AD evaluation up to a
+    false-positive rate of ``fpr_limit``, divided by it.  A pixel is defective iff truth > 0.5, a region is an
+    8-connected component of defective pixels of one image, and every region weighs the same: a defective pixel lifts
+    the curve by 1 / (regions * its region's size).  ``update`` labels the batch's regions (unet_label_regions) and
+    appends the selected pixels as sort keys and (key, size) elements (unet_region_auc_append) without synchronising;
+    only those and the counts are kept.  ``compute`` reads the counts once, sorts and integrates (unet_region_auc).
+    No region, no ok pixel or any NaN / inf score give 0.0.  The result depends only on the multiset of (score, region
+    size) pixels, bitwise."""
+
+    def __init__(self, fpr_limit=0.3):
+        self.fpr_limit = float(fpr_limit)
+        if not 0.0 < self.fpr_limit <= 1.0:
+            raise ValueError(f"RegionOverlapAUC: fpr_limit {fpr_limit} is not in (0, 1]")
+        self._chunks = []                     # (slots, capacity, counts[6]): one exactly-sized chunk per update
+        self._max_region = 1
+
+    def update(self, pred, truth, select=None):
+        """pred / truth: device tensors of equal shape [N, (1,) H, W]; select: host or device bool per image."""
+        _require_cuda(pred)
+        p = pred.detach().contiguous().float()
+        t = truth.detach().to(p.device).contiguous().float()
+        if p.shape != t.shape:
+            raise ValueError("RegionOverlapAUC.update: prediction / truth shapes differ")
+        p = _image_planes(p, "RegionOverlapAUC.update")
+        n, per = p.shape[0], p.shape[1] * p.shape[2]
+        runs, sel = _select_runs(select, n, "RegionOverlapAUC.update")
+        cap = sum(b - a for a, b in runs) * per
+        if cap == 0:
+            return
+        _, sizes, regions = label_regions(t, _runs=(runs, sel))
+        sizes = sizes.reshape(p.shape)
+        slots = torch.empty(cap, dtype=torch.int64, device=p.device)
+        counts = torch.zeros(3, dtype=torch.int64, device=p.device)
+        lib = L.lib()
+        for a, b in runs:
+            L.check(lib.unet_region_auc_append(_ptr(p[a:b]), _ptr(sizes[a:b]), _ptr(sel), b - a, per, _ptr(slots), cap,
+                                               _ptr(counts), _stream()), "unet_region_auc_append")
+        self._chunks.append((slots, cap, torch.cat([counts, regions])))
+        self._max_region = max(self._max_region, per)
+
+    def compute(self):
+        """{"aupro", "pro_at_limit", "fpr_limit", "regions", "defective", "ok", "nonfinite"} over every update."""
+        totals = [0] * 6
+        if self._chunks:
+            per_chunk = torch.stack([c for _, _, c in self._chunks]).tolist()      # the one read of the counts
+            totals = [sum(c[i] for c in per_chunk) for i in range(6)]
+        n_pos, n_neg, nonfinite, regions, defective, ok = totals
+        res = {"aupro": 0.0, "pro_at_limit": 0.0, "fpr_limit": self.fpr_limit, "regions": regions,
+               "defective": defective, "ok": ok, "nonfinite": nonfinite}
+        if nonfinite or not regions or not ok:
+            return res
+        lib = L.lib()
+        nbytes = lib.unet_region_auc_workspace(n_pos, n_neg)
+        if nbytes == 0:
+            raise RuntimeError(f"RegionOverlapAUC: {n_pos + n_neg} pixels, at most 2^31 - 1 are supported")
+        dev = self._chunks[0][0].device
+        pos = torch.cat([s[:c[0]] for (s, _, _), c in zip(self._chunks, per_chunk)])          # copies: the sort
+        neg = torch.cat([s.view(torch.int32)[2 * cap - c[1]:]                                 # destroys its input
+                         for (s, cap, _), c in zip(self._chunks, per_chunk)])
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+        L.check(lib.unet_region_auc(_ptr(pos), n_pos, _ptr(neg), n_neg, regions, self._max_region, self.fpr_limit,
+                                    _ptr(out), _ptr(ws), nbytes, _stream()), "unet_region_auc")
+        res["aupro"], res["pro_at_limit"] = out.tolist()
         return res
 
 

@@ -25,6 +25,8 @@ FLAGS = [  # reference src/test.py:26-61
     ("--save_visualizations", dict(action="store_true")),
     ("--max_vis_samples", dict(type=int, default=20)),
     ("--precision", dict(type=str, default="fp32", choices=["fp32", "bf16"])),   # build-only
+    ("--pro_fpr_limit", dict(type=float, default=0.3)),     # build-only: the PRO curve is integrated up to this fpr
+    ("--binary_masks", dict(action="store_true")),          # build-only: masks as (mask > 0) instead of k / 255
 ]
 
 
@@ -32,10 +34,14 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Test UNet for MVTec anomaly detection (MI355X HIP path)")
     for name, kw in FLAGS:
         ap.add_argument(name, **kw)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not 0.0 < args.pro_fpr_limit <= 1.0:
+        raise SystemExit(f"--pro_fpr_limit must be in (0, 1], got {args.pro_fpr_limit}")
+    return args
 
 
-def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None):
+def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None, pro_fpr_limit=0.3,
+               binary_masks=False):
     from . import AnomalyUNet, ops
     from .utils import compute_anomaly_score, get_optimal_threshold
     model.eval()
@@ -43,6 +49,7 @@ def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None
                            "image_paths", "anomaly_scores")}
     pix = None
     pix_auc = ops.BinaryAUC()         # pixel AUROC / AUPRC of the anomalous images, ranked on the device (:172-178)
+    pix_pro = ops.RegionOverlapAUC(pro_fpr_limit)     # AUPRO over every test image (good ones supply ok pixels)
     with torch.no_grad():
         from .train_utils import _batches
         for batch, images, _ in _batches(test_loader, device):     # (raw uint8 batches are transformed on the device)
@@ -50,13 +57,15 @@ def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None
                 recon, amap = model(images)
             else:
                 amap, recon = model(images, sigmoid=True), images      # sigmoid inside the head kernel
+            masks = (batch["mask"] > 0).float() if binary_masks else batch["mask"]
             if pixel_thresholds:          # pixel-level confusion counts of the anomalous images, on the device (:86-101)
                 bad = torch.as_tensor(np.asarray(batch["label"]) == 1)
-                pix = ops.threshold_confusion(amap, batch["mask"], pixel_thresholds, select=bad, counts=pix)
-                pix_auc.update(amap, batch["mask"], select=bad)
+                pix = ops.threshold_confusion(amap, masks, pixel_thresholds, select=bad, counts=pix)
+                pix_auc.update(amap, masks, select=bad)
+                pix_pro.update(amap, masks)
             out["anomaly_scores"].extend(compute_anomaly_score(recon, images).cpu().numpy())
             out["images"].extend(images.cpu()); out["reconstructions"].extend(recon.cpu())
-            out["anomaly_maps"].extend(amap.cpu().numpy()); out["masks_true"].extend(batch["mask"].cpu().numpy())
+            out["anomaly_maps"].extend(amap.cpu().numpy()); out["masks_true"].extend(masks.cpu().numpy())
             out["labels"].extend(np.asarray(batch["label"])); out["anomaly_types"].extend(batch["anomaly_type"])
             out["image_paths"].extend(batch["image_path"])
     for k in ("labels", "anomaly_scores", "masks_true", "anomaly_maps"):
@@ -72,6 +81,7 @@ def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None
     if pix is not None:
         out["pixel_counts"] = {float(t): c for t, c in zip(pixel_thresholds, pix.cpu().tolist())}
         out["pixel_auc"] = pix_auc.compute()
+        out["pixel_pro"] = pix_pro.compute()
     return out
 
 
@@ -98,6 +108,9 @@ def evaluate_results(results, pixel_thresholds):
         sel = np.array([k == kind for k in results["anomaly_types"]])
         ev["type_metrics"][kind] = {"count": int(sel.sum()),
                                     "detected": int(results["predictions"][sel].sum())}
+    pro = results.get("pixel_pro")
+    if pro and pro["regions"] > 0 and pro["ok"] > 0:         # build-only: AUPRO of the MVTec AD evaluation
+        ev["region_metrics"] = {k: pro[k] for k in ("aupro", "pro_at_limit", "fpr_limit", "regions")}
     return ev
 
 
@@ -119,7 +132,8 @@ def main(argv=None):
     model = (AnomalyUNet(3, args.bilinear, precision=args.precision) if args.model == "anomaly_unet"
              else UNet(3, 1, args.bilinear, precision=args.precision)).to(device)
     load_checkpoint(model, None, args.checkpoint, device)
-    results = test_model(model, loader, device, args.threshold, pixel_thresholds=args.pixel_thresholds)
+    results = test_model(model, loader, device, args.threshold, pixel_thresholds=args.pixel_thresholds,
+                         pro_fpr_limit=args.pro_fpr_limit, binary_masks=args.binary_masks)
     ev = evaluate_results(results, args.pixel_thresholds)
     print_metrics(ev["image_metrics"], "Image-level")
 
