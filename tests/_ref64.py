@@ -23,6 +23,14 @@ BF16_MANT = 8                 # bf16 significand bits (7 stored + the implicit o
 # block at this K; the GPU tests assert they stay at or below it.
 MAX_WGRAD_K = 8 * 128 * 128
 
+# Reductions over pixels (BatchNorm statistics, dbeta / dgamma): the longest one the suite holds to 2^-18 S is the
+# benchmark's 32 x 256 x 256.  One missing 32-pixel row group moves a sum by about 32 |mean| (+ noise 6 sigma), the
+# bound at that length is 2^-18 * 2 097 152 * E|y| = 8 E|y|: such a defect is only visible when the channel has an offset.
+# The large GPU cases therefore give y and the gradient per-channel offsets of at least MIN_STREAM_OFFSET sigma;
+# test_cpu_ref64.py plants the defect at MAX_STREAM_PIXELS with exactly that offset, the GPU tests assert both limits.
+MAX_STREAM_PIXELS = 32 * 256 * 256
+MIN_STREAM_OFFSET = 1.0
+
 # worst err / bound seen per comparator kind in this process (printed by the tests, quoted in reviews)
 WORST = {"bf16": 0.0, "fp32": 0.0}
 
@@ -104,6 +112,329 @@ def sums_over_pixels(v):
     return v.sum((0, 2, 3)), v.abs().sum((0, 2, 3))
 
 
+# ------------------------------------------------------------------ streaming / reduction kernels: (value, S) in float64
+# These references take the compute dtype of the kernel under test: rd() gives the operands the kernel reads.
+def rd(t, dtype):
+    """the value a kernel of compute dtype `dtype` reads, exact in float64"""
+    return t.detach().to(dtype).to(torch.float64).cpu()
+
+
+def stored(v, dtype):
+    """a float64 value as a correct kernel stores it: rounded once to fp32 (the register), then to the compute dtype"""
+    return v.to(torch.float32).to(dtype).to(torch.float64)
+
+
+def _c(v):
+    return v.detach().to(torch.float64).cpu()[None, :, None, None]
+
+
+def _eps32(eps):
+    return float(torch.tensor(eps, dtype=torch.float32))
+
+
+def bn_train_stats(y, dtype, gamma, beta, running_mean=None, running_var=None, momentum=0.1, eps=1e-5):
+    """unet_bn_train_stats / unet_bn_finalize_partials: every output as (value, S) with SUM_EPS * S the DERIVED bound.
+
+    The kernel sums y and y^2 (|d sum y| <= SUM_EPS sum|y|, |d sum y^2| <= SUM_EPS sum y^2), everything after that is
+    fp64 until the fp32 store.  With M pixels:
+      mean    d_mean  = SUM_EPS E|y| + 2^-24 |mean|                              (sum error / M, one fp32 store)
+      var     d       = SUM_EPS (E[y^2] + 2 |mean| E|y|)                         (var = E[y^2] - mean^2)
+      istd    d_istd  = istd (d / (2 (var + eps)) + 2^-23)                        (d/dvar (var+eps)^-1/2, store + fp32 eps)
+      scale   d_scale = |gamma| d_istd + 2^-24 |scale|                           (product rule, one fp32 product)
+      shift   d_shift = |scale| d_mean + |mean| d_scale + 2^-23 (|beta| + |mean scale|)   (fma of the ROUNDED mean)
+      running mean / var = (1 - m) old + m new in fp32: m d_new + 2^-22 (|(1 - m) old| + |m new|)   (four fp32 roundings:
+              1 - m, two products, the sum), new variance = var M / (M - 1) (var itself when M = 1) with d M / (M - 1).
+    momentum=None of nn.BatchNorm2d is the caller passing 1 / num_batches_tracked as the momentum.
+    Also returns 'istd_rel' = d_istd / istd per channel (the allowed relative error the tests print)."""
+    y = rd(y, dtype)
+    M = y.numel() // y.shape[1]
+    g, b = gamma.detach().double().cpu(), beta.detach().double().cpu()
+    eps = _eps32(eps)
+    ea, ey2 = y.abs().mean((0, 2, 3)), (y * y).mean((0, 2, 3))
+    mean = y.mean((0, 2, 3))
+    var = ((y - mean[None, :, None, None]) ** 2).mean((0, 2, 3))           # two-pass: no cancellation in the reference
+    d_mean = SUM_EPS * ea + 2.0 ** -24 * mean.abs()
+    d = SUM_EPS * (ey2 + 2 * mean.abs() * ea)
+    istd = (var + eps).rsqrt()
+    d_istd = istd * (d / (2 * (var + eps)) + 2.0 ** -23)
+    scale = g * istd
+    d_scale = g.abs() * d_istd + 2.0 ** -24 * scale.abs()
+    shift = b - mean * scale
+    d_shift = scale.abs() * d_mean + mean.abs() * d_scale + 2.0 ** -23 * (b.abs() + (mean * scale).abs())
+    out = {"mean": (mean, d_mean / SUM_EPS), "istd": (istd, d_istd / SUM_EPS), "scale": (scale, d_scale / SUM_EPS),
+           "shift": (shift, d_shift / SUM_EPS), "var": (var, d / SUM_EPS), "istd_rel": d_istd / istd}
+    if running_mean is not None:
+        m = float(torch.tensor(momentum, dtype=torch.float32))
+        rm, rv = running_mean.detach().double().cpu(), running_var.detach().double().cpu()
+        k = M / (M - 1.0) if M > 1 else 1.0
+        unb = var * k
+        nrm, nrv = (1 - m) * rm + m * mean, (1 - m) * rv + m * unb
+        d_rm = m * d_mean + 2.0 ** -22 * (((1 - m) * rm).abs() + (m * mean).abs())
+        d_rv = m * (d * k + 2.0 ** -24 * unb) + 2.0 ** -22 * (((1 - m) * rv).abs() + (m * unb).abs())
+        out["running_mean"], out["running_var"] = (nrm, d_rm / SUM_EPS), (nrv, d_rv / SUM_EPS)
+    return out
+
+
+def bn_relu_apply(y, dtype, scale, shift):
+    """unet_bn_relu_apply (scale / shift from unet_bn_eval_coeffs or the test): a = max(y scale + shift, 0)"""
+    y = rd(y, dtype)
+    t = y * _c(scale)
+    return (t + _c(shift)).clamp_min(0), t.abs() + _c(shift).abs()
+
+
+def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps=1e-5):
+    """unet_bn_eval_coeffs(4): istd = (running_var + eps)^-1/2 (fp64, one fp32 store), scale = gamma istd, shift = beta -
+    running_mean scale (fp32): bounds as in bn_train_stats with exact statistics (d = d_mean = 0)."""
+    g, b = gamma.detach().double().cpu(), beta.detach().double().cpu()
+    rm, rv = running_mean.detach().double().cpu(), running_var.detach().double().cpu()
+    istd = (rv + _eps32(eps)).rsqrt()
+    d_istd = 2.0 ** -23 * istd
+    scale = g * istd
+    d_scale = g.abs() * d_istd + 2.0 ** -24 * scale.abs()
+    shift = b - rm * scale
+    d_shift = rm.abs() * d_scale + 2.0 ** -23 * (b.abs() + (rm * scale).abs())
+    return {"mean": (rm, torch.zeros_like(rm)), "istd": (istd, d_istd / SUM_EPS), "scale": (scale, d_scale / SUM_EPS),
+            "shift": (shift, d_shift / SUM_EPS)}
+
+
+def bn_bwd_premasked(dz, y, dtype, gamma, mean, istd, frozen=False):
+    """The BatchNorm backward for a gradient that carries the ReLU mask already (dz, y: as the kernel reads them):
+    dbeta = sum dz, dgamma = sum dz yhat (yhat = (y - mean) istd), dy = A dz + B y + K with A = gamma istd,
+    B = -A istd dgamma / M, K = -A dbeta / M - B mean (frozen statistics: B = K = 0).
+    S of dy: |A dz| for its own product, plus what the kernel's own dgamma / dbeta may be off by, carried through B and K:
+    |A| istd S_dgamma / M (|y| + |mean|) + |A| S_dbeta / M.  S_dgamma >= |dgamma|, so this also covers the fp32 roundings
+    of the coefficients and the cancellation of B y against K for a channel whose mean is large against its spread."""
+    dz, y = rd(dz, dtype), rd(y, dtype)
+    M = y.numel() // y.shape[1]
+    mu, si, A = _c(mean), _c(istd), _c(gamma) * _c(istd)
+    t = dz * ((y - mu) * si)
+    db, sdb = dz.sum((0, 2, 3)), dz.abs().sum((0, 2, 3))
+    dg, sdg = t.sum((0, 2, 3)), t.abs().sum((0, 2, 3))
+    if frozen:
+        dy, S = A * dz, (A * dz).abs()
+    else:
+        B = -A * si * dg[None, :, None, None] / M
+        K = -A * db[None, :, None, None] / M - B * mu
+        dy = A * dz + B * y + K
+        S = (A * dz).abs() + A.abs() * si * sdg[None, :, None, None] / M * (y.abs() + mu.abs()) \
+            + A.abs() * sdb[None, :, None, None] / M
+    return {"dbeta": (db, sdb), "dgamma": (dg, sdg), "dy": (dy, S)}
+
+
+def bn_relu_bwd(da, y, dtype, gamma, mean, istd, scale, shift, frozen=False, mask_ge=False):
+    """unet_bn_relu_bwd / _frozen: dz = da [y scale + shift > 0], then bn_bwd_premasked.  The sign of the fp32
+    fma(y, scale, shift) is the sign of the exact value (a rounding never crosses zero), so the mask of the sums is exact;
+    'clear' (bn_relu_mask) is for the element-wise dy comparison only.  mask_ge: the defective mask [z >= 0]."""
+    yq, daq = rd(y, dtype), rd(da, dtype)
+    z = yq * _c(scale) + _c(shift)
+    on = (z >= 0) if mask_ge else (z > 0)
+    dz = daq * on
+    out = bn_bwd_premasked(dz, yq, torch.float64, gamma, mean, istd, frozen)
+    out["dz"], out["on"], out["clear"] = (dz, dz.abs()), on, (z.abs() > 1e-4) | (z == 0)      # (an exact zero is no tie)
+    return out
+
+
+def maxpool2(x):
+    """MaxPool2d(2), floor: exact (no rounding freedom, compare with torch.equal)"""
+    return F.max_pool2d(x.detach().to(torch.float64).cpu(), 2)
+
+
+def maxpool2_route(x, g, last=False):
+    """gradient of MaxPool2d(2): g goes to the FIRST maximum of each window in row-major order (last=True: the defect),
+    rows / columns dropped by the floor get 0.  x, g float64.  Returns the routed gradient (exact: one term per element)."""
+    n, c, h, w = x.shape
+    oh, ow = h // 2, w // 2
+    win = x[:, :, :2 * oh, :2 * ow].reshape(n, c, oh, 2, ow, 2).permute(0, 1, 2, 4, 3, 5).reshape(n, c, oh, ow, 4)
+    eq = win == win.max(-1, keepdim=True).values
+    if last:
+        eq = eq.flip(-1)
+    first = eq & (eq.cumsum(-1) == 1)
+    if last:
+        first = first.flip(-1)
+    r = (first * g[..., None]).reshape(n, c, oh, ow, 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(n, c, 2 * oh, 2 * ow)
+    return F.pad(r, [0, w - 2 * ow, 0, h - 2 * oh])
+
+
+def bn_relu_pool_bwd(y, dpooled, da_old, dtype, scale, shift, mean):
+    """unet_bn_relu_pool_bwd: da = da_old + route(dpooled) with the route taken on the activation AS STORED (a rounded to
+    the compute dtype: ties between stored values go to the first), stored once; dz = da [z > 0] on the fp32
+    pre-activation; the two sums run over the STORED dz: sum dz, sum dz (y - mean).
+    -> {'dz': (value, S), 'dz_stored', 'sum': (.., S), 'sum_c': (.., S)}"""
+    yq, g = rd(y, dtype), rd(dpooled, dtype)
+    old = rd(da_old, dtype) if da_old is not None else torch.zeros_like(yq)
+    z = yq * _c(scale) + _c(shift)
+    routed = maxpool2_route(stored(z.clamp_min(0), dtype), g)
+    on = z > 0
+    da = old + routed
+    dzs = stored(da, dtype) * on
+    t = dzs * (yq - _c(mean))
+    return {"dz": (da * on, (old.abs() + routed.abs()) * on), "dz_stored": dzs, "on": on,
+            "sum": (dzs.sum((0, 2, 3)), dzs.abs().sum((0, 2, 3))), "sum_c": (t.sum((0, 2, 3)), t.abs().sum((0, 2, 3)))}
+
+
+def bilinear_weights(n_in, wrong=False):
+    """[2 n_in][n_in] interpolation matrix of nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True) in
+    float64: source coordinate o (n_in - 1) / (2 n_in - 1) (wrong=True: n_in / (2 n_in), the defect)"""
+    n_out = 2 * n_in
+    o = torch.arange(n_out, dtype=torch.float64)
+    src = o * ((n_in / n_out) if wrong else ((n_in - 1) / (n_out - 1)))
+    i0 = src.floor().clamp_max(n_in - 1).long()
+    i1 = (i0 + 1).clamp_max(n_in - 1)
+    f = src - i0
+    m = torch.zeros(n_out, n_in, dtype=torch.float64)
+    m.scatter_add_(1, i0[:, None], (1 - f)[:, None])
+    m.scatter_add_(1, i1[:, None], f[:, None])
+    return m
+
+
+def bilinear2x(x, dtype, wrong=False):
+    """unet_upsample_bilinear2x_fwd: weighted sum of the four neighbours, S = the same sum of |.| (weights >= 0)"""
+    x = rd(x, dtype)
+    wy, wx = bilinear_weights(x.shape[2], wrong), bilinear_weights(x.shape[3], wrong)
+    f = lambda v: torch.einsum("oh,nchw,pw->ncop", wy, v, wx)       # noqa: E731
+    return f(x), f(x.abs())
+
+
+def bilinear2x_bwd(dy, dtype):
+    """unet_upsample_bilinear2x_bwd: the adjoint"""
+    dy = rd(dy, dtype)
+    wy, wx = bilinear_weights(dy.shape[2] // 2), bilinear_weights(dy.shape[3] // 2)
+    f = lambda v: torch.einsum("oh,ncop,pw->nchw", wy, v, wx)       # noqa: E731
+    return f(dy), f(dy.abs())
+
+
+def adam_step(p, g, m, v, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, decoupled=False,
+              grad_scale=1.0, bias_step=None, swap_decay=False):
+    """one step of torch.optim.Adam (L2 decay joins the gradient) / AdamW (decoupled: p *= 1 - lr wd first) in float64
+    from the state given.  -> ((p, S), (m, S), (v, S)); S = |value| + the absolute terms it was formed from.
+    bias_step / swap_decay (the other decay rule): the planted defects of test_cpu_ref64.py."""
+    p, g, m, v = (t.detach().to(torch.float64).cpu() for t in (p, g, m, v))
+    lr, eps, wd = (float(torch.tensor(x, dtype=torch.float32)) for x in (lr, eps, weight_decay))
+    g = g * grad_scale
+    sp = p.abs()
+    if decoupled != swap_decay:
+        p = p * (1 - lr * wd)
+    else:
+        g = g + wd * p
+    m2 = beta1 * m + (1 - beta1) * g
+    v2 = beta2 * v + (1 - beta2) * g * g
+    t = step if bias_step is None else bias_step
+    bc1, bc2 = 1 - beta1 ** t, 1 - beta2 ** t
+    upd = lr / bc1 * m2 / (v2.sqrt() / bc2 ** 0.5 + eps)
+    p2 = p - upd
+    return ((p2, p2.abs() + sp + upd.abs()), (m2, m2.abs() + (beta1 * m).abs() + ((1 - beta1) * g).abs()),
+            (v2, 2 * v2))
+
+
+def anomaly_score(recon, image, l1=False):
+    """unet_anomaly_score: score = mean_c (recon - image)^2 (l1: mean_c |.|) per pixel, image_score = its mean over the
+    pixels.  S: the same with |recon| + |image| for the difference (the subtraction is rounded relative to its operands).
+    -> ((score, S), (image_score, S))"""
+    r, i = recon.detach().double().cpu(), image.detach().double().cpu()
+    d, a = r - i, r.abs() + i.abs()
+    v, S = (d.abs(), a) if l1 else (d * d, a * a)
+    v, S = v.mean(1), S.mean(1)
+    return (v, S), (v.flatten(1).mean(1), S.flatten(1).mean(1))
+
+
+def mse_focal(recon, image, amap, mask, alpha=0.25, gamma=2.0):
+    """unet_loss_mse_focal, the oracle's formula (oracle/unet_oracle.py combined_loss / focal_loss / _BCE) in float64,
+    clamps included: mse = mean d^2, d_recon = 2 d / n; bce = -(t max(log p, -100) + (1 - t) max(log(1 - p), -100)),
+    pt = exp(-bce), focal = mean alpha (1 - pt)^gamma bce, d_amap = alpha ((1 - pt)^gamma + gamma (1 - pt)^(gamma - 1) pt bce)
+    (p - t) / max((1 - p) p, 1e-12) / n.  S = |value| + the absolute terms it was formed from: 1 - pt is formed from 1 and
+    pt, so S carries (1 + pt) in its place; d carries |recon| + |image|."""
+    r, i = recon.detach().double().cpu().reshape(-1), image.detach().double().cpu().reshape(-1)
+    p, t = amap.detach().double().cpu().reshape(-1), mask.detach().double().cpu().reshape(-1)
+    d, a = r - i, r.abs() + i.abs()
+    bce = -(t * p.log().clamp_min(-100.0) + (1 - t) * (1 - p).log().clamp_min(-100.0))
+    pt = (-bce).exp()
+    om, op = 1 - pt, 1 + pt
+    dbce = (p - t) / ((1 - p) * p).clamp_min(1e-12)
+    na = p.numel()
+
+    def dfoc(x):
+        return alpha * (x ** gamma + gamma * x ** (gamma - 1) * pt * bce) * dbce / na
+    return {"mse": ((d * d).mean(), (a * a).mean()), "d_recon": (2 * d / d.numel(), 2 * a / d.numel()),
+            "focal": ((alpha * om ** gamma * bce).mean(), (alpha * op ** gamma * bce).mean()),
+            "d_amap": (dfoc(om), dfoc(op).abs())}
+
+
+def head_fwd(x, dtype, weight, bias, sigmoid):
+    """unet_head_fwd: out = conv1x1(x, w) + b (fp32 NCHW), optionally through a sigmoid.  Logits: S = sum |x w| + |b|.
+    Probabilities s: S = s + s (1 - s) S_logit (the value, plus what the logit's summation error becomes behind the
+    sigmoid's slope); the sigmoid itself is a library function -> assert_measured(extra=SUM_EPS)."""
+    x, w, b = rd(x, dtype), weight.detach().double().cpu(), bias.detach().double().cpu()
+    z, S = F.conv2d(x, w, b), F.conv2d(x.abs(), w.abs(), b.abs())
+    if not sigmoid:
+        return z, S
+    s = torch.sigmoid(z)
+    return s, s + s * (1 - s) * S
+
+
+def head_bwd(x, dtype, out, dout, weight, sigmoid):
+    """unet_head_bwd from the forward result `out` and its gradient `dout` as the kernel reads them (fp32): dlogit = dout
+    out (1 - out) with a sigmoid, dout without; dx = sum_co dlogit w (compute dtype), dW = sum_pixels dlogit x, db = sum_pixels
+    dlogit (fp32).  S: the sums of the absolute products.  -> {'dx', 'dw', 'db'}"""
+    x, w = rd(x, dtype), weight.detach().double().cpu()
+    o, g = out.detach().double().cpu(), dout.detach().double().cpu()
+    dl = g * o * (1 - o) if sigmoid else g
+    w2 = w.flatten(1)
+    return {"dx": (torch.einsum("nohw,oi->nihw", dl, w2), torch.einsum("nohw,oi->nihw", dl.abs(), w2.abs())),
+            "dw": (torch.einsum("nohw,nihw->oi", dl, x)[:, :, None, None], torch.einsum("nohw,nihw->oi", dl.abs(), x.abs())[:, :, None, None]),
+            "db": (dl.sum((0, 2, 3)), dl.abs().sum((0, 2, 3)))}
+
+
+def head_bnrelu_fwd(y, dtype, scale, shift, weight, bias, sigmoid):
+    """unet_head_bnrelu_fwd: the 1x1 head on a = max(y scale + shift, 0) formed on load and rounded to the compute dtype
+    like the stored activation of the unfused pair -- bn_relu_apply, stored, then head_fwd."""
+    a = stored(bn_relu_apply(y, dtype, scale, shift)[0], dtype)
+    return head_fwd(a, torch.float64, weight, bias, sigmoid)
+
+
+def head_bnrelu_bwd(y, dtype, scale, shift, mean, out, dout, weight, sigmoid):
+    """unet_head_bnrelu_bwd: head_bwd on the recomputed, rounded activation (dW, db); dz = dx [y scale + shift > 0] stored
+    once in the compute dtype; the BatchNorm-backward partials are sums over the STORED dz: sum dz, sum dz (y - mean).
+    -> {'dw', 'db', 'dz', 'dz_stored', 'sum', 'sum_c'}"""
+    yq = rd(y, dtype)
+    z = yq * _c(scale) + _c(shift)
+    hb = head_bwd(stored(z.clamp_min(0), dtype), torch.float64, out, dout, weight, sigmoid)
+    on = z > 0
+    dzs = stored(hb["dx"][0], dtype) * on
+    t = dzs * (yq - _c(mean))
+    return {"dw": hb["dw"], "db": hb["db"], "dz": (hb["dx"][0] * on, hb["dx"][1] * on), "dz_stored": dzs,
+            "sum": (dzs.sum((0, 2, 3)), dzs.abs().sum((0, 2, 3))), "sum_c": (t.sum((0, 2, 3)), t.abs().sum((0, 2, 3)))}
+
+
+def ssim(img1, img2, window=11, per_image=False):
+    """unet_ssim_loss (per_image: unet_ssim_loss_per_image), the oracle's formula (oracle/unet_oracle.py ssim_loss) in
+    float64: depthwise Gaussian blur with zero padding, variances as E[x^2] - mu^2, C1 = 1e-4, C2 = 9e-4,
+    loss = 1 - mean(map) over everything, or per image.  The gradient is the blur of the five adjoint maps
+    M = d loss / d (mu1, mu2, E11, E22, E12):  d img1 = blur(M_mu1) + 2 img1 blur(M_E11) + img2 blur(M_E12), d img2 alike.
+    S of a gradient: the same expression over |M| and |img|; S of a loss: 1 + mean |map|.
+    -> {'loss': (v, S), 'd1': (v, S), 'd2': (v, S)}"""
+    from oracle import unet_oracle as O
+    x, y = img1.detach().double().cpu(), img2.detach().double().cpu()
+    c = x.shape[1]
+    win = O.gaussian_window(window, 1.5, torch.float64)[None, None].expand(c, 1, -1, -1).contiguous()
+
+    def blur(t):
+        return F.conv2d(t, win, padding=window // 2, groups=c)
+    lv = [blur(t).requires_grad_(True) for t in (x, y, x * x, y * y, x * y)]
+    mu1, mu2, e11, e22, e12 = lv
+    c1, c2 = 0.01 ** 2, 0.03 ** 2
+    smap = ((2 * mu1 * mu2 + c1) * (2 * (e12 - mu1 * mu2) + c2)) / ((mu1 * mu1 + mu2 * mu2 + c1) * (e11 - mu1 * mu1 + e22 - mu2 * mu2 + c2))
+    if per_image:
+        loss, sl = 1 - smap.mean((1, 2, 3)), 1 + smap.abs().mean((1, 2, 3))
+    else:
+        loss, sl = 1 - smap.mean(), 1 + smap.abs().mean()
+    m1, m2, m11, m22, m12 = torch.autograd.grad(loss.sum(), lv)
+    d1 = blur(m1) + 2 * x * blur(m11) + y * blur(m12)
+    d2 = blur(m2) + 2 * y * blur(m22) + x * blur(m12)
+    s1 = blur(m1.abs()) + 2 * x.abs() * blur(m11.abs()) + y.abs() * blur(m12.abs())
+    s2 = blur(m2.abs()) + 2 * y.abs() * blur(m22.abs()) + x.abs() * blur(m12.abs())
+    return {"loss": (loss.detach(), sl.detach()), "d1": (d1, s1), "d2": (d2, s2)}
+
+
 # ------------------------------------------------------------------ comparator
 def _where(idx, shape):
     out = []
@@ -148,3 +479,29 @@ def assert_fp32(out, ref_s, what, mask=None):
     """fp32-stored output (dw, db, statistics sums): |out - ref| <= 2^-18 S; returns the worst err / bound"""
     ref, S = ref_s
     return _compare("fp32", out, ref, S, what, mask)
+
+
+MEASURED = {}                 # what -> (host err / S, kernel err / S, allowed / S) of assert_measured, for the results file
+MEASURED_FLOOR = 2.0 ** -22   # never ask for less than 4 fp32 roundings of S
+
+
+def assert_measured(out, ref_s, host, what, extra=0.0, mask=None):
+    """fp32 output of a kernel whose error is a library function's (sqrt, log, pow, a division), not a summation's: the
+    oracle's fp32 CPU evaluation `host` of the same formula on the same inputs is measured against the float64 value,
+    worst |err| / S, and the kernel gets 4 x that, never less than 2^-22 S (device functions are specified to 1-2 ulp
+    where the host libm is within 1; fma contraction).  extra: added to the allowed ratio (SUM_EPS for reduced scalars).
+    Results in fp32's denormal range are held to 2^-148 absolutely and left out of the measured ratio (a store there is
+    not a relative error).  Returns the worst err / bound."""
+    ref, S = ref_s
+    S = S.to(torch.float64)
+    tiny = 2.0 ** -148                 # two stores in fp32's denormal range (half of 2^-149 each, the first carried along)
+    normal = ref.abs() >= 2.0 ** -126                   # denormal results are held absolutely, and kept out of the ratio
+    if mask is not None:
+        normal = normal & mask
+    den = torch.where(S > 0, S, torch.full_like(S, 1e-300))
+    hr = torch.where(normal, (host.detach().to(torch.float64).cpu() - ref).abs() / den, torch.zeros_like(den))
+    host_ratio = float(hr.max())
+    allow = max(4 * host_ratio, MEASURED_FLOOR) + extra
+    kr = torch.where(normal, (out.detach().to(torch.float64).cpu() - ref).abs() / den, torch.zeros_like(den))
+    MEASURED[what] = (host_ratio, float(kr.max()), allow)
+    return _compare("fp32", out, ref, (S * allow + tiny) / SUM_EPS, what, mask)

@@ -1,6 +1,7 @@
 """CPU self-test of tests/_ref64.py: the exact reference passes its own comparator, and the defects the bf16 GPU tests
 are there to catch -- one dropped product term, truncating instead of round-to-nearest-even, one missing 32-pixel
-block of a weight-gradient reduction at the largest K the suite uses -- are rejected."""
+block of a weight-gradient reduction at the largest K the suite uses -- are rejected.  The second half does the same for
+the references of the streaming and reduction kernels (BatchNorm, pooling, bilinear, Adam)."""
 import pytest
 import torch
 
@@ -102,3 +103,369 @@ def test_half_ulp_is_exact():
     # a correct round-to-nearest-even of any value lands within it
     u = _gen(14, (10000,)) * 100
     assert bool(((u.float().bfloat16().double() - u).abs() <= R.half_ulp_bf16(u) + 2.0 ** -24 * u.abs()).all())     # (+ the fp32 step)
+
+
+# ====================================================================== streaming / reduction kernels
+# (BatchNorm, pooling, bilinear, Adam): the references equal torch in float64, the exact value stored the way a correct
+# kernel stores it passes, and each planted defect is rejected at the largest size the GPU tests use it at.
+F = torch.nn.functional
+EPS32 = float(torch.tensor(1e-5, dtype=torch.float32))
+F64 = torch.float64
+
+
+def _close(a, b):
+    return torch.allclose(a, b, rtol=1e-12, atol=1e-12)
+
+
+def _bn_case(seed, shape, offset=0.3):
+    c = shape[1]
+    y = _gen(seed, shape) * 1.7 + offset
+    ga, be = torch.rand(c, generator=torch.Generator().manual_seed(seed + 1), dtype=F64) + 0.5, _gen(seed + 2, (c,)) * 0.3
+    rm, rv = _gen(seed + 3, (c,)) * 0.1, torch.rand(c, generator=torch.Generator().manual_seed(seed + 4), dtype=F64) + 0.5
+    return y, ga, be, rm, rv, _gen(seed + 5, shape)
+
+
+@pytest.mark.parametrize("momentum", [0.1, 1.0 / 3.0])          # (momentum=None: the caller passes 1 / batches seen)
+def test_bn_references_match_autograd(momentum):
+    y, ga, be, rm, rv, da = _bn_case(20, (3, 8, 7, 5))
+    m32 = float(torch.tensor(momentum, dtype=torch.float32))
+    yr, gr, br = y.clone().requires_grad_(True), ga.clone().requires_grad_(True), be.clone().requires_grad_(True)
+    trm, trv = rm.clone(), rv.clone()
+    a = F.relu(F.batch_norm(yr, trm, trv, gr, br, True, m32, EPS32))
+    a.backward(da)
+    st = R.bn_train_stats(y, F64, ga, be, rm, rv, momentum, 1e-5)
+    assert _close(st["mean"][0], y.mean((0, 2, 3))) and _close(st["var"][0], y.var((0, 2, 3), unbiased=False))
+    assert _close(st["running_mean"][0], trm) and _close(st["running_var"][0], trv)
+    scale, shift, mean, istd = st["scale"][0], st["shift"][0], st["mean"][0], st["istd"][0]
+    assert _close(R.bn_relu_apply(y, F64, scale, shift)[0], a.detach())
+    bw = R.bn_relu_bwd(da, y, F64, ga, mean, istd, scale, shift)
+    assert _close(bw["dbeta"][0], br.grad) and _close(bw["dgamma"][0], gr.grad) and _close(bw["dy"][0], yr.grad)
+    # frozen statistics (eval-mode BatchNorm inside a training graph) and the eval coefficients
+    yr2, gr2, br2 = y.clone().requires_grad_(True), ga.clone().requires_grad_(True), be.clone().requires_grad_(True)
+    a2 = F.relu(F.batch_norm(yr2, rm, rv, gr2, br2, False, 0.0, EPS32))
+    a2.backward(da)
+    ev = R.bn_eval_coeffs(ga, be, rm, rv)
+    assert _close(R.bn_relu_apply(y, F64, ev["scale"][0], ev["shift"][0])[0], a2.detach())
+    fz = R.bn_relu_bwd(da, y, F64, ga, ev["mean"][0], ev["istd"][0], ev["scale"][0], ev["shift"][0], frozen=True)
+    assert _close(fz["dbeta"][0], br2.grad) and _close(fz["dgamma"][0], gr2.grad) and _close(fz["dy"][0], yr2.grad)
+
+
+def test_single_pixel_statistics_are_finite():
+    y, ga, be, rm, rv, _ = _bn_case(26, (1, 4, 1, 1))
+    st = R.bn_train_stats(y, F64, ga, be, rm, rv)
+    assert torch.equal(st["var"][0], torch.zeros(4, dtype=F64)) and _close(st["istd"][0], torch.full((4,), EPS32 ** -0.5, dtype=F64))
+    assert _close(st["running_var"][0], (1 - float(torch.tensor(0.1, dtype=torch.float32))) * rv) and bool(torch.isfinite(st["running_var"][0]).all())
+
+
+def test_pool_and_bilinear_references_match_autograd():
+    x = _gen(30, (2, 3, 7, 9)).bfloat16().double()
+    x[:, 0, 0:2, 0:2] = 1.5                                       # ties: first maximum
+    g = _gen(31, (2, 3, 3, 4)).bfloat16().double()
+    xr = x.clone().requires_grad_(True)
+    yp = F.max_pool2d(xr, 2)
+    yp.backward(g)
+    assert torch.equal(R.maxpool2(x), yp.detach()) and torch.equal(R.maxpool2_route(x, g), xr.grad)
+    assert float(R.maxpool2_route(x, g)[:, :, 6].abs().max()) == 0 and float(R.maxpool2_route(x, g)[:, :, :, 8].abs().max()) == 0
+    # fused BatchNorm + ReLU + pool backward, scale 1 / shift 0 on bf16-grid data in fp32: every store is exact
+    old = _gen(32, (2, 3, 7, 9)).bfloat16().double()
+    one, zero = torch.ones(3), torch.zeros(3)
+    xr = x.clone().requires_grad_(True)
+    ar = F.relu(xr)
+    (F.max_pool2d(ar, 2) * g).sum().backward(retain_graph=True)
+    ar.backward(old)
+    pb = R.bn_relu_pool_bwd(x, g, old, torch.float32, one, zero, zero)
+    assert _close(pb["dz"][0], xr.grad) and _close(pb["dz_stored"], xr.grad)
+    assert _close(pb["sum"][0], xr.grad.sum((0, 2, 3))) and _close(pb["sum_c"][0], (xr.grad * x).sum((0, 2, 3)))
+    for shape in ((2, 3, 5, 4), (1, 2, 1, 6), (1, 2, 3, 1)):
+        u = _gen(33, shape)
+        ur = u.clone().requires_grad_(True)
+        up = F.interpolate(ur, scale_factor=2, mode="bilinear", align_corners=True)
+        gy = _gen(34, tuple(up.shape))
+        up.backward(gy)
+        assert _close(R.bilinear2x(u, F64)[0], up.detach()) and _close(R.bilinear2x_bwd(gy, F64)[0], ur.grad)
+
+
+@pytest.mark.parametrize("decoupled", [False, True], ids=["adam", "adamw"])
+def test_adam_reference_matches_torch_optim(decoupled):
+    p0, g1, g2 = _gen(40, (257,)), _gen(41, (257,)), _gen(42, (257,))
+    lr, eps, wd = (float(torch.tensor(x, dtype=torch.float32)) for x in (1e-3, 1e-8, 1e-2))
+    ref = torch.nn.Parameter(p0.clone())
+    opt = (torch.optim.AdamW if decoupled else torch.optim.Adam)([ref], lr=lr, eps=eps, weight_decay=wd)
+    p, m, v = p0, torch.zeros_like(p0), torch.zeros_like(p0)
+    for step, g in enumerate((g1, g2), 1):
+        ref.grad = g.clone()
+        opt.step()
+        (p, _), (m, _), (v, _) = R.adam_step(p, g, m, v, step, 1e-3, 0.9, 0.999, 1e-8, 1e-2, decoupled)
+    assert _close(p, ref.detach()) and _close(m, opt.state[ref]["exp_avg"]) and _close(v, opt.state[ref]["exp_avg_sq"])
+
+
+# ---------------------------------------------------------------------- exact values pass, planted defects do not
+@pytest.fixture(scope="module")
+def stream_case():
+    """bf16-grid data of the GPU tests' generator: 1.7 randn + 0.3, scale in [0.5, 1.5), shift = 0.3 randn; exact zeros
+    and negative zeros planted in channel 0 (with shift[0] = 0 the pre-activation there is exactly 0)"""
+    y, ga, be, rm, rv, da = _bn_case(50, (4, 8, 64, 64))
+    y = y.bfloat16().double()
+    y[:, 0, ::2, ::3] = 0.0
+    y[:, 0, 1::2, ::3] = -0.0
+    scale, shift = ga.float(), (be * 1.0).float()
+    shift[0] = 0.0
+    return y, da.bfloat16().double(), scale, shift
+
+
+def test_exact_streaming_values_are_accepted(stream_case):
+    y, da, scale, shift = stream_case
+    for dt in (torch.bfloat16, torch.float32):
+        a = R.bn_relu_apply(y, dt, scale, shift)
+        (R.assert_bf16 if dt == torch.bfloat16 else R.assert_fp32)(R.stored(a[0], dt), a, "exact bn apply")
+    mean, istd = _gen(51, (8,)).float() * 0.1, (torch.rand(8) + 0.5)
+    bw = R.bn_relu_bwd(da, y, torch.bfloat16, scale / istd, mean, istd, scale, shift)
+    R.assert_bf16(_as_kernel_bf16(bw["dy"][0]), bw["dy"], "exact bn dy", mask=bw["clear"])
+    assert float((~bw["clear"]).double().mean()) <= 1e-3
+    R.assert_fp32(bw["dbeta"][0].float(), bw["dbeta"], "exact dbeta")
+    R.assert_fp32(bw["dgamma"][0].float(), bw["dgamma"], "exact dgamma")
+    up = R.bilinear2x(y, torch.bfloat16)
+    R.assert_bf16(_as_kernel_bf16(up[0]), up, "exact bilinear")
+    st = R.bn_train_stats(y, torch.bfloat16, scale, shift, mean, istd)
+    for k in ("mean", "istd", "scale", "shift", "running_mean", "running_var"):
+        R.assert_fp32(st[k][0].float(), st[k], "exact " + k)
+
+
+def test_truncating_streaming_stores_are_rejected(stream_case):
+    y, da, scale, shift = stream_case
+    a = R.bn_relu_apply(y, torch.bfloat16, scale, shift)
+    with pytest.raises(AssertionError):
+        R.assert_bf16(R.round_bf16_toward_zero(a[0]), a, "truncated bn apply")
+    up = R.bilinear2x(y, torch.bfloat16)
+    with pytest.raises(AssertionError):
+        R.assert_bf16(R.round_bf16_toward_zero(up[0]), up, "truncated bilinear")
+    dn = R.bilinear2x_bwd(da, torch.bfloat16)
+    with pytest.raises(AssertionError):
+        R.assert_bf16(R.round_bf16_toward_zero(dn[0]), dn, "truncated bilinear adjoint")
+
+
+def test_wrong_relu_masks_are_rejected(stream_case):
+    """[z >= 0] instead of [z > 0] on data with exact zeros and negative zeros, and a mask taken from a ROUNDED value
+    (the product y * scale rounded to bf16 before the shift is added) instead of the fp32 pre-activation.  The mask of the
+    stored activation, bf16(max(z, 0)) > 0, is the same mask -- bf16 has fp32's exponent range -- and must pass."""
+    y, da, scale, shift = stream_case
+    mean, istd = torch.zeros(8), torch.ones(8)
+    bw = R.bn_relu_bwd(da, y, torch.bfloat16, scale, mean, istd, scale, shift)
+    ge = R.bn_relu_bwd(da, y, torch.bfloat16, scale, mean, istd, scale, shift, mask_ge=True)
+    assert bool((ge["on"] != bw["on"]).any())                     # the planted zeros are where the two masks differ
+    with pytest.raises(AssertionError):
+        R.assert_fp32(ge["dbeta"][0].float(), bw["dbeta"], "dbeta with >= mask")
+    with pytest.raises(AssertionError):
+        R.assert_bf16(_as_kernel_bf16(ge["dz"][0]), bw["dz"], "dz with >= mask")
+    a = R.stored(R.bn_relu_apply(y, torch.bfloat16, scale, shift)[0], torch.bfloat16)
+    assert torch.equal(a > 0, bw["on"])
+    zr = R.stored(R.rd(y, torch.bfloat16) * scale.double()[None, :, None, None], torch.bfloat16) + shift.double()[None, :, None, None]
+    assert bool(((zr > 0) != bw["on"]).any())
+    with pytest.raises(AssertionError):
+        R.assert_bf16(_as_kernel_bf16(R.rd(da, torch.bfloat16) * (zr > 0)), bw["dz"], "dz with the mask of a rounded product")
+
+
+@pytest.mark.parametrize("offset", [1.0, 30.0])
+def test_missing_and_repeated_row_group_is_rejected_at_the_largest_reduction(offset):
+    """one 32-pixel row group missing from / counted twice in sum y, sum y^2 (seen through mean and E[y^2]), dbeta and dgamma
+    at 2 097 152 pixels, with the smallest per-channel offset the large GPU cases use"""
+    pixels = R.MAX_STREAM_PIXELS
+    assert offset >= R.MIN_STREAM_OFFSET
+    y = (_gen(60, (1, 2, pixels, 1)) + offset).bfloat16().double()
+    da = (_gen(61, (1, 2, pixels, 1)) + offset).bfloat16().double()
+    s = (y.sum((0, 2, 3)), y.abs().sum((0, 2, 3)))
+    ss = ((y * y).sum((0, 2, 3)), (y * y).sum((0, 2, 3)))
+    gamma, mean, istd = torch.ones(2), torch.zeros(2), torch.ones(2)          # yhat = y: dgamma = sum dz y
+    bw = R.bn_relu_bwd(da, y, torch.bfloat16, gamma, mean, istd, torch.ones(2), torch.full((2,), 100.0))    # mask all on
+    terms = {"sum y": (s, y), "sum y^2": (ss, y * y), "dbeta": (bw["dbeta"], da), "dgamma": (bw["dgamma"], da * y)}
+    for name, (rs, t) in terms.items():
+        R.assert_fp32(rs[0].float(), rs, "exact " + name)
+        groups = t.view(2, -1, 32).sum(2)
+        k = int(groups[0].abs().argsort()[groups.shape[1] // 2])            # a group of median weight
+        for sign in (-1.0, 1.0):
+            bad = rs[0].clone()
+            bad[0] += sign * groups[0, k]
+            with pytest.raises(AssertionError):
+                R.assert_fp32(bad.float(), rs, f"{name} row group {'twice' if sign > 0 else 'missing'}")
+
+
+def test_zero_mean_data_would_hide_a_missing_row_group():
+    """why the large cases carry an offset: on zero-mean data the same defect is inside the bound"""
+    y = _gen(62, (1, 1, R.MAX_STREAM_PIXELS, 1)).bfloat16().double()
+    rs = (y.sum((0, 2, 3)), y.abs().sum((0, 2, 3)))
+    groups = y.view(-1, 32).sum(1)
+    bad = rs[0] - groups[int(groups.abs().argsort()[groups.numel() // 2])]
+    assert R.assert_fp32(bad.float(), rs, "zero-mean, group missing") < 1.0
+
+
+def test_wrong_variance_denominators_are_rejected():
+    y, ga, be, rm, rv, _ = _bn_case(70, (2, 8, 12, 20))
+    y = y.bfloat16().double()
+    M = 2 * 12 * 20
+    st = R.bn_train_stats(y, torch.bfloat16, ga, be, rm, rv, 0.1)
+    var = st["var"][0]
+    m = float(torch.tensor(0.1, dtype=torch.float32))
+    with pytest.raises(AssertionError):           # running variance from the BIASED variance
+        R.assert_fp32(((1 - m) * rv + m * var).float(), st["running_var"], "running var / count")
+    with pytest.raises(AssertionError):           # normalisation with the UNBIASED variance
+        R.assert_fp32((var * M / (M - 1) + EPS32).rsqrt().float(), st["istd"], "istd / (count - 1)")
+
+
+def test_wrong_bilinear_weight_and_last_maximum_are_rejected():
+    x = _gen(80, (1, 8, 16, 16))
+    up = R.bilinear2x(x, torch.bfloat16)
+    with pytest.raises(AssertionError):
+        R.assert_bf16(_as_kernel_bf16(R.bilinear2x(x, torch.bfloat16, wrong=True)[0]), up, "H / 2H weights")
+    a = _gen(81, (1, 8, 8, 8)).bfloat16().double()
+    a[:, 0] = 0.5                                                      # a tie in every window of channel 0
+    g = _gen(82, (1, 8, 4, 4)).bfloat16().double()
+    good, bad = R.maxpool2_route(a, g), R.maxpool2_route(a, g, last=True)
+    assert not torch.equal(good, bad) and torch.equal(good[:, 1:], bad[:, 1:])
+    assert float(good[0, 0, 1::2].abs().max()) == 0 and float(good[0, 0, :, 1::2].abs().max()) == 0
+
+
+@pytest.mark.parametrize("decoupled", [False, True], ids=["adam", "adamw"])
+def test_adam_defects_are_rejected_and_fp32_torch_is_accepted(decoupled):
+    n = 4096 + 7
+    p0, g = _gen(90, (n,)).float(), _gen(91, (n,)).float()
+    m0, v0 = (_gen(92, (n,)) * 0.1).float(), (_gen(93, (n,)) ** 2 * 0.01).float()
+    for step in (2, 1000):
+        ref = R.adam_step(p0, g, m0, v0, step, weight_decay=1e-2, decoupled=decoupled)
+        hp = torch.nn.Parameter(p0.clone())
+        opt = (torch.optim.AdamW if decoupled else torch.optim.Adam)([hp], lr=1e-3, weight_decay=1e-2)
+        opt.state[hp] = {"step": torch.tensor(float(step - 1)), "exp_avg": m0.clone(), "exp_avg_sq": v0.clone()}
+        hp.grad = g.clone()
+        opt.step()
+        host = hp.detach()
+        R.assert_measured(host, ref[0], host, "fp32 torch against itself")
+        assert R.MEASURED["fp32 torch against itself"][0] < 2.0 ** -22          # (so the floor is what binds on the host)
+        if step == 2:
+            late = R.adam_step(p0, g, m0, v0, step, weight_decay=1e-2, decoupled=decoupled, bias_step=step - 1)
+            with pytest.raises(AssertionError):
+                R.assert_measured(late[0][0].float(), ref[0], host, "bias correction of step t-1")
+        other = R.adam_step(p0, g, m0, v0, step, weight_decay=1e-2, decoupled=decoupled, swap_decay=True)
+        with pytest.raises(AssertionError):
+            R.assert_measured(other[0][0].float(), ref[0], host, "the other decay rule")
+
+
+# ---------------------------------------------------------------------- heads, MSE + focal loss, anomaly score
+def test_head_and_loss_references_match_torch():
+    from oracle import unet_oracle as O
+    x, w, b = _gen(100, (2, 64, 5, 7)), _gen(101, (3, 64, 1, 1)) * 0.2, _gen(102, (3,))
+    dout = _gen(103, (2, 3, 5, 7))
+    for sigmoid in (False, True):
+        xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        out = F.conv2d(xr, wr, br)
+        out = torch.sigmoid(out) if sigmoid else out
+        out.backward(dout)
+        assert _close(R.head_fwd(x, F64, w, b, sigmoid)[0], out.detach())
+        bw = R.head_bwd(x, F64, out.detach(), dout, w, sigmoid)
+        assert _close(bw["dx"][0], xr.grad) and _close(bw["dw"][0], wr.grad) and _close(bw["db"][0], br.grad)
+    recon, image = _gen(104, (2, 3, 6, 5)), _gen(105, (2, 3, 6, 5))
+    amap = torch.rand(60, generator=torch.Generator().manual_seed(106), dtype=F64).view(2, 1, 6, 5)
+    mask = (torch.rand(60, generator=torch.Generator().manual_seed(107)) < 0.3).double().view(2, 1, 6, 5)
+    for gamma in (2.0, 1.5):
+        rr, ar = recon.clone().requires_grad_(True), amap.clone().requires_grad_(True)
+        bce = F.binary_cross_entropy(ar, mask, reduction="none")
+        foc = (0.25 * (1 - torch.exp(-bce)) ** gamma * bce).mean()
+        mse = F.mse_loss(rr, image)
+        (foc + mse).backward()
+        ref = R.mse_focal(recon, image, amap, mask, 0.25, gamma)
+        assert _close(ref["mse"][0], mse.detach()) and _close(ref["focal"][0], foc.detach())
+        assert _close(ref["d_recon"][0], rr.grad.reshape(-1)) and _close(ref["d_amap"][0], ar.grad.reshape(-1))
+        d = O.combined_loss(recon, amap, image, mask, focal_gamma=gamma)           # the oracle is the same formula
+        assert _close(ref["focal"][0], d["seg_loss"]) and _close(ref["mse"][0], d["recon_loss"])
+    (sc, _), (im, _) = R.anomaly_score(recon, image)
+    assert _close(sc, O.anomaly_score(recon, image)) and _close(im, O.anomaly_score(recon, image).flatten(1).mean(1))
+    assert _close(R.anomaly_score(recon, image, l1=True)[0][0], (recon - image).abs().mean(1))
+
+
+def test_head_exact_values_pass_and_truncated_or_short_sums_do_not():
+    x, w, b = _gen(110, (2, 64, 24, 24)), (_gen(111, (8, 64, 1, 1)) * 0.2).float(), _gen(112, (8,)).float()
+    z = R.head_fwd(x, torch.bfloat16, w, b, False)
+    R.assert_fp32(z[0].float(), z, "exact logits")
+    out = torch.sigmoid(z[0]).float()
+    dout = _gen(113, (2, 8, 24, 24)).float()
+    bw = R.head_bwd(x, torch.bfloat16, out, dout, w, True)
+    R.assert_bf16(_as_kernel_bf16(bw["dx"][0]), bw["dx"], "exact head dx")
+    R.assert_fp32(bw["dw"][0].float(), bw["dw"], "exact head dW")
+    R.assert_fp32(bw["db"][0].float(), bw["db"], "exact head db")
+    with pytest.raises(AssertionError):
+        R.assert_bf16(R.round_bf16_toward_zero(bw["dx"][0]), bw["dx"], "truncated head dx")
+    bad = z[0].clone()
+    bad[0, 3, 5, 7] -= R.q64(x)[0, 17, 5, 7] * w.double()[3, 17, 0, 0]           # one of the 64 products missing
+    with pytest.raises(AssertionError):
+        R.assert_fp32(bad.float(), z, "logit with a dropped product")
+    # the sigmoid is measured: fp32 torch passes against itself, a logit-level defect does not
+    s = R.head_fwd(x, torch.bfloat16, w, b, True)
+    host = torch.sigmoid(F.conv2d(R.q64(x).float(), w, b))
+    R.assert_measured(host, s, host, "host sigmoid head", extra=R.SUM_EPS)
+    with pytest.raises(AssertionError):
+        R.assert_measured(torch.sigmoid(bad).float(), s, host, "sigmoid of the defective logit", extra=R.SUM_EPS)
+
+
+def test_focal_edge_probabilities_are_finite_and_host_measured():
+    from oracle import unet_oracle as O
+    n = 4096
+    amap = torch.rand(n, generator=torch.Generator().manual_seed(120))
+    amap[:6] = torch.tensor([0.0, 1.0, 1e-30, 1 - 1e-7, 0.5, 1e-45])
+    mask = (torch.rand(n, generator=torch.Generator().manual_seed(121)) < 0.1).float()
+    recon, image = _gen(122, (n,)).float(), _gen(123, (n,)).float()
+    ref = R.mse_focal(recon, image, amap, mask)
+    assert all(bool(torch.isfinite(v[0]).all()) and bool(torch.isfinite(v[1]).all()) for v in ref.values())
+    ar = amap.clone().requires_grad_(True)
+    O.focal_loss(ar, mask).backward()
+    R.assert_measured(ar.grad, ref["d_amap"], ar.grad, "host focal gradient")
+    with pytest.raises(AssertionError):          # the gradient of gamma = 2 through the general pow path with gamma - 1 = 2
+        R.assert_measured(R.mse_focal(recon, image, amap, mask, gamma=3.0)["d_amap"][0].float(), ref["d_amap"], ar.grad, "wrong gamma")
+
+
+# ---------------------------------------------------------------------- fused head, SSIM
+def test_fused_head_and_ssim_references_match_torch():
+    from oracle import unet_oracle as O
+    # fused head in float64 on fp32-exact operands (scale 1, shift 0, bf16-grid y): relu -> 1x1 conv -> sigmoid
+    y = _gen(130, (2, 64, 5, 7)).bfloat16().double()
+    w, b, dout = _gen(131, (3, 64, 1, 1)) * 0.2, _gen(132, (3,)), _gen(133, (2, 3, 5, 7))
+    one, zero = torch.ones(64), torch.zeros(64)
+    mean = _gen(134, (64,)).float()
+    for sigmoid in (False, True):
+        yr, wr, br = y.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        out = F.conv2d(F.relu(yr), wr, br)
+        out = torch.sigmoid(out) if sigmoid else out
+        out.backward(dout)
+        assert _close(R.head_bnrelu_fwd(y, F64, one, zero, w, b, sigmoid)[0], out.detach())
+        bw = R.head_bnrelu_bwd(y, F64, one, zero, mean, out.detach(), dout, w, sigmoid)
+        assert _close(bw["dz"][0], yr.grad) and _close(bw["dw"][0], wr.grad) and _close(bw["db"][0], br.grad)
+        assert torch.allclose(bw["sum"][0], yr.grad.sum((0, 2, 3)), rtol=1e-6, atol=1e-6)          # (over the fp32-STORED dz)
+        assert torch.allclose(bw["sum_c"][0], (yr.grad * (y - mean.double()[None, :, None, None])).sum((0, 2, 3)), rtol=1e-6, atol=1e-5)
+    a = torch.rand(2, 3, 20, 27, generator=torch.Generator().manual_seed(135), dtype=F64)
+    c = _gen(136, (2, 3, 20, 27))
+    for per_image in (False, True):
+        ar, cr = a.clone().requires_grad_(True), c.clone().requires_grad_(True)
+        v = O.ssim_loss(ar, cr, 11, size_average=not per_image)
+        v.sum().backward()
+        ref = R.ssim(a, c, 11, per_image)
+        assert _close(ref["loss"][0], v.detach()) and _close(ref["d1"][0], ar.grad) and _close(ref["d2"][0], cr.grad)
+        assert bool((ref["d1"][1] >= ref["d1"][0].abs() - 1e-15).all())
+
+
+def test_ssim_host_passes_and_a_wrong_border_is_rejected():
+    from oracle import unet_oracle as O
+    a = torch.rand(1, 3, 40, 37, generator=torch.Generator().manual_seed(140))
+    c = _gen(141, (1, 3, 40, 37)).float()
+    ar, cr = a.clone().requires_grad_(True), c.clone().requires_grad_(True)
+    v = O.ssim_loss(ar, cr)
+    v.backward()
+    ref = R.ssim(a, c)
+    R.assert_measured(v.detach(), ref["loss"], v.detach(), "host ssim loss", extra=R.SUM_EPS)
+    R.assert_measured(ar.grad, ref["d1"], ar.grad, "host ssim d1")
+    # a blur that leaves out the last column of a frame that is not a multiple of the 32-pixel tile: replicate it by
+    # taking the gradient of the frame cropped by one column
+    bad = R.ssim(a[..., :36], c[..., :36])["d1"][0]
+    with pytest.raises(AssertionError):
+        R.assert_measured(bad.float(), (ref["d1"][0][..., :36], ref["d1"][1][..., :36]), ar.grad[..., :36], "cropped frame")
+    fz = R.head_bnrelu_bwd(_gen(142, (1, 64, 4, 4)), torch.bfloat16, torch.ones(64), torch.zeros(64), torch.zeros(64),
+                           torch.full((1, 2, 4, 4), 0.5), _gen(143, (1, 2, 4, 4)).float(), (_gen(144, (2, 64, 1, 1))).float(), True)
+    R.assert_bf16(fz["dz_stored"].bfloat16(), fz["dz"], "exact fused dz")
+    with pytest.raises(AssertionError):
+        R.assert_bf16(R.round_bf16_toward_zero(fz["dz"][0]), fz["dz"], "truncated fused dz")

@@ -1,6 +1,9 @@
 """GPU parity tests, kernel level: each C-ABI entry point of libunet_hip.so against the CPU oracle /
 plain fp32 torch on the same seeded inputs.  fp32 kernels are held to tight bounds (the parity mode);
-bf16 kernels are compared on bf16-rounded inputs with a bound set by bf16 output rounding (2^-8)."""
+bf16 kernels are compared on bf16-rounded inputs with a bound set by bf16 output rounding (2^-8).
+The convolutions here, and the BatchNorm, pooling, bilinear, head, loss, anomaly-score and Adam kernels in
+test_gpu_streaming.py, are also held
+element by element to the float64 references of _ref64.py."""
 import ctypes as C
 
 import pytest

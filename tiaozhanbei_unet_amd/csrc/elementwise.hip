@@ -491,12 +491,19 @@ __global__ __launch_bounds__(256) void bn_relu_pool_bwd_kernel(const T* __restri
 }
 
 // ------------------------------------------------------------------------------- bilinear x2 (align_corners)
-__device__ inline void bil_axis(int o, int n_in, int n_out, int& i0, int& i1, float& f) {
-  const float src = (n_out > 1) ? o * ((float)(n_in - 1) / (float)(n_out - 1)) : 0.f;
-  i0 = (int)floorf(src);
+// source coordinate o * (n_in - 1) / (n_out - 1) in integers: i0 is its floor, f = rem / (n_out - 1) the weight of i1 and
+// g = (n_out - 1 - rem) / (n_out - 1) the weight of i0, each rounded once (1.f - f would carry f's ABSOLUTE rounding error
+// into a weight that may be 1000 times smaller).  (Formed in fp32, o * scale carries an absolute error of an ulp of the COORDINATE, 6e-5 at row 1000:
+// the weight of a 704-row frame was off by up to 2000 x what fp32 arithmetic on the pixel values costs.)
+__device__ inline void bil_axis(int o, int n_in, int n_out, int& i0, int& i1, float& f, float& g) {
+  const unsigned den = n_out > 1 ? n_out - 1 : 1;
+  const unsigned num = (unsigned)o * (unsigned)(n_in - 1);      // < 2^31: the launchers take sides up to 32768
+  i0 = (int)(num / den);
   if (i0 > n_in - 1) i0 = n_in - 1;
   i1 = i0 + 1 < n_in ? i0 + 1 : n_in - 1;
-  f = src - (float)i0;
+  const unsigned rem = num - (unsigned)i0 * den;
+  f = (float)rem / (float)den;
+  g = (float)(den - rem) / (float)den;
 }
 
 template <typename T>
@@ -511,9 +518,9 @@ __global__ void bilinear2x_fwd_kernel(const T* __restrict__ x, T* __restrict__ y
     const int ox = (int)(t % OW);  t /= OW;
     const int oy = (int)(t % OH);
     const long long n = t / OH;
-    int y0, y1, x0, x1; float fy, fx;
-    bil_axis(oy, H, OH, y0, y1, fy);
-    bil_axis(ox, W, OW, x0, x1, fx);
+    int y0, y1, x0, x1; float fy, fx, gy, gx;
+    bil_axis(oy, H, OH, y0, y1, fy, gy);
+    bil_axis(ox, W, OW, x0, x1, fx, gx);
     float a[PIECE], b[PIECE], c[PIECE], d[PIECE];
     const T* p = x + n * H * (long long)W * C + g * PIECE;
     Vec<T>::load(p + ((long long)y0 * W + x0) * C, a);
@@ -522,8 +529,8 @@ __global__ void bilinear2x_fwd_kernel(const T* __restrict__ x, T* __restrict__ y
     Vec<T>::load(p + ((long long)y1 * W + x1) * C, d);
 #pragma unroll
     for (int j = 0; j < PIECE; ++j) {
-      const float top = a[j] * (1.f - fx) + b[j] * fx, bot = c[j] * (1.f - fx) + d[j] * fx;
-      a[j] = top * (1.f - fy) + bot * fy;
+      const float top = a[j] * gx + b[j] * fx, bot = c[j] * gx + d[j] * fx;
+      a[j] = top * gy + bot * fy;
     }
     Vec<T>::store(y + i * PIECE, a);
   }
@@ -549,17 +556,17 @@ __global__ void bilinear2x_bwd_kernel(const T* __restrict__ dy, T* __restrict__ 
     const int oy_lo = max(0, 2 * iy - 2), oy_hi = min(OH - 1, 2 * iy + 3);
     const int ox_lo = max(0, 2 * ix - 2), ox_hi = min(OW - 1, 2 * ix + 3);
     for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-      int y0, y1; float fy;
-      bil_axis(oy, H, OH, y0, y1, fy);
+      int y0, y1; float fy, gy;
+      bil_axis(oy, H, OH, y0, y1, fy, gy);
       float wy = 0.f;
-      if (y0 == iy) wy += 1.f - fy;
+      if (y0 == iy) wy += gy;
       if (y1 == iy) wy += fy;
       if (wy == 0.f) continue;
       for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-        int x0, x1; float fx;
-        bil_axis(ox, W, OW, x0, x1, fx);
+        int x0, x1; float fx, gx;
+        bil_axis(ox, W, OW, x0, x1, fx, gx);
         float wx = 0.f;
-        if (x0 == ix) wx += 1.f - fx;
+        if (x0 == ix) wx += gx;
         if (x1 == ix) wx += fx;
         if (wx == 0.f) continue;
         float v[PIECE];
@@ -764,14 +771,16 @@ extern "C" int32_t unet_bn_relu_pool_bwd(int32_t dtype, const void* y, const voi
 extern "C" int32_t unet_upsample_bilinear2x_fwd(int32_t dtype, const void* x, int32_t n, int32_t h, int32_t w,
                                                 int32_t c, void* y, void* stream) {
   UNET_REQUIRE(x && y, UNET_ERR_BAD_ARG, "unet_upsample_bilinear2x_fwd: null pointer");
-  UNET_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0, UNET_ERR_UNSUPPORTED, "unet_upsample_bilinear2x_fwd: dims");
+  UNET_REQUIRE(n > 0 && h > 0 && w > 0 && h <= 32768 && w <= 32768 && c > 0 && c % 8 == 0, UNET_ERR_UNSUPPORTED,
+               "unet_upsample_bilinear2x_fwd: dims");
   EW_DISPATCH("bilinear2x_fwd_kernel", bilinear2x_fwd_kernel, (long long)n * 4 * h * w * c, (const T*)x, (T*)y, n, h, w, c);
 }
 
 extern "C" int32_t unet_upsample_bilinear2x_bwd(int32_t dtype, const void* dy, int32_t n, int32_t h, int32_t w,
                                                 int32_t c, void* dx, void* stream) {
   UNET_REQUIRE(dy && dx, UNET_ERR_BAD_ARG, "unet_upsample_bilinear2x_bwd: null pointer");
-  UNET_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0, UNET_ERR_UNSUPPORTED, "unet_upsample_bilinear2x_bwd: dims");
+  UNET_REQUIRE(n > 0 && h > 0 && w > 0 && h <= 32768 && w <= 32768 && c > 0 && c % 8 == 0, UNET_ERR_UNSUPPORTED,
+               "unet_upsample_bilinear2x_bwd: dims");
   EW_DISPATCH("bilinear2x_bwd_kernel", bilinear2x_bwd_kernel, (long long)n * h * w * c, (const T*)dy, (T*)dx, n, h, w, c);
 }
 
