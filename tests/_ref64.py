@@ -435,6 +435,210 @@ def ssim(img1, img2, window=11, per_image=False):
     return {"loss": (loss.detach(), sl.detach()), "d1": (d1, s1), "d2": (d2, s2)}
 
 
+# ------------------------------------------------------------------ segmentation loss (csrc/segloss.hip)
+# The largest sizes at which the GPU tests (test_gpu_segloss.py) rely on the comparator to see each class of defect;
+# test_cpu_ref64.py plants the defect at exactly these sizes, the GPU tests assert they stay within them.
+#   one block's partial (4096 pixels) missing: moves a per-image sum by 4096 / hw and the CE denominator by 4096 / (N hw),
+#     both far above 2^-18 at every size in use -- planted at the largest image and the largest batch;
+#   one pixel missing at the tail: moves a per-image sum by about 1 / hw, which reaches the 2^-18 bound near 512 x 512 --
+#     only the small pixel-count sweep is relied on for it.
+MAX_SEG_IMAGE_HW = 1408 * 1024
+MAX_SEG_PIXELS = 48 * 512 * 512
+MAX_SEG_TAIL_HW = 12289
+MAX_SEG_TAIL_HW_C1 = 257      # one class: the gradient is identically 0, only the (nearly flat) Dice value is left to see it
+SEG_CE_ABS = 2.0 ** -24       # see seg_loss: what an fp32 sum / probability next to 1 cannot resolve
+SEG_BLOCK = 4096              # pixels per block of seg_reduce_kernel below its cap on blocks per image
+
+SEG_DEFECTS = ("drop_block", "drop_tail", "b_sign", "a_class", "no_focal_dterm", "ce_clamp", "sump_skips_ignored",
+               "focal_over_valid")
+
+
+def _f32(x):
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def _seg_pixels(z, t, C, ignore, cw, alpha, gamma, dtype, is_prob=False, defect=None):
+    """per-pixel quantities of ONE image ([C, P] logits, [P] labels) evaluated in `dtype`: float64 is the reference,
+    float32 the host evaluation of the same formulas that assert_measured holds the device functions against"""
+    z = z.to(dtype)
+    P = z.shape[1]
+    valid = (t != ignore) & (t >= 0) & (t < C)
+    tc = torch.where(valid, t, torch.zeros_like(t))
+    h = torch.zeros((C, P), dtype=torch.bool).scatter_(0, tc[None], valid[None])
+    if is_prob:
+        return {"p": z, "h": h, "valid": valid, "tc": tc}
+    d = z - z.max(0).values                              # <= 0, exactly 0 at the maximum
+    e = d.exp()
+    s = e.sum(0)
+    p = e / s
+    dt = d.gather(0, tc[None])[0]
+    nll = torch.where(valid, s.log() - dt, torch.zeros_like(s))
+    if defect == "ce_clamp":                             # -log(max(pt, 1e-38)) of a normalised probability
+        nll = nll.clamp_max(87.498)
+    pt = torch.where(valid, p.gather(0, tc[None])[0], torch.ones_like(s))
+    w = torch.where(valid, (cw.to(dtype)[tc] if cw is not None else torch.ones_like(s)), torch.zeros_like(s))
+    om = 1 - pt
+    foc = torch.where(valid, alpha * om ** gamma * nll, torch.zeros_like(s))
+    return {"p": p, "h": h, "valid": valid, "tc": tc, "d": d, "nll": nll, "pt": pt, "w": w, "om": om, "foc": foc,
+            "s_nll": torch.where(valid, s.log() + dt.abs(), torch.zeros_like(s))}
+
+
+def seg_loss(logits, target, class_weights=None, ignore_index=-1, ce_w=1.0, dice_w=1.0, focal_w=0.0, alpha=1.0,
+             gamma=2.0, is_prob=False, grad=True, defect=None, images=None):
+    """unet_seg_loss in float64 from the fp32 logits [N, C, hw] and int64 labels [N, hw] the kernel reads.
+
+    CONTRACT (wider than the reference's F.cross_entropy / dice_loss / focal_loss):
+      * a label equal to ignore_index, negative or >= C is not valid: it adds nothing to CE, focal, the Dice intersection I
+        and the one-hot sum T; its softmax probability still enters the Dice sum P = sum p;
+      * CE = sum w nll / sum w over valid pixels, 0 with a zero CE gradient when sum w = 0 (torch: NaN);
+      * focal = sum alpha (1 - pt)^gamma nll / (N hw): a mean over ALL pixels;
+      * Dice: dice[n, c] = (2 I + s) / (P + T + s), s = 1e-8, loss = 1 - mean over N C;
+      * total = the terms whose weight is > 0, weighted;  is_prob: Dice of the given map, gradient w.r.t. the map.
+    Gradient, closed form:  d = p_c (g_c - sum_j g_j p_j) + k (p_c - h_c),  g_c = h_c A_c + B_c,
+      A = -dice_w 2 / (N C U),  B = dice_w (2 I + s) / (N C U^2),  U = P + T + s,
+      k = ce_w w / sum w + focal_w alpha ((1 - pt)^gamma + gamma (1 - pt)^(gamma - 1) pt nll) / (N hw).
+
+    BOUNDS.  Every output is (value, S) plus an absolute allowance; assert_measured(..., absolute=) asks for
+        |out - ref| <= S (max(4 host, 2^-22) + extra) + absolute,
+    host = the worst |fp32 host evaluation - ref| / S of the same formulas (exp, log, pow and the softmax division are
+    library functions: the module's measured rule; the host evaluation is never the kernel).
+    Per pixel:
+      p_c    = exp(d_c) / sum exp(d), d = z - max z.  The fp32 subtraction rounds d by 2^-24 |d|, which exp turns into a
+               RELATIVE error 2^-24 |d| = 2^-22 |d| / 4 of p_c:  S(p_c) = p_c (1 + |d_c| / 4).
+      nll    = log(sum) - d_t:  S = log(sum) + |d_t| (both roundings are relative to their own term), plus the absolute
+               SEG_CE_ABS = 2^-24: the sum is an fp32 number in [1, C] whose largest term is exactly 1, half an ulp of it
+               next to 1 is 2^-24 and d log(sum) = d sum / sum, so an nll below that cannot be resolved (the same
+               half ulp of pt at 1 in the -log(pt) form).  Derived, not measured.
+      1 - pt   is formed from 1 and pt: S carries (1 + pt) in its place (mse_focal's convention), so
+      focal_i  S = alpha (1 + pt)^gamma S(nll), absolute alpha (1 + pt)^gamma 2^-24.
+    Sums of like-signed fp32 terms (I, P, CE numerator and denominator, focal) add SUM_EPS S; T is a count, exact.
+    First-order propagation (sums are fp64 after the per-block fp32 partials, every store is one fp32 rounding):
+      r_I, r_P = SUM_EPS + lib: relative error of I and P, lib = max(4 x measured host error of the sum, 2^-22)
+      dice[n,c]  d = 2 r_I I / U + dice r_P P / U                    -> dice loss: S = 1 + mean(2 I / U + dice P / U)
+      A          r_A = r_P P / U + 2^-24                              (d(1 / U) = dU / U^2, one store)
+      B          r_B = r_I 2 I / (2 I + s) + 2 r_P P / U + 2^-24      (d(1 / U^2) = 2 dU / U^3)
+      ce         S = sum w S(nll) / sum w, absolute 2^-24, extra 2 SUM_EPS + 2^-24   (numerator, denominator, store)
+      ce_w / sum w   r = SUM_EPS + 2^-24;   focal_w / (N hw): one rounding, inside the 2^-22 floor
+      focal      S = sum S(focal_i) / (N hw), absolute mean of the per-pixel one, extra SUM_EPS + 2^-24
+      total      the weighted sum of the three (S, absolute and extra alike)
+      dlogits    S = S(p_c) (G_c + sum_j G_j S(p_j)) + K (S(p_c) + h_c),  G_c = h_c |A_c| + |B_c|,
+                 K = ce_w w / sum w + focal_w alpha ((1 + pt)^gamma + gamma (1 + pt)^(gamma - 1) S(pt) S(nll)) / (N hw);
+                 absolute = p_c (D_c + sum_j D_j p_j) + (p_c + h_c) (r ce_w w / sum w
+                            + focal_w alpha gamma (1 - pt)^(gamma - 1) pt 2^-24 / (N hw)),  D_c = h_c r_A |A_c| + r_B |B_c|
+      is_prob    d = h_c A_c + B_c:  bound h_c r_A |A_c| + r_B |B_c| + 2^-24 |d| with lib = 0 (no library function),
+                 returned as S = bound / SUM_EPS for assert_fp32.
+    -> {'loss': (v[4], S[4]), 'loss_abs': [4], 'loss_extra': [4], 'loss_host': [4], 'dlogits': (v, S), 'dlogits_abs',
+        'dlogits_host', 'A', 'B', 'ce_scale'}; images: the image indices the gradient is returned for (default all).
+    defect: one of SEG_DEFECTS, the planted defects of test_cpu_ref64.py."""
+    z32 = logits.detach().to(torch.float32).cpu()
+    tg = target.detach().to(torch.int64).cpu()
+    N, C, hw = z32.shape
+    cw = None if class_weights is None else class_weights.detach().to(torch.float32).cpu()
+    ce_w, dice_w, focal_w, alpha, gamma = (_f32(v) for v in (ce_w, dice_w, focal_w, alpha, gamma))
+    f64, f32 = torch.float64, torch.float32
+    sm = 1e-8
+    I, Pp, T, Ih, Ph = (torch.zeros(N, C, dtype=f64) for _ in range(5))
+    num = den = fsum = numh = fsumh = s_num = s_foc = a_num = a_foc = 0.0
+    for n in range(N):
+        zn, tn = z32[n], tg[n]
+        if defect == "drop_block" and n == 0:            # the second 4096-pixel block (the last one if there is no other)
+            keep = torch.ones(hw, dtype=torch.bool)
+            b0 = min(SEG_BLOCK, max(hw - SEG_BLOCK, 0))
+            keep[b0:b0 + SEG_BLOCK] = False
+            zn, tn = zn[:, keep], tn[keep]
+        if defect == "drop_tail" and n == 0:
+            zn, tn = zn[:, :-1], tn[:-1]
+        for dt_ in (f64, f32):
+            q = _seg_pixels(zn, tn, C, ignore_index, cw, alpha, gamma, dt_, is_prob, defect)
+            p, h = q["p"].to(f64), q["h"]
+            pin = p * q["valid"] if defect == "sump_skips_ignored" else p
+            if dt_ == f64:
+                I[n], Pp[n], T[n] = (p * h).sum(1), pin.sum(1), h.sum(1).to(f64)
+            else:
+                Ih[n], Ph[n] = (p * h).sum(1), pin.sum(1)
+            if is_prob:
+                continue
+            if dt_ == f64:
+                num, den, fsum = num + float((q["w"] * q["nll"]).sum()), den + float(q["w"].sum()), fsum + float(q["foc"].sum())
+                op = (1 + q["pt"]) ** gamma * q["valid"]
+                s_num, a_num = s_num + float((q["w"] * q["s_nll"]).sum()), a_num + float(q["w"].sum()) * SEG_CE_ABS
+                s_foc, a_foc = s_foc + float((alpha * op * q["s_nll"]).sum()), a_foc + float((alpha * op).sum()) * SEG_CE_ABS
+            else:
+                numh, fsumh = numh + float((q["w"].to(f64) * q["nll"].to(f64)).sum()), fsumh + float(q["foc"].to(f64).sum())
+    npix = float(N) * hw
+    fden = float(den) if defect == "focal_over_valid" else npix          # (unit weights: den counts the valid pixels)
+    U = Pp + T + sm
+    dice_nc = (2 * I + sm) / U
+    lib = lambda a, b: max(4 * float(((a - b).abs() / b.clamp_min(1e-300)).max()), MEASURED_FLOOR)      # noqa: E731
+    r_I, r_P = (0.0, 0.0) if is_prob else (lib(Ih, I), lib(Ph, Pp))
+    r_I, r_P = r_I + SUM_EPS, r_P + SUM_EPS
+    dice = 1 - dice_nc.mean()
+    s_dice = 1 + (2 * I / U + dice_nc * Pp / U).mean()
+    dice_h = 1 - ((2 * Ih + sm) / (Ph + T + sm)).mean()
+    ce, ce_h = (num / den, numh / den) if den > 0 else (0.0, 0.0)
+    s_ce, a_ce = (s_num / den, a_num / den) if den > 0 else (0.0, 0.0)
+    focal, focal_h, s_focal, a_focal = fsum / fden, fsumh / fden, s_foc / fden, a_foc / fden
+    wts = [w if w > 0 else 0.0 for w in (ce_w, dice_w, focal_w)]
+    mix = lambda a, b, c: wts[0] * a + wts[1] * b + wts[2] * c      # noqa: E731
+    e_ce, e_dice, e_focal = 2 * SUM_EPS + 2.0 ** -24, SUM_EPS + 2.0 ** -24, SUM_EPS + 2.0 ** -24
+    t64 = lambda *v: torch.tensor([float(x) for x in v], dtype=f64)      # noqa: E731
+    out = {"loss": (t64(mix(ce, dice, focal), ce, dice, focal), t64(mix(s_ce, s_dice, s_focal), s_ce, s_dice, s_focal)),
+           "loss_abs": t64(mix(a_ce, 0.0, a_focal), a_ce, 0.0, a_focal),
+           "loss_extra": t64(max(e_ce, e_dice, e_focal) + 2.0 ** -24, e_ce, e_dice, e_focal),
+           "loss_host": t64(mix(ce_h, dice_h, focal_h), ce_h, dice_h, focal_h)}
+    if is_prob:                                          # loss[1], loss[3] are outside the contract for a probability map
+        out["loss"] = (out["loss"][0][[0, 2]], out["loss"][1][[0, 2]])
+        for k in ("loss_abs", "loss_extra", "loss_host"):
+            out[k] = out[k][[0, 2]]
+    inv_nc = 1.0 / (N * C)
+    A = -wts[1] * inv_nc * 2.0 / U
+    B = wts[1] * inv_nc * (2 * I + sm) / (U * U)
+    if defect == "b_sign":
+        B = -B
+    if defect == "a_class":
+        A = A.roll(1, 1)
+    r_A = r_P * Pp / U + 2.0 ** -24
+    r_B = r_I * 2 * I / (2 * I + sm) + 2 * r_P * Pp / U + 2.0 ** -24
+    ce_s = wts[0] / den if den > 0 else 0.0
+    fo_s = wts[2] / fden
+    r_den = SUM_EPS + 2.0 ** -24
+    out.update(A=A, B=B, ce_scale=ce_s)
+    if not grad:
+        return out
+    images = list(range(N)) if images is None else list(images)
+    val, S, Ab, host = (torch.empty((len(images), C, hw), dtype=f64) for _ in range(4))
+    for i, n in enumerate(images):
+        An, Bn = A[n][:, None], B[n][:, None]
+        if is_prob:
+            h = _seg_pixels(z32[n], tg[n], C, ignore_index, None, alpha, gamma, f64, True)["h"].to(f64)
+            val[i] = h * An + Bn
+            S[i] = (h * An.abs() * r_A[n][:, None] + Bn.abs() * r_B[n][:, None] + 2.0 ** -24 * val[i].abs()) / SUM_EPS
+            Ab[i], host[i] = 0.0, val[i]
+            continue
+        for dt_ in (f64, f32):
+            q = _seg_pixels(z32[n], tg[n], C, ignore_index, cw, alpha, gamma, dt_, False, defect)
+            p, h, pt, nll, om, w = q["p"], q["h"].to(dt_), q["pt"], q["nll"], q["om"], q["w"]
+            a_, b_ = An.to(dt_), Bn.to(dt_)
+            g = h * a_ + b_
+            dterm = 0.0 if defect == "no_focal_dterm" else gamma * om ** (gamma - 1) * pt * nll
+            k = torch.tensor(ce_s, dtype=dt_) * w + torch.tensor(fo_s * alpha, dtype=dt_) * (om ** gamma + dterm) * q["valid"]
+            dv = p * (g - (g * p).sum(0)) + k * (p - h)
+            if dt_ == f32:
+                host[i] = dv.to(f64)
+                continue
+            val[i] = dv
+            sp = p * (1 + q["d"].abs() / 4)
+            G = h * An.abs() + Bn.abs()
+            spt = torch.where(q["valid"], sp.gather(0, q["tc"][None])[0], torch.ones_like(pt))
+            K = ce_s * w + fo_s * alpha * ((1 + pt) ** gamma + gamma * (1 + pt) ** (gamma - 1) * spt * q["s_nll"]) * q["valid"]
+            S[i] = sp * (G + (G * sp).sum(0)) + K * (sp + h)
+            D = h * (An.abs() * r_A[n][:, None]) + Bn.abs() * r_B[n][:, None]
+            Ab[i] = p * (D + (D * p).sum(0)) + (p + h) * (r_den * ce_s * w + fo_s * alpha * gamma * om ** (gamma - 1) * pt
+                                                          * SEG_CE_ABS * q["valid"])
+    out.update(dlogits=(val, S), dlogits_abs=Ab, dlogits_host=host)
+    return out
+
+
 # ------------------------------------------------------------------ comparator
 def _where(idx, shape):
     out = []
@@ -485,13 +689,14 @@ MEASURED = {}                 # what -> (host err / S, kernel err / S, allowed /
 MEASURED_FLOOR = 2.0 ** -22   # never ask for less than 4 fp32 roundings of S
 
 
-def assert_measured(out, ref_s, host, what, extra=0.0, mask=None):
+def assert_measured(out, ref_s, host, what, extra=0.0, mask=None, absolute=0.0):
     """fp32 output of a kernel whose error is a library function's (sqrt, log, pow, a division), not a summation's: the
     oracle's fp32 CPU evaluation `host` of the same formula on the same inputs is measured against the float64 value,
     worst |err| / S, and the kernel gets 4 x that, never less than 2^-22 S (device functions are specified to 1-2 ulp
     where the host libm is within 1; fma contraction).  extra: added to the allowed ratio (SUM_EPS for reduced scalars).
     Results in fp32's denormal range are held to 2^-148 absolutely and left out of the measured ratio (a store there is
-    not a relative error).  Returns the worst err / bound."""
+    not a relative error).  absolute: a DERIVED absolute allowance per element (seg_loss), added to the bound and taken
+    off the host's error before it is measured.  Returns the worst err / bound."""
     ref, S = ref_s
     S = S.to(torch.float64)
     tiny = 2.0 ** -148                 # two stores in fp32's denormal range (half of 2^-149 each, the first carried along)
@@ -499,9 +704,33 @@ def assert_measured(out, ref_s, host, what, extra=0.0, mask=None):
     if mask is not None:
         normal = normal & mask
     den = torch.where(S > 0, S, torch.full_like(S, 1e-300))
-    hr = torch.where(normal, (host.detach().to(torch.float64).cpu() - ref).abs() / den, torch.zeros_like(den))
+    hr = torch.where(normal, ((host.detach().to(torch.float64).cpu() - ref).abs() - absolute).clamp_min(0) / den, torch.zeros_like(den))
     host_ratio = float(hr.max())
     allow = max(4 * host_ratio, MEASURED_FLOOR) + extra
     kr = torch.where(normal, (out.detach().to(torch.float64).cpu() - ref).abs() / den, torch.zeros_like(den))
     MEASURED[what] = (host_ratio, float(kr.max()), allow)
-    return _compare("fp32", out, ref, (S * allow + tiny) / SUM_EPS, what, mask)
+    return _compare("fp32", out, ref, (S * allow + tiny + absolute) / SUM_EPS, what, mask)
+
+
+SEG_OUTPUTS = ("total", "ce", "dice", "focal")
+
+
+def assert_seg(loss, dlogits, ref, what):
+    """unet_seg_loss outputs against seg_loss(): the loss values one by one (each has its own S, absolute and extra) and
+    every gradient element.  dlogits None: values only.  -> {output name: worst err / bound}"""
+    names = SEG_OUTPUTS if ref["loss"][0].numel() == 4 else ("total", "dice")
+    loss = loss.detach().to(torch.float64).cpu().reshape(-1)
+    if len(names) == 2:
+        loss = loss[[0, 2]]
+    worst = {}
+    for i, k in enumerate(names):
+        worst[k] = assert_measured(loss[i:i + 1], (ref["loss"][0][i:i + 1], ref["loss"][1][i:i + 1]), ref["loss_host"][i:i + 1],
+                                   f"{what}: {k} loss", extra=float(ref["loss_extra"][i]), absolute=ref["loss_abs"][i:i + 1])
+    if dlogits is not None:
+        d = dlogits.detach().to(torch.float64).cpu().reshape(ref["dlogits"][0].shape)
+        if len(names) == 2:
+            worst["dlogits"] = assert_fp32(d, ref["dlogits"], f"{what}: d dice / d map")
+        else:
+            worst["dlogits"] = assert_measured(d, ref["dlogits"], ref["dlogits_host"], f"{what}: dlogits",
+                                               absolute=ref["dlogits_abs"])
+    return worst

@@ -2,7 +2,7 @@
 plain fp32 torch on the same seeded inputs.  fp32 kernels are held to tight bounds (the parity mode);
 bf16 kernels are compared on bf16-rounded inputs with a bound set by bf16 output rounding (2^-8).
 The convolutions here, and the BatchNorm, pooling, bilinear, head, loss, anomaly-score and Adam kernels in
-test_gpu_streaming.py, are also held
+test_gpu_streaming.py and the segmentation loss in test_gpu_segloss.py, are also held
 element by element to the float64 references of _ref64.py."""
 import ctypes as C
 

@@ -16,6 +16,16 @@
 //   seg_confusion_kernel first-maximum argmax (torch.argmax tie rule), optional label map, confusion matrix counted
 //                        with integer atomics (exact, order-independent)
 // Everything is deterministic: fixed pixel -> block mapping, ordered reductions, integer atomics only.
+//
+// Contract of unet_seg_loss (wider than the reference's, pinned by tests/test_gpu_segloss.py):
+//   * a target equal to ignore_index, negative or >= C contributes nothing to CE, focal, the Dice intersection and the
+//     one-hot sums; its softmax probability still enters the Dice sum p (the reference sums softmax(pred) over all pixels)
+//   * CE = sum w nll / sum w over the valid pixels; with no valid pixel (or zero total weight) CE is 0 with a zero CE
+//     gradient, where torch's F.cross_entropy gives NaN
+//   * focal is a mean over ALL N * hw pixels (ignored ones count as 0); Dice has smooth = 1e-8 per (image, class),
+//     the loss is 1 - mean over N * C
+//   * the per-pixel cross entropy is log(sum exp(z - max)) - (z_t - max): it follows the exact value for any finite gap
+//   * input_is_prob: Dice of the given map, gradient with respect to the map; loss[1] and loss[3] are not defined
 #include <stdlib.h>
 
 #include "common.h"
@@ -33,16 +43,20 @@ struct SegParams {
   int bpi;                               // blocks per image
 };
 
-__device__ __forceinline__ void softmax_c(const float (&z)[MAXC], int C, float (&p)[MAXC]) {
+// p = softmax(z); z is left holding z - max(z); returns log(sum exp(z - max)), so that the cross entropy of class t is
+// lse - z[t]: exact in the gap for any finite logits, where -log(p[t]) stops at the smallest fp32 probability (a gap
+// of about 87.3) and resolves nothing below half an ulp of p[t] next to 1.
+__device__ __forceinline__ float softmax_c(float (&z)[MAXC], int C, float (&p)[MAXC]) {
   float m = z[0];
 #pragma unroll
   for (int c = 1; c < MAXC; ++c) if (c < C) m = fmaxf(m, z[c]);
   float s = 0.f;
 #pragma unroll
-  for (int c = 0; c < MAXC; ++c) { p[c] = c < C ? expf(z[c] - m) : 0.f; s += p[c]; }
+  for (int c = 0; c < MAXC; ++c) { z[c] -= m; p[c] = c < C ? expf(z[c]) : 0.f; s += p[c]; }
   const float inv = 1.f / s;
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) p[c] *= inv;
+  return logf(s);
 }
 
 __global__ __launch_bounds__(SEG_THREADS) void seg_reduce_kernel(const SegParams P, float* __restrict__ part) {
@@ -57,25 +71,26 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_reduce_kernel(const SegParams
     float z[MAXC], p[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) z[c] = c < P.C ? P.logits[((long long)n * P.C + c) * P.hw + q] : 0.f;
+    float lse = 0.f;
     if (P.is_prob) {
 #pragma unroll
       for (int c = 0; c < MAXC; ++c) p[c] = z[c];
     } else {
-      softmax_c(z, P.C, p);
+      lse = softmax_c(z, P.C, p);
     }
     const long long t = P.target[(long long)n * P.hw + q];
     const bool valid = t != P.ignore && t >= 0 && t < P.C;
-    float pt = 1.f;
+    float pt = 1.f, zt = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
       const bool hit = valid && t == c;
       acc[c] += hit ? p[c] : 0.f;                // intersection
       acc[MAXC + c] += p[c];                     // sum p
       acc[2 * MAXC + c] += hit ? 1.f : 0.f;      // sum one-hot
-      if (hit) pt = p[c];
+      if (hit) { pt = p[c]; zt = z[c]; }
     }
     if (valid) {
-      const float ce = -logf(fmaxf(pt, 1e-38f));
+      const float ce = P.is_prob ? -logf(fmaxf(pt, 1e-38f)) : lse - zt;     // (a probability map: Dice only, unused)
       float w = 1.f;
       if (P.cw) w = P.cw[t];
       acc[3 * MAXC] += w * ce;
@@ -158,25 +173,26 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_grad_kernel(const SegParams P
     float z[MAXC], p[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) z[c] = c < P.C ? P.logits[((long long)n * P.C + c) * P.hw + q] : 0.f;
+    float lse = 0.f;
     if (P.is_prob) {
 #pragma unroll
       for (int c = 0; c < MAXC; ++c) p[c] = z[c];
     } else {
-      softmax_c(z, P.C, p);
+      lse = softmax_c(z, P.C, p);
     }
     const long long t = P.target[(long long)n * P.hw + q];
     const bool valid = t != P.ignore && t >= 0 && t < P.C;
-    float g[MAXC], gp = 0.f, pt = 1.f;
+    float g[MAXC], gp = 0.f, pt = 1.f, zt = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
       const bool hit = valid && t == c;
       g[c] = (hit ? A[c] : 0.f) + B[c];          // d loss / d p_c (Dice)
       gp += g[c] * p[c];
-      if (hit) pt = p[c];
+      if (hit) { pt = p[c]; zt = z[c]; }
     }
     float k = 0.f;                                // CE + focal both act through (p - onehot)
     if (valid) {
-      const float ce = -logf(fmaxf(pt, 1e-38f));
+      const float ce = P.is_prob ? -logf(fmaxf(pt, 1e-38f)) : lse - zt;
       const float w = P.cw ? P.cw[t] : 1.f;
       const float om = 1.f - pt;
       k = ce_s * w + fo_s * P.alpha * (powf(om, P.gamma) + P.gamma * powf(om, P.gamma - 1.f) * pt * ce);
