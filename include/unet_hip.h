@@ -474,6 +474,41 @@ int32_t unet_region_auc(uint64_t* pos_pairs, int64_t n_pos, uint32_t* neg_keys, 
                         int64_t max_region, double fpr_limit, double* out, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* The visualisation sheet of the evaluation CLI (src/test.py:315-332 -> src/utils.py:111-157 visualize_results, drawn
+ * there by matplotlib on the host): n rows of k <= 8 panels of h x w pixels as one packed uint8 RGB image
+ * sheet[n h + (n - 1) gutter][k w + (k - 1) gutter][3], panels separated by `gutter` pixels of 255 in both directions.
+ * panels: HOST array of k descriptions, one per column; rgb = fp32 [n][3][h][w], map = fp32 [n][1][h][w] (device):
+ *   UNET_PANEL_IMAGE    rgb, ImageNet-normalised: v = x * std3[c], then + mean3[c] (fp32, each rounded), clamped to
+ *                       [0, 1]; byte = (uint8)(v * 255.0f), truncating; NaN gives 0
+ *   UNET_PANEL_UNIT     rgb in [0, 1]: the clamp and the byte rule alone (the reconstruction)
+ *   UNET_PANEL_GRAY     map through a 256-entry colour table after scaling the plane to its own range, in fp64:
+ *   UNET_PANEL_HOT      t = ((double)x - lo) / (hi - lo), i = floor(256 t) clipped to [0, 255]; hi == lo gives i = 0;
+ *                       lo / hi = the smallest / largest finite value of the plane; a non-finite pixel, and every pixel
+ *                       of a plane without a finite one, is (255, 255, 255).  The index is the one matplotlib's
+ *                       cmap(Normalize()(x.astype(float64))) takes, exactly
+ *   UNET_PANEL_OVERLAY  rgb and map: (alpha8 * HOT(map) + (255 - alpha8) * IMAGE(rgb) + 127) / 255 per channel in
+ *                       integers, 0 <= alpha8 <= 255; a non-finite map pixel shows the image
+ * Two steps.  The range step writes keys[2][k][n] (uint32, device): the order-preserving keys (as in the rank-AUC
+ * append step, -0.0 == +0.0) of lo, then of hi, of every map plane; a plane without a finite pixel keeps lo = 0xffffffff
+ * > hi = 0; entries of panels without a map are not read.  Integer atomicMin / atomicMax only: independent of scheduling.
+ * The sheet step takes those keys and luts[2][256][3] (device bytes: the gray table, then the hot one) and writes the
+ * whole sheet in one launch.  mean3 / std3 are HOST arrays.  Any h, w >= 1 and gutter >= 0; k > 8, n >= 65536 or a sheet
+ * of 2^31 bytes or more is UNET_ERR_UNSUPPORTED.  Allocates nothing, does not synchronise. */
+enum unet_panel_kind {
+  UNET_PANEL_IMAGE = 0, UNET_PANEL_UNIT = 1, UNET_PANEL_GRAY = 2, UNET_PANEL_HOT = 3, UNET_PANEL_OVERLAY = 4
+};
+typedef struct unet_panel {
+  int32_t kind;        /* unet_panel_kind */
+  int32_t alpha8;      /* UNET_PANEL_OVERLAY only */
+  const float* rgb;
+  const float* map;
+} unet_panel;
+int32_t unet_render_range(const unet_panel* panels, int32_t k, int32_t n, int32_t h, int32_t w, uint32_t* keys,
+                          void* stream);
+int32_t unet_render_sheet(const unet_panel* panels, int32_t k, int32_t n, int32_t h, int32_t w, int32_t gutter,
+                          const float* mean3, const float* std3, const uint32_t* keys, const uint8_t* luts,
+                          uint8_t* sheet, void* stream);
+
 /* ---- nn.Dropout2d of SegmentationUNet's bottleneck (src/model.py:129,146): y = x * scale[n][c] on dense NHWC; the
  * caller draws scale = bernoulli(1-p)/(1-p) per (image, channel); the same call is the backward (dx = dy * scale). */
 int32_t unet_channel_scale(int32_t dtype, const void* x, const float* scale, int32_t n, int64_t hw, int32_t c, void* y,

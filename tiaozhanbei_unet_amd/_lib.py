@@ -39,6 +39,14 @@ class RemapDesc(C.Structure):
 
 
 REMAP_PAD, REMAP_UNPAD = 0, 1
+
+
+class Panel(C.Structure):
+    """struct unet_panel"""
+    _fields_ = [("kind", C.c_int32), ("alpha8", C.c_int32), ("rgb", C.c_void_p), ("map", C.c_void_p)]
+
+
+PANEL_IMAGE, PANEL_UNIT, PANEL_GRAY, PANEL_HOT, PANEL_OVERLAY = range(5)
 _i, _l, _f, _p, _z, _d = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes): every symbol include/unet_hip.h declares
@@ -123,6 +131,8 @@ SIGNATURES = {
     "unet_region_auc_append": (_i, [_p, _p, _p, _l, _l, _p, _l, _p, _p]),
     "unet_region_auc_workspace": (_z, [_l, _l]),
     "unet_region_auc": (_i, [_p, _l, _p, _l, _l, _l, _d, _p, _p, _z, _p]),
+    "unet_render_range": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "unet_render_sheet": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "unet_channel_scale": (_i, [_i, _p, _p, _i, _l, _i, _p, _p]),
     "unet_anomaly_score_workspace": (_z, [_i, _l]),
     "unet_anomaly_score": (_i, [_p, _p, _i, _i, _l, _i, _p, _p, _p, _z, _p]),

@@ -111,6 +111,18 @@ template <> struct Vec<bf16_t> {
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- scores as sort keys (rankauc.hip, render.hip) ------------------------------------------
+// order-preserving key of a finite float: -0.0 == +0.0 first, then sign-magnitude -> unsigned order
+__device__ __forceinline__ uint32_t score_key(float x) {
+  uint32_t u = __float_as_uint(x);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float score_of_key(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ bool finite_score(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
 // ---- segment map of a two-source (skip | up-sampled) convolution input with a narrow first source (widths.hip) ------
 // Packed column q of the padded input -> column of the parameter's input axis, or -1 (a zero column).  split = logical
 // channels of source 0; source 1 starts at pad64(split).  split == 0: contiguous, the columns >= c are zero.

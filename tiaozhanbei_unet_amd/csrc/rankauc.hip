@@ -46,13 +46,6 @@ struct AppendParams {
 // 8-byte slots: a positive is the element key << 32 | size from slot 0 up, a negative a uint32 key from the end down
 __device__ __forceinline__ uint64_t pair_of(uint32_t key, uint32_t size) { return ((uint64_t)key << 32) | size; }
 
-// order-preserving key of a finite float: -0.0 == +0.0 first, then sign-magnitude -> unsigned order
-__device__ __forceinline__ uint32_t score_key(float x) {
-  uint32_t u = __float_as_uint(x);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 template <int V>
 __device__ __forceinline__ void load_units(const float* p, const float* t, long long u, float (&x)[V], float (&y)[V]) {
   if constexpr (V == 4) {
@@ -64,7 +57,6 @@ __device__ __forceinline__ void load_units(const float* p, const float* t, long 
     x[0] = p[u]; y[0] = t[u];
   }
 }
-__device__ __forceinline__ bool finite_score(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 // A block owns a fixed unit range of one image and walks it twice: the first walk counts its positives, negatives and
 // non-finite scores (one atomicAdd per class for the whole block reserves its output ranges: a per-wave atomic on

@@ -1419,6 +1419,147 @@ def preprocess_u8(images_u8, flips=None, mean=(0.485, 0.456, 0.406), std=(0.229,
     return out
 
 
+# ----------------------------------------------------------------------------- visualisation sheet
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # reference src/utils.py:21
+_PANEL_KINDS = {"image": L.PANEL_IMAGE, "unit": L.PANEL_UNIT, "gray": L.PANEL_GRAY, "hot": L.PANEL_HOT,
+                "overlay": L.PANEL_OVERLAY}
+MAX_PANELS = 8
+# matplotlib's `hot` (_cm.py _hot_data): per channel the (x, y) knots of a piecewise-linear map
+_HOT_KNOTS = (((0.0, 0.0416), (0.365079, 1.0), (1.0, 1.0)),
+              ((0.0, 0.0), (0.365079, 0.0), (0.746032, 1.0), (1.0, 1.0)),
+              ((0.0, 0.0), (0.746032, 0.0), (1.0, 1.0)))
+_luts = {}                 # device index -> uint8 [2][256][3] (gray, hot), uploaded once
+
+
+def colormap_lut(name):
+    """The 256 RGB byte triples of matplotlib's `gray` or `hot` as a list of tuples, in host float64 (Python floats):
+    floor(255 * L(x_k)) at x_k = k * (1 / 255), x_255 = 1 -- the abscissae as numpy's linspace forms them, so 255 * x_k
+    falls below k for some k and gray is not simply (k, k, k).  L is linear between the knots, in matplotlib's
+    operation order.  matplotlib itself is not needed."""
+    if name not in ("gray", "hot"):
+        raise ValueError(f"colormap_lut: no table for {name!r}")
+
+    def level(knots, x):
+        for (x0, y0), (x1, y1) in zip(knots, knots[1:]):
+            if x <= x1:
+                return ((x - x0) / (x1 - x0)) * (y1 - y0) + y0
+        return knots[-1][1]
+
+    step = 1.0 / 255.0
+    out = []
+    for k in range(256):
+        x = k * step if k < 255 else 1.0
+        vals = (x, x, x) if name == "gray" else tuple(level(kn, x) for kn in _HOT_KNOTS)
+        out.append(tuple(int(255.0 * min(max(v, 0.0), 1.0)) for v in vals))      # (int() floors: nothing is negative)
+    return out
+
+
+def _render_luts(device):
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    t = _luts.get(key)
+    if t is None:
+        t = torch.tensor([colormap_lut("gray"), colormap_lut("hot")], dtype=torch.uint8).to(device)
+        _luts[key] = t
+    return t
+
+
+def _map_planes(t, what):
+    if not (t.dim() == 3 or (t.dim() == 4 and t.shape[1] == 1)):
+        raise ValueError(f"{what}: a map is (N, 1, H, W) or (N, H, W), got {tuple(t.shape)}")
+    return t.shape[0], t.shape[-2], t.shape[-1]
+
+
+def _panels(columns, what):
+    """Checks `columns` and returns (descriptors, n, h, w, tensors kept alive): nothing is launched before this passes."""
+    columns = list(columns)
+    if not 1 <= len(columns) <= MAX_PANELS:
+        raise ValueError(f"{what}: 1 to {MAX_PANELS} columns, got {len(columns)}")
+    parsed, shape, dev = [], None, None
+    for col in columns:
+        kind = col[0]
+        if kind not in _PANEL_KINDS or len(col) != (4 if kind == "overlay" else 2):
+            raise ValueError(f"{what}: a column is (kind, tensor) with kind in image / unit / gray / hot, or "
+                             f"('overlay', image, map, alpha); got {col[0]!r} with {len(col) - 1} values")
+        rgb = col[1] if kind in ("image", "unit", "overlay") else None
+        amap = col[2] if kind == "overlay" else (col[1] if rgb is None else None)
+        a8 = 0
+        if kind == "overlay":
+            if not 0.0 <= float(col[3]) <= 1.0:
+                raise ValueError(f"{what}: overlay alpha {col[3]} is not in [0, 1]")
+            a8 = int(round(255 * float(col[3])))
+        _require_cuda(rgb, amap)
+        for t, is_rgb in ((rgb, True), (amap, False)):
+            if t is None:
+                continue
+            if is_rgb:
+                if t.dim() != 4 or t.shape[1] != 3:
+                    raise ValueError(f"{what}: an {kind} input is (N, 3, H, W), got {tuple(t.shape)}")
+                nhw = (t.shape[0], t.shape[2], t.shape[3])
+            else:
+                nhw = _map_planes(t, what)
+            if min(nhw) < 1:
+                raise ValueError(f"{what}: empty input {tuple(t.shape)}")
+            shape, dev = shape or nhw, dev or t.device
+            if nhw != shape or t.device != dev:
+                raise ValueError(f"{what}: all columns share N, H, W and the device; got {nhw} on {t.device} after "
+                                 f"{shape} on {dev}")
+        parsed.append((kind, rgb, amap, a8))
+    descs, keep = (L.Panel * len(parsed))(), []
+    for i, (kind, rgb, amap, a8) in enumerate(parsed):
+        ptrs = []
+        for t in (rgb, amap):
+            if t is not None:
+                t = t.detach().float().contiguous()          # bf16 outputs are upcast; fp32 contiguous ones pass as they are
+                keep.append(t)
+            ptrs.append(None if t is None else t.data_ptr())
+        descs[i] = L.Panel(_PANEL_KINDS[kind], a8, ptrs[0], ptrs[1])
+    return descs, shape, keep
+
+
+def panel_range(t):
+    """(N, 2) fp32 DEVICE tensor: the smallest and the largest finite value of each plane of t (N, 1, H, W) or (N, H, W),
+    NaN / NaN for a plane without a finite pixel; -0.0 and +0.0 may fold.  The range pass of render_sheet on its own
+    (unet_render_range: integer atomics on order-preserving keys); does not synchronise."""
+    _require_cuda(t)
+    descs, (n, h, w), keep = _panels([("gray", t)], "panel_range")
+    keys = torch.empty((2, n), dtype=torch.int32, device=t.device)
+    L.check(L.lib().unet_render_range(descs, 1, n, h, w, _ptr(keys), _stream()), "unet_render_range")
+    k = keys.to(torch.int64) & 0xFFFFFFFF                    # the key transform, undone
+    bits = torch.where(k >= 1 << 31, k - (1 << 31), 0xFFFFFFFF - k)
+    vals = bits.to(torch.int32).view(torch.float32)
+    vals = torch.where((k[0] > k[1]).unsqueeze(0), torch.full_like(vals, float("nan")), vals)
+    return vals.t().contiguous()
+
+
+def render_sheet(columns, gutter=4, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """The visualisation sheet of visualize_results (/root/reference/src/utils.py:111-157) as a uint8 DEVICE tensor
+    (N H + (N - 1) gutter, K W + (K - 1) gutter, 3): one row per sample, one panel per column, `gutter` pixels of 255
+    between panels.  columns: up to 8 of ("image", t) -- ImageNet-normalised (N, 3, H, W), denormalised with mean / std
+    and clamped --, ("unit", t) -- (N, 3, H, W) clamped to [0, 1] --, ("gray", t) / ("hot", t) -- (N, 1, H, W) maps, each
+    plane scaled to its own finite range and sent through matplotlib's table --, ("overlay", image, map, alpha) -- the
+    hot map blended over the image, 0 <= alpha <= 1.  Bytes equal matplotlib's (see include/unet_hip.h).  Two launches
+    (unet_render_range, unet_render_sheet); does not synchronise."""
+    descs, (n, h, w), keep = _panels(columns, "render_sheet")
+    gutter = int(gutter)
+    if gutter < 0:
+        raise ValueError(f"render_sheet: gutter {gutter} is negative")
+    dev = keep[0].device
+    k = len(descs)
+    rows, cols = n * h + (n - 1) * gutter, k * w + (k - 1) * gutter
+    if rows * cols * 3 >= 1 << 31:
+        raise ValueError(f"render_sheet: a sheet of {rows} x {cols} pixels (fewer than 2^31 bytes are supported)")
+    luts = _render_luts(dev)
+    keys = torch.empty((2, k, n), dtype=torch.int32, device=dev)
+    sheet = torch.empty((rows, cols, 3), dtype=torch.uint8, device=dev)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s_ = (C.c_float * 3)(*[float(v) for v in std])
+    lib = L.lib()
+    L.check(lib.unet_render_range(descs, k, n, h, w, _ptr(keys), _stream()), "unet_render_range")
+    L.check(lib.unet_render_sheet(descs, k, n, h, w, gutter, m, s_, _ptr(keys), _ptr(luts), _ptr(sheet), _stream()),
+            "unet_render_sheet")
+    return sheet
+
+
 # ----------------------------------------------------------------------------- profiling / optimiser
 def prof_enable(on: bool) -> None:
     L.check(L.lib().unet_prof_enable(int(on)), "unet_prof_enable")

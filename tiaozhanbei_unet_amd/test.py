@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Evaluation CLI with the reference's contract (/root/reference/src/test.py: flags :26-61, test_model :66-133,
-`test_metrics.json` / `detailed_results.json` :187-232) on the HIP path.  The forward runs on the GPU; thresholding
-and metrics are host numpy, as in the reference."""
+`test_metrics.json` / `detailed_results.json` :187-232, `visualizations.png` :315-332) on the HIP path.  The forward
+runs on the GPU; thresholding and metrics are host numpy, as in the reference; the visualisation sheet is rendered on
+the GPU (ops.render_sheet) and only encoded on the host."""
 import argparse
 import json
 import os
@@ -27,7 +28,9 @@ FLAGS = [  # reference src/test.py:26-61
     ("--precision", dict(type=str, default="fp32", choices=["fp32", "bf16"])),   # build-only
     ("--pro_fpr_limit", dict(type=float, default=0.3)),     # build-only: the PRO curve is integrated up to this fpr
     ("--binary_masks", dict(action="store_true")),          # build-only: masks as (mask > 0) instead of k / 255
+    ("--vis_overlay_alpha", dict(type=float, default=None)),    # build-only: adds an anomaly-map-over-image column
 ]
+VIS_GUTTER = 4              # white pixels between the panels of visualizations.png
 
 
 def parse_args(argv=None):
@@ -37,6 +40,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if not 0.0 < args.pro_fpr_limit <= 1.0:
         raise SystemExit(f"--pro_fpr_limit must be in (0, 1], got {args.pro_fpr_limit}")
+    if args.vis_overlay_alpha is not None and not 0.0 <= args.vis_overlay_alpha <= 1.0:
+        raise SystemExit(f"--vis_overlay_alpha must be in [0, 1], got {args.vis_overlay_alpha}")
     return args
 
 
@@ -114,6 +119,43 @@ def evaluate_results(results, pixel_thresholds):
     return ev
 
 
+def save_visualizations(results, out_dir, max_samples, with_reconstruction, overlay_alpha=None):
+    """`visualizations.png` of the reference (src/test.py:315-332 -> src/utils.py:111-157 visualize_results): a random
+    choice of min(max_samples, all) test samples, one row each: original | true mask (gray) | predicted map (hot) |
+    reconstruction (with_reconstruction) | map over original (overlay_alpha).  Rendered on the device at native resolution
+    (ops.render_sheet), encoded once with Pillow; no titles or axes: `visualizations.json` beside it names, row by row,
+    what matplotlib's titles would.  Returns the path of the PNG (None when there is nothing to draw)."""
+    from PIL import Image
+    from . import ops
+    total = len(results["images"])
+    n = min(max_samples, total)
+    if n <= 0:
+        return None
+    indices = np.random.choice(total, n, replace=False)         # the reference's draw (:321)
+    dev = torch.device("cuda")
+    images = torch.stack([results["images"][i] for i in indices]).to(dev)
+    masks = torch.as_tensor(np.stack([results["masks_true"][i] for i in indices])).to(dev)
+    maps = torch.as_tensor(np.stack([results["anomaly_maps"][i] for i in indices])).to(dev)
+    columns = [("image", images), ("gray", masks), ("hot", maps)]
+    if with_reconstruction:
+        columns.append(("unit", torch.stack([results["reconstructions"][i] for i in indices]).to(dev)))
+    if overlay_alpha is not None:
+        columns.append(("overlay", images, maps, float(overlay_alpha)))
+    sheet = ops.render_sheet(columns, gutter=VIS_GUTTER)
+    path = os.path.join(out_dir, "visualizations.png")
+    Image.fromarray(sheet.cpu().numpy()).save(path)
+    names = {"image": "original", "gray": "mask_true", "hot": "anomaly_map", "unit": "reconstruction",
+             "overlay": "overlay"}
+    rows = [{"index": int(i), "image_path": str(results["image_paths"][i]), "label": int(results["labels"][i]),
+             "anomaly_type": str(results["anomaly_types"][i]), "image_score": float(results["image_scores"][i]),
+             "prediction": int(results["predictions"][i])} for i in indices]
+    with open(os.path.join(out_dir, "visualizations.json"), "w") as f:
+        json.dump({"columns": [names[c[0]] for c in columns], "gutter": VIS_GUTTER, "overlay_alpha": overlay_alpha,
+                   "panel_size": [int(images.shape[2]), int(images.shape[3])], "rows": rows}, f, indent=2)
+    print(f"Visualization saved to {path}")
+    return path
+
+
 def main(argv=None):
     from . import AnomalyUNet, UNet
     from .dataset import get_available_categories, get_dataloaders
@@ -152,6 +194,10 @@ def main(argv=None):
         json.dump({"labels": results["labels"].tolist(), "predictions": results["predictions"].tolist(),
                    "anomaly_scores": results["image_scores"].tolist(), "anomaly_types": list(results["anomaly_types"]),
                    "image_paths": list(results["image_paths"]), "threshold": float(results["threshold"])}, f, indent=2)
+    if args.save_visualizations:
+        print("Saving visualizations...")
+        save_visualizations(results, out_dir, args.max_vis_samples, args.model == "anomaly_unet",
+                            args.vis_overlay_alpha)
     print(f"\nTesting completed!\nResults saved to: {out_dir}")
     return out_dir
 
