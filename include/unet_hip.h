@@ -509,6 +509,52 @@ int32_t unet_render_sheet(const unet_panel* panels, int32_t k, int32_t n, int32_
                           const float* mean3, const float* std3, const uint32_t* keys, const uint8_t* luts,
                           uint8_t* sheet, void* stream);
 
+/* Per-pixel prediction and confidence of the Gear / KolektorSDD visualisation CLIs (visualize.py:134-135,
+ * visualize_kolektorsdd.py:131: softmax(logits, dim=0).max(dim=0)[0]; torch.argmax) of fp32 NCHW logits [n][c][hw],
+ * 2 <= c <= 8 (the limits of unet_seg_image_stats): labels[n][hw] (uint8) = argmax over classes, the FIRST maximum winning
+ * ties (as torch.argmax and unet_seg_image_stats); conf[n][hw] (fp32) = 1 / sum_j expf(z_j - max z), every operation in
+ * fp32, j in class order.  labels or conf may be NULL (not both).  The contract covers finite logits.  One streaming
+ * launch: a lane owns 4 consecutive pixels (16-byte loads and stores) when hw % 4 == 0 and the pointers are aligned
+ * (logits, conf 16 bytes; labels 4), else one pixel -- with hw % 4 != 0 the class planes of a pixel do not share an
+ * alignment, so such shapes run on scalar accesses throughout.  Other c, n < 1 or hw < 1: UNET_ERR_UNSUPPORTED.
+ * Allocates nothing, does not synchronise. */
+int32_t unet_seg_confidence(const float* logits, int32_t n, int32_t c, int64_t hw, uint8_t* labels, float* conf,
+                            void* stream);
+
+/* The prediction sheets of the Gear / KolektorSDD visualisation CLIs (visualize.py:120-236 visualize_single_prediction /
+ * visualize_prediction_grid, visualize_kolektorsdd.py:101-202, drawn there by matplotlib on the host) as one packed
+ * uint8 RGB image written by one launch: R = ceil(n / per_row) rows of per_row samples, each sample k <= 8 panels of
+ * h x w pixels side by side; sample i sits in row i / per_row at cell i % per_row.
+ * sheet[R h + (R - 1) gutter][per_row k w + (per_row k - 1) gutter][3]; the gutters and the cells past n are 255.
+ * image = fp32 [n][3][h][w], ImageNet-normalised (device; may be NULL when no panel draws it).  panels: HOST array of k
+ * descriptions; labels = uint8 [n][h][w], map = fp32 [n][h][w] (device):
+ *   UNET_SEG_PANEL_IMAGE    the bytes of UNET_PANEL_IMAGE: v = x * std3[c], then + mean3[c] (fp32, each rounded), clamped
+ *                           to [0, 1], NaN gives 0; byte = (uint8)(v * 255.0f), truncating
+ *   UNET_SEG_PANEL_CLASSES  palette[labels[p]] (imshow(mask, cmap='tab10', ...), visualize_kolektorsdd.py:118-124)
+ *   UNET_SEG_PANEL_OVERLAY  where labels[p] == 0 the IMAGE byte (no overlay on the background, visualize.py:112-113),
+ *                           elsewhere (alpha8 * palette[l] + (255 - alpha8) * IMAGE + 127) / 255 per channel in integers,
+ *                           0 <= alpha8 <= 255: the blend of UNET_PANEL_OVERLAY.  This is the library's own blend; it is
+ *                           NOT claimed to equal Agg's compositing of the reference's RGBA layer (visualize.py:102-117)
+ *   UNET_SEG_PANEL_LUT      map over the fixed range [0, 1] (imshow(vmin=0, vmax=1), visualize_kolektorsdd.py:132):
+ *                           lut[min(floor(v * 256), 255)] for finite v, v < 0 gives lut[0]; a non-finite pixel is
+ *                           (255, 255, 255), like the map panels of unet_render_sheet
+ * palette[256][3] and lut[256][3] are device bytes; mean3 / std3 are HOST arrays.  Any h, w >= 1, gutter >= 0 and
+ * per_row >= 1 (pixels are packed into whole 32-bit stores where the row allows, byte stores elsewhere); k > 8,
+ * n >= 65536 or a sheet of 2^31 bytes or more is UNET_ERR_UNSUPPORTED.  The bytes are a function of the inputs alone.
+ * Allocates nothing, does not synchronise. */
+enum unet_seg_panel_kind {
+  UNET_SEG_PANEL_IMAGE = 0, UNET_SEG_PANEL_CLASSES = 1, UNET_SEG_PANEL_OVERLAY = 2, UNET_SEG_PANEL_LUT = 3
+};
+typedef struct unet_seg_panel {
+  int32_t kind;        /* unet_seg_panel_kind */
+  int32_t alpha8;      /* UNET_SEG_PANEL_OVERLAY only */
+  const uint8_t* labels;
+  const float* map;
+} unet_seg_panel;
+int32_t unet_seg_render_sheet(const float* image, const unet_seg_panel* panels, int32_t k, int32_t n, int32_t h,
+                              int32_t w, int32_t gutter, int32_t per_row, const float* mean3, const float* std3,
+                              const uint8_t* palette, const uint8_t* lut, uint8_t* sheet, void* stream);
+
 /* ---- nn.Dropout2d of SegmentationUNet's bottleneck (src/model.py:129,146): y = x * scale[n][c] on dense NHWC; the
  * caller draws scale = bernoulli(1-p)/(1-p) per (image, channel); the same call is the backward (dx = dy * scale). */
 int32_t unet_channel_scale(int32_t dtype, const void* x, const float* scale, int32_t n, int64_t hw, int32_t c, void* y,

@@ -47,6 +47,14 @@ class Panel(C.Structure):
 
 
 PANEL_IMAGE, PANEL_UNIT, PANEL_GRAY, PANEL_HOT, PANEL_OVERLAY = range(5)
+
+
+class SegPanel(C.Structure):
+    """struct unet_seg_panel"""
+    _fields_ = [("kind", C.c_int32), ("alpha8", C.c_int32), ("labels", C.c_void_p), ("map", C.c_void_p)]
+
+
+SEG_PANEL_IMAGE, SEG_PANEL_CLASSES, SEG_PANEL_OVERLAY, SEG_PANEL_LUT = range(4)
 _i, _l, _f, _p, _z, _d = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes): every symbol include/unet_hip.h declares
@@ -133,6 +141,8 @@ SIGNATURES = {
     "unet_region_auc": (_i, [_p, _l, _p, _l, _l, _l, _d, _p, _p, _z, _p]),
     "unet_render_range": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "unet_render_sheet": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "unet_seg_confidence": (_i, [_p, _i, _i, _l, _p, _p, _p]),
+    "unet_seg_render_sheet": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "unet_channel_scale": (_i, [_i, _p, _p, _i, _l, _i, _p, _p]),
     "unet_anomaly_score_workspace": (_z, [_i, _l]),
     "unet_anomaly_score": (_i, [_p, _p, _i, _i, _l, _i, _p, _p, _p, _z, _p]),

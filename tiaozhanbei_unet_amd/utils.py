@@ -131,3 +131,28 @@ def plot_training_curves(train_losses, val_losses, save_path=None):
     if save_path:
         fig.savefig(save_path, dpi=120, bbox_inches="tight")
     plt.close(fig)
+
+
+def setup_logging(log_dir, experiment_name, log_level=None):
+    """Logger writing to ``{log_dir}/{experiment_name}_{timestamp}.log`` and to stdout (reference src/utils.py:218-269:
+    the same file name, formats and levels).  Handlers of an earlier call under the same name are closed and replaced."""
+    import logging
+    import sys
+    from datetime import datetime
+    level = logging.INFO if log_level is None else log_level
+    os.makedirs(log_dir, exist_ok=True)
+    logger = logging.getLogger(experiment_name)
+    logger.setLevel(level)
+    for h in list(logger.handlers):
+        logger.removeHandler(h)
+        h.close()
+    path = os.path.join(log_dir, f"{experiment_name}_{datetime.now().strftime('%Y%m%d_%H%M%S')}.log")
+    to_file = logging.FileHandler(path, encoding="utf-8")
+    to_file.setFormatter(logging.Formatter("%(asctime)s - %(name)s - %(levelname)s - %(message)s", "%Y-%m-%d %H:%M:%S"))
+    to_console = logging.StreamHandler(sys.stdout)
+    to_console.setFormatter(logging.Formatter("%(asctime)s - %(levelname)s - %(message)s", "%H:%M:%S"))
+    for h in (to_file, to_console):
+        h.setLevel(level)
+        logger.addHandler(h)
+    logger.info(f"Logging initialized. Log file: {path}")
+    return logger
