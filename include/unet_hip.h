@@ -609,6 +609,18 @@ int32_t unet_polygon_mask_u8(const int32_t* verts, const int32_t* poly_offsets, 
                              const int32_t* poly_image, int32_t n_polys, int32_t max_poly_vertices, const int32_t* src_hw,
                              int32_t n, int32_t out_h, int32_t out_w, const int32_t* yidx, const int32_t* xidx,
                              uint8_t* dst, void* stream);
+/* Class-overlap census of Gear label sets (reference analyze_class_overlaps.py): hist[n][8] (int64, DEVICE),
+ * hist[i][b] = number of pixels of image i, at its native src_hw[i] = (h, w), whose set of covering raw classes is
+ * exactly b -- bit c of b is set when at least one class-c polygon covers the pixel (several polygons of one class are
+ * OR-ed; classes outside 0..2 are skipped).  Coverage is unet_polygon_mask_u8's rule and code; the polygon arrays have
+ * the same layout and limits.  max_h / max_w = the largest height / width in src_hw: the grid scans rows 0 .. max_h - 1
+ * of every image (rows beyond an image's height add nothing) and max_w <= 4096, n <= 65535, max_poly_vertices <= 512,
+ * else UNET_ERR_UNSUPPORTED; an image wider than max_w adds nothing.  hist is cleared on `stream` before the launch;
+ * the bins of image i sum to h * w.  Integer atomics only: the result does not depend on scheduling. */
+int32_t unet_polygon_class_histogram(const int32_t* verts, const int32_t* poly_offsets, const int32_t* poly_class,
+                                     const int32_t* poly_image, int32_t n_polys, int32_t max_poly_vertices,
+                                     const int32_t* src_hw, int32_t n, int32_t max_h, int32_t max_w, int64_t* hist,
+                                     void* stream);
 /* RandomHorizontalFlip + RandomRotation: dst = rotate(flip[n] ? mirror(src) : src) with Image.rotate(angle, NEAREST,
  * expand=False, fill 0) = Geometry.c affine_fixed in 16.16 fixed point.  matrices[n][6] (DEVICE, may be NULL: no
  * rotation) = {a0, a1, a2, a3, a4, a5} ALREADY in fixed point, a2 / a5 including the half-pixel terms (FIX(a[2] +

@@ -153,6 +153,7 @@ SIGNATURES = {
     "unet_resize_nearest_index": (_i, [_i, _i, _p]),
     "unet_resize_nearest_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "unet_polygon_mask_u8": (_i, [_p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "unet_polygon_class_histogram": (_i, [_p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _p, _p]),
     "unet_flip_rotate_u8": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "unet_color_jitter_workspace": (_z, [_i]),
     "unet_color_jitter_normalize_u8": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _z, _p]),

@@ -240,6 +240,7 @@ class DeviceTransform:
 
 
 POLY_MAX_VERTICES = 512      # unet_polygon_mask_u8: crossings of one polygon on one scan line live in LDS
+POLY_MAX_WIDTH = 4096        # ... and so does the row of class bits
 
 
 def _nearest_tables(sizes, out_h, out_w, device):
@@ -247,6 +248,31 @@ def _nearest_tables(sizes, out_h, out_w, device):
     ys = [_axis_tables("nearest", h, out_h, device)[0] for h, _ in sizes]
     xs = [_axis_tables("nearest", w, out_w, device)[0] for _, w in sizes]
     return torch.stack(ys).contiguous(), torch.stack(xs).contiguous()
+
+
+def _check_polygons(what, polys, sizes):
+    """The flat polygon arrays of ``gear_dataset.flatten_polygons`` as int64 numpy arrays, refused with ValueError when
+    they do not describe ``len(sizes)`` images the polygon kernels can take: (verts, offsets, classes, images, counts)."""
+    n = len(sizes)
+    verts = np.ascontiguousarray(np.asarray(polys["verts"], dtype=np.int64).reshape(-1, 2))
+    offsets = np.asarray(polys["offsets"], dtype=np.int64).reshape(-1)
+    classes = np.asarray(polys["classes"], dtype=np.int64).reshape(-1)
+    images = np.asarray(polys["images"], dtype=np.int64).reshape(-1)
+    p = len(classes)
+    if len(offsets) != p + 1 or len(images) != p or offsets[0] != 0 or offsets[-1] != len(verts):
+        raise ValueError(f"{what}: offsets / classes / images do not describe the vertex array")
+    counts = np.diff(offsets)
+    if p and (counts.min() < 3 or counts.max() > POLY_MAX_VERTICES):
+        bad = int(np.argmax((counts < 3) | (counts > POLY_MAX_VERTICES)))
+        raise ValueError(f"{what}: polygon {bad} of image {int(images[bad])} has {int(counts[bad])} vertices; "
+                         f"every polygon needs 3..{POLY_MAX_VERTICES}")
+    if p and (np.any(np.diff(images) < 0) or images.min() < 0 or images.max() >= n):
+        raise ValueError(f"{what}: image indices must be non-decreasing and inside the batch")
+    if verts.size and np.abs(verts).max() >= (1 << 24):
+        raise ValueError(f"{what}: coordinates must stay below 2^24 in magnitude (exact in float32)")
+    if any(h <= 0 or w <= 0 or h >= (1 << 24) or w >= (1 << 24) for h, w in sizes):
+        raise ValueError(f"{what}: bad source size")
+    return verts, offsets, classes, images, counts
 
 
 def polygon_masks_u8(polys, src_sizes, out_h: int, out_w: int, device="cuda") -> torch.Tensor:
@@ -264,24 +290,8 @@ def polygon_masks_u8(polys, src_sizes, out_h: int, out_w: int, device="cuda") ->
     n = len(sizes)
     if n == 0 or out_h <= 0 or out_w <= 0:
         raise ValueError("polygon_masks_u8: need at least one image and a positive output size")
-    verts = np.ascontiguousarray(np.asarray(polys["verts"], dtype=np.int64).reshape(-1, 2))
-    offsets = np.asarray(polys["offsets"], dtype=np.int64).reshape(-1)
-    classes = np.asarray(polys["classes"], dtype=np.int64).reshape(-1)
-    images = np.asarray(polys["images"], dtype=np.int64).reshape(-1)
+    verts, offsets, classes, images, counts = _check_polygons("polygon_masks_u8", polys, sizes)
     p = len(classes)
-    if len(offsets) != p + 1 or len(images) != p or offsets[0] != 0 or offsets[-1] != len(verts):
-        raise ValueError("polygon_masks_u8: offsets / classes / images do not describe the vertex array")
-    counts = np.diff(offsets)
-    if p and (counts.min() < 3 or counts.max() > POLY_MAX_VERTICES):
-        bad = int(np.argmax((counts < 3) | (counts > POLY_MAX_VERTICES)))
-        raise ValueError(f"polygon_masks_u8: polygon {bad} of image {int(images[bad])} has {int(counts[bad])} vertices; "
-                         f"every polygon needs 3..{POLY_MAX_VERTICES}")
-    if p and (np.any(np.diff(images) < 0) or images.min() < 0 or images.max() >= n):
-        raise ValueError("polygon_masks_u8: image indices must be non-decreasing and inside the batch")
-    if verts.size and np.abs(verts).max() >= (1 << 24):
-        raise ValueError("polygon_masks_u8: coordinates must stay below 2^24 in magnitude (exact in float32)")
-    if any(h <= 0 or w <= 0 or h >= (1 << 24) or w >= (1 << 24) for h, w in sizes):
-        raise ValueError("polygon_masks_u8: bad source size")
     if p == 0:                               # nothing to draw: all background
         return torch.zeros((n, out_h, out_w), dtype=torch.uint8, device=device)
 
@@ -295,3 +305,42 @@ def polygon_masks_u8(polys, src_sizes, out_h: int, out_w: int, device="cuda") ->
     L.check(L.lib().unet_polygon_mask_u8(_ptr(v_d), _ptr(o_d), _ptr(c_d), _ptr(i_d), p, int(counts.max()), _ptr(hw), n,
                                          out_h, out_w, _ptr(yi), _ptr(xi), _ptr(out), _stream()), "unet_polygon_mask_u8")
     return out
+
+
+def polygon_class_histogram(polys, src_sizes, device="cuda") -> torch.Tensor:
+    """Per-image histogram of raw-class bit sets (unet_polygon_class_histogram): int64 [N, 8], ``hist[i][b]`` = pixels of
+    image ``i`` at its native size whose covering raw classes are exactly the bits of ``b`` (1 = raw 0 pitting, 2 = raw 1
+    spalling, 4 = raw 2 scrape).  Everything ``analyze_class_overlaps.py`` of the reference reports per file (pixels per
+    class, pairwise and triple overlaps, the classes after priority resolution) is a sum of these bins; no mask leaves
+    the chip.  ``polys`` / ``src_sizes`` as for ``polygon_masks_u8``, coverage by the same rule; widths at most
+    ``POLY_MAX_WIDTH``.  With no polygons the histogram is ``hist[i][0] = h * w``, without a launch."""
+    sizes = [(int(h), int(w)) for h, w in src_sizes]
+    n = len(sizes)
+    if n == 0:
+        raise ValueError("polygon_class_histogram: need at least one image")
+    verts, offsets, classes, images, counts = _check_polygons("polygon_class_histogram", polys, sizes)
+    wide = [i for i, (_, w) in enumerate(sizes) if w > POLY_MAX_WIDTH]
+    if wide:
+        raise ValueError(f"polygon_class_histogram: image {wide[0]} is {sizes[wide[0]][1]} pixels wide; the kernel takes "
+                         f"at most {POLY_MAX_WIDTH}")
+    if n > 65535:
+        raise ValueError("polygon_class_histogram: at most 65535 images per call")
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    p = len(classes)
+    if p == 0:                               # nothing drawn: every pixel has the empty class set
+        hist = torch.zeros((n, 8), dtype=torch.int64)
+        hist[:, 0] = torch.tensor([h * w for h, w in sizes], dtype=torch.int64)
+        return hist.to(device)
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device, non_blocking=True)
+
+    hw = dev(np.asarray(sizes, dtype=np.int32).reshape(n, 2))
+    v_d, o_d, c_d, i_d = dev(verts), dev(offsets), dev(classes), dev(images)
+    hist = torch.empty((n, 8), dtype=torch.int64, device=device)
+    L.check(L.lib().unet_polygon_class_histogram(_ptr(v_d), _ptr(o_d), _ptr(c_d), _ptr(i_d), p, int(counts.max()),
+                                                 _ptr(hw), n, max(h for h, _ in sizes), max(w for _, w in sizes),
+                                                 _ptr(hist), _stream()), "unet_polygon_class_histogram")
+    return hist

@@ -33,11 +33,13 @@ PRIORITY = (1, 0, 2)                                    # spalling > pitting > s
 RAW_TO_FINAL = {0: 1, 1: 2, 2: 3}
 
 
-def parse_labelme_txt(path, w, h):
+def parse_labelme_txt(path, w, h, keep_partial=False):
     """[(raw class id, [(x, y), ...])] of a LabelMe txt file at image size (w, h), parsed like the reference's
     ``_create_mask_from_labelme`` (:121-147): lines of fewer than 5 tokens are skipped, an odd trailing coordinate is
     dropped, polygons of fewer than 3 points are skipped, and any exception anywhere in the file yields NO polygons
-    (the reference then returns an all-zero mask)."""
+    (the reference then returns an all-zero mask).  ``keep_partial=True`` is the rule of the reference's
+    ``analyze_class_overlaps.py`` instead: its ``try`` encloses the loop and it returns what it has drawn, so the
+    polygons of the lines before the exception are kept and the warning is printed."""
     polys = []
     try:
         with open(path, "r") as f:
@@ -56,8 +58,10 @@ def parse_labelme_txt(path, w, h):
                         pts.append((int(coords[i] * w), int(coords[i + 1] * h)))
                 if len(pts) >= 3:
                     polys.append((class_id, pts))
-    except Exception:
-        return []
+    except Exception as e:
+        if not keep_partial:
+            return []
+        print(f"Warning: Could not parse label file {path}: {e}")
     return polys
 
 
