@@ -449,6 +449,37 @@ size_t unet_label_regions_workspace(int64_t n, int64_t h, int64_t w);
 int32_t unet_label_regions(const float* truth, const uint8_t* select, int64_t n, int64_t h, int64_t w, int32_t* labels,
                            int32_t* sizes, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Class regions of uint8 label maps and their overlaps (no reference counterpart: the defect-level figures of the Gear
+ * and KolektorSDD evaluation -- defects found, false alarms, parts rejected -- need the connected defects of the truth
+ * and of the argmax prediction).  classes: uint8 [n][h][w]; a pixel has class c iff its value is c with
+ * 1 <= c < num_classes; 0 and every value >= num_classes (255, the ignore value, among them) are background.  A class
+ * region is an 8-connected component of pixels of one and the same class in one image: touching regions of different
+ * classes stay apart.
+ * unet_label_class_regions: region[n][h][w] (int32) = 1 + the smallest linear index y * w + x of the pixel's region (the
+ * numbering of unet_label_regions), sizes[n][h][w] (int32) = the region's pixel count at every one of its pixels; both
+ * 0 on background.  counts[n][num_classes] (int64, device) = regions per image and class (column 0 stays as it is) is
+ * ADDED to: zero it first.  The tiled union-find of unet_label_regions with "has my class" as the union predicate.
+ * unet_match_class_regions: truth / pred with the region and sizes arrays that unet_label_class_regions made of them.  A
+ * predicted region is kept iff its size >= min_pixels (>= 1).  hit of a truth region = its pixels whose predicted class
+ * is the region's class and whose predicted region is kept; hit of a kept predicted region = its pixels whose truth class
+ * is its class.  Every truth region goes to truth_records and every kept predicted region to pred_records as one record
+ * of 5 int32 {image_base + image, class, root index y * w + x, size, hit}, at the slot that an atomic add on
+ * record_counts[2] = {truth, predicted} (int64, device; ADDED to: zero it first) hands out: the order is arbitrary, sort
+ * by (image, root index).  capacity = records that each buffer holds; a record past it is counted and not written.
+ * Integer atomics only: apart from the record order the outputs are a function of the two maps alone.
+ * Both: any h, w >= 1; n < 65536, n h w <= 2^31 - 1 and 2 <= num_classes <= 255, else UNET_ERR_UNSUPPORTED before any
+ * launch (and the workspace queries return 0).  Allocate nothing, do not synchronise. */
+size_t unet_label_class_regions_workspace(int64_t n, int64_t h, int64_t w, int32_t num_classes);
+int32_t unet_label_class_regions(const uint8_t* classes, int64_t n, int64_t h, int64_t w, int32_t num_classes,
+                                 int32_t* region, int32_t* sizes, int64_t* counts, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+size_t unet_match_class_regions_workspace(int64_t n, int64_t h, int64_t w, int32_t num_classes);
+int32_t unet_match_class_regions(const uint8_t* truth, const int32_t* truth_region, const int32_t* truth_sizes,
+                                 const uint8_t* pred, const int32_t* pred_region, const int32_t* pred_sizes, int64_t n,
+                                 int64_t h, int64_t w, int32_t num_classes, int32_t min_pixels, int32_t image_base,
+                                 int32_t* truth_records, int32_t* pred_records, int64_t capacity,
+                                 int64_t* record_counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* AUPRO: the area below the per-region-overlap curve up to a false-positive rate of fpr_limit, divided by fpr_limit (the
  * localisation metric of the MVTec AD evaluation; no reference counterpart).  With R regions and N ok pixels, walking
  * the distinct scores v downwards from the point (0, 0): fpr = #{ok pixels >= v} / N, pro = sum over the defective

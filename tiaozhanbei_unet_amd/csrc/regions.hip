@@ -10,15 +10,11 @@
 //   finish         every pixel: label = 1 + region root, size = the root's count; the totals {regions, defective, ok}.
 // A link only ever decreases and always stays inside its region, so a stale read costs a retry, never a wrong union;
 // the minimum index of a region is its only possible root, so labels and sizes are a function of the mask alone.
-#include "common.h"
+#include "unionfind.h"
 
 namespace {
 
-constexpr int LT = 32;                                 // tile edge
-constexpr int LT_PIX = LT * LT;
-constexpr int LT_THREADS = 256;
-constexpr int LT_ITEMS = LT_PIX / LT_THREADS;
-constexpr int PX_THREADS = 256;
+using namespace uf;                                   // tiles, links, find_root, unite (unionfind.h)
 constexpr int FIN_ITEMS = 8;                           // pixels per lane of finish_labels: 3 count atomics per 2048 pixels
 
 struct LabelParams {
@@ -28,31 +24,6 @@ struct LabelParams {
   int* parent; int* labels; int* sizes;
   unsigned long long* counts;                          // {regions, defective, ok}
 };
-
-template <int SCOPE>
-__device__ __forceinline__ int link_of(const int* L, int i) { return __hip_atomic_load(&L[i], __ATOMIC_RELAXED, SCOPE); }
-
-template <int SCOPE>
-__device__ __forceinline__ int find_root(const int* L, int i) {
-  int r = link_of<SCOPE>(L, i);
-  while (r != i) { i = r; r = link_of<SCOPE>(L, i); }
-  return r;
-}
-
-// the larger root is linked below the smaller; a lost race (the link was no longer a's own) carries on from what
-// the atomic returned, which is in a's set
-template <int SCOPE>
-__device__ __forceinline__ void unite(int* L, int a, int b) {
-  for (;;) {
-    a = find_root<SCOPE>(L, a);
-    b = find_root<SCOPE>(L, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(&L[a], b);
-    if (old == a) return;
-    a = old;
-  }
-}
 
 __global__ __launch_bounds__(LT_THREADS) void label_tile(const LabelParams A) {
   __shared__ int par[LT_PIX];
@@ -143,12 +114,7 @@ __global__ __launch_bounds__(PX_THREADS) void root_sizes(const LabelParams A) {
   if (g >= A.per) return;
   int* parent = A.parent + (long long)n * A.per;
   int* sizes = A.sizes + (long long)n * A.per;
-  const int own = __hip_atomic_load(&sizes[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (own <= 0) return;                                // not a tile root
-  const int r = find_root<__HIP_MEMORY_SCOPE_AGENT>(parent, (int)g);
-  if (r == (int)g) return;
-  atomicAdd(&sizes[r], own);                           // integer: exact in any order; nobody adds to a non-root
-  __hip_atomic_store(&parent[g], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  add_tile_root(parent, sizes, (int)g);
 }
 
 __global__ __launch_bounds__(PX_THREADS) void finish_labels(const LabelParams A) {
@@ -193,13 +159,7 @@ __global__ __launch_bounds__(PX_THREADS) void finish_labels(const LabelParams A)
   }
 }
 
-inline bool supported(int64_t n, int64_t h, int64_t w) {
-  if (n <= 0 || h <= 0 || w <= 0 || n >= 65536) return false;
-  const int64_t lim = (1LL << 31) - 1;
-  if (h > lim || w > lim || h > lim / w) return false;
-  return n <= lim / (h * w);                           // n h w <= 2^31 - 1
-}
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+inline bool supported(int64_t n, int64_t h, int64_t w) { return frames_supported(n, h, w); }
 
 }  // namespace
 

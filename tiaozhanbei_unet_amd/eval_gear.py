@@ -32,17 +32,19 @@ def _class_names(dataset, num_classes):
     return ["background", "pitting", "spalling", "scrape"][:num_classes]       # reference test.py:289 (Subset)
 
 
+def _batches(args, loader, device):
+    """(images, masks, paths) device batches of a raw loader"""
+    from .gear_dataset import GearPreprocess
+    pre = GearPreprocess((args.image_size, args.image_size), train=False)
+    for images, polys, sizes, paths in loader:
+        x, m = pre(images, polys, sizes, device=device)
+        yield x, m, paths
+
+
 def main(argv=None):
     args = parse_args(argv)
-
-    def batches(loader, device):
-        from .gear_dataset import GearPreprocess
-        pre = GearPreprocess((args.image_size, args.image_size), train=False)
-        for images, polys, sizes, paths in loader:
-            x, m = pre(images, polys, sizes, device=device)
-            yield x, m, paths
-
-    return seg_eval.run(args, "GEAR", _split_loader, batches, _class_names)
+    return seg_eval.run(args, "GEAR", _split_loader, lambda loader, device: _batches(args, loader, device),
+                        _class_names)
 
 
 if __name__ == "__main__":

@@ -34,17 +34,19 @@ def _class_names(dataset, num_classes):
     return ["background", "defect_type_1", "defect_type_2"][:num_classes]      # reference test_kolektorsdd.py (Subset)
 
 
+def _batches(args, loader, device):
+    """(images, masks, paths) device batches of a raw loader"""
+    from .kolektorsdd_dataset import GpuPreprocess
+    pre = GpuPreprocess((args.image_height, args.image_width), train=False)
+    for images, masks, paths in loader:
+        x, m = pre(images, masks, device=device)
+        yield x, m, paths
+
+
 def main(argv=None):
     args = parse_args(argv)
-
-    def batches(loader, device):
-        from .kolektorsdd_dataset import GpuPreprocess
-        pre = GpuPreprocess((args.image_height, args.image_width), train=False)
-        for images, masks, paths in loader:
-            x, m = pre(images, masks, device=device)
-            yield x, m, paths
-
-    return seg_eval.run(args, "KOLEKTORSDD", _split_loader, batches, _class_names)
+    return seg_eval.run(args, "KOLEKTORSDD", _split_loader, lambda loader, device: _batches(args, loader, device),
+                        _class_names)
 
 
 if __name__ == "__main__":

@@ -1400,6 +1400,143 @@ class RegionOverlapAUC:
         return res
 
 
+def _class_maps(labels, what):
+    """uint8 [N, H, W] device maps of integer label maps; values outside 0..254 become 255 (background)."""
+    _require_cuda(labels)
+    t = labels.detach()
+    if t.dtype != torch.uint8:
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise ValueError(f"{what}: integer label maps, got {t.dtype}")
+        t = t.long()
+        t = torch.where((t >= 0) & (t < 255), t, torch.full_like(t, 255)).to(torch.uint8)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"{what}: [N, H, W] label maps, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _class_regions_error(what, n, h, w, num_classes):
+    return RuntimeError(f"{what}: {n} x {h} x {w} maps of {num_classes} classes are not supported (n < 65536, at most "
+                        "2^31 - 1 pixels, 2..255 classes)")
+
+
+def label_class_regions(labels_u8, num_classes):
+    """Class regions of integer label maps [N, H, W]: a pixel has class c iff its value is c with 1 <= c < num_classes
+    (0 and every value >= num_classes, 255 among them, are background), and a class region is an 8-connected component
+    of pixels of one class in one image.  Returns (region, sizes, counts), DEVICE tensors: region (int32 [N, H, W]) =
+    1 + the smallest linear index y * W + x of the pixel's region, sizes (int32) = the region's pixel count at each of
+    its pixels, both 0 on background; counts (int64 [N, num_classes]) = regions per image and class.  Per class,
+    scipy.ndimage.label(map == c, np.ones((3, 3))) on the device (unet_label_class_regions); does not synchronise."""
+    t = _class_maps(labels_u8, "label_class_regions")
+    n, h, w = t.shape
+    c = int(num_classes)
+    lib = L.lib()
+    nbytes = lib.unet_label_class_regions_workspace(n, h, w, c) if 0 <= c < 2 ** 31 else 0
+    if nbytes == 0:
+        raise _class_regions_error("label_class_regions", n, h, w, num_classes)
+    region = torch.empty((n, h, w), dtype=torch.int32, device=t.device)
+    sizes = torch.empty((n, h, w), dtype=torch.int32, device=t.device)
+    counts = torch.zeros((n, c), dtype=torch.int64, device=t.device)
+    ws = _workspace(nbytes, t.device)
+    L.check(lib.unet_label_class_regions(_ptr(t), n, h, w, c, _ptr(region), _ptr(sizes), _ptr(counts), _ptr(ws),
+                                         ws.numel(), _stream()), "unet_label_class_regions")
+    return region, sizes, counts
+
+
+RECORD_FIELDS = ("image", "class", "root", "size", "hit")
+
+
+class ClassRegionMatcher:
+    """Defect-level matching of predicted against true label maps, accumulated over batches.  Regions are those of
+    ``label_class_regions``; a predicted region is kept iff it has at least ``min_pixels`` pixels.  ``hit`` of a truth
+    region = its pixels whose predicted class is the region's and whose predicted region is kept; ``hit`` of a kept
+    predicted region = its pixels whose truth class is its class (unet_match_class_regions; integers throughout).
+
+    ``update`` labels truth and prediction in one call, matches them and keeps only the batch's two record buffers and
+    its counts; it does not synchronise.  The buffers have to hold one record per pixel when they are made (the device
+    alone knows how many regions there are), so the record counts travel to pinned host memory behind the kernels, and a
+    later ``update`` trims every buffer whose counts have arrived, without waiting.  ``compute`` reads everything back
+    once."""
+
+    def __init__(self, num_classes, min_pixels=1):
+        self.num_classes, self.min_pixels = int(num_classes), int(min_pixels)
+        if not 2 <= self.num_classes <= 255:
+            raise ValueError(f"ClassRegionMatcher: {num_classes} classes, 2..255 are supported")
+        if self.min_pixels < 1:
+            raise ValueError(f"ClassRegionMatcher: min_pixels {min_pixels} is below 1")
+        self.images = 0
+        self._chunks = []          # [truth records, pred records, class counts [2n, C], host counts, event or None]
+
+    def _trim(self, wait):
+        for ch in self._chunks:
+            if ch[4] is None or not (wait or ch[4].query()):
+                continue
+            if wait:
+                ch[4].synchronize()
+            kt, kp = ch[3].tolist()
+            if kt > ch[0].shape[0] or kp > ch[1].shape[0]:
+                raise RuntimeError("ClassRegionMatcher: more records than pixels")      # cannot happen
+            ch[0], ch[1], ch[4] = ch[0][:kt].clone(), ch[1][:kp].clone(), None
+
+    def update(self, pred_labels, truth):
+        """pred_labels / truth: integer device label maps of equal shape [N, H, W] (the uint8 argmax of
+        ``metrics.per_image_stats(..., labels=True)`` and the loaders' masks; values outside 0..254 become 255)."""
+        p = _class_maps(pred_labels, "ClassRegionMatcher.update")
+        t = _class_maps(truth.to(p.device), "ClassRegionMatcher.update")
+        if p.shape != t.shape:
+            raise ValueError("ClassRegionMatcher.update: prediction / truth shapes differ")
+        self._trim(wait=False)
+        n, h, w = p.shape
+        c, dev = self.num_classes, p.device
+        region, sizes, class_counts = label_class_regions(torch.cat([t, p]), c)      # one pass labels both
+        lib = L.lib()
+        nbytes = lib.unet_match_class_regions_workspace(n, h, w, c)
+        if nbytes == 0 or self.images + n >= 2 ** 31:
+            raise _class_regions_error("ClassRegionMatcher.update", n, h, w, c)
+        cap = n * h * w
+        records = [torch.empty((cap, len(RECORD_FIELDS)), dtype=torch.int32, device=dev) for _ in range(2)]
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        ws = _workspace(nbytes, dev)
+        L.check(lib.unet_match_class_regions(_ptr(t), _ptr(region[:n]), _ptr(sizes[:n]), _ptr(p), _ptr(region[n:]),
+                                             _ptr(sizes[n:]), n, h, w, c, self.min_pixels, self.images,
+                                             _ptr(records[0]), _ptr(records[1]), cap, _ptr(counts), _ptr(ws),
+                                             ws.numel(), _stream()), "unet_match_class_regions")
+        host = torch.empty(2, dtype=torch.int64, pin_memory=True)
+        host.copy_(counts, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self._chunks.append([records[0], records[1], class_counts, host, done])
+        self.images += n
+
+    def compute(self):
+        """{"truth", "pred"}: int32 [K, 5] numpy records (image, class, root index y * W + x, size, hit), the image index
+        counted over all updates, sorted by (image, root index); {"truth_counts", "pred_counts"}: int64
+        [images, num_classes] regions per image and class (pred_counts before the min_pixels rule); "images"."""
+        import numpy as np
+        c, f = self.num_classes, len(RECORD_FIELDS)
+        empty = np.zeros((0, f), np.int32)
+        res = {"truth": empty, "pred": empty.copy(), "truth_counts": np.zeros((0, c), np.int64),
+               "pred_counts": np.zeros((0, c), np.int64), "images": self.images}
+        if not self._chunks:
+            return res
+        self._trim(wait=True)
+        parts = [ch[0].reshape(-1) for ch in self._chunks] + [ch[1].reshape(-1) for ch in self._chunks]
+        parts += [ch[2].to(torch.int32).reshape(-1) for ch in self._chunks]          # a count is below 2^31 pixels
+        flat = torch.cat(parts).cpu().numpy()                                       # the one read-back
+        kt = sum(ch[0].shape[0] for ch in self._chunks) * f
+        kp = sum(ch[1].shape[0] for ch in self._chunks) * f
+        for key, rec in (("truth", flat[:kt]), ("pred", flat[kt:kt + kp])):
+            rec = rec.reshape(-1, f)
+            res[key] = np.ascontiguousarray(rec[np.lexsort((rec[:, 2], rec[:, 0]))])
+        at, tc, pc = kt + kp, [], []
+        for ch in self._chunks:
+            n = ch[2].shape[0] // 2
+            both = flat[at:at + 2 * n * c].reshape(2, n, c).astype(np.int64)
+            tc.append(both[0]); pc.append(both[1])
+            at += 2 * n * c
+        res["truth_counts"], res["pred_counts"] = np.concatenate(tc), np.concatenate(pc)
+        return res
+
+
 def preprocess_u8(images_u8, flips=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """uint8 [N, H, W, 3] device batch -> normalised fp32 NCHW (ToTensor + Normalize, optional per-sample horizontal
     flip): /root/reference/src/dataset.py:134-146, src/kolektorsdd_dataset.py:133-150, on the GPU."""
