@@ -320,6 +320,17 @@ size_t unet_bn_relu_pool_max_parts(void);
 int32_t unet_bn_relu_pool_bwd(int32_t dtype, const void* y, const void* dpooled, const void* da_old, int32_t n, int32_t h,
                               int32_t w, int32_t c, const float* scale, const float* shift, const float* mean, void* dz,
                               float* partial, int32_t* n_parts, void* stream);
+/* The same backward without ever storing dz (a streaming producer can afford to form it twice):
+ *   unet_bn_relu_pool_bwd_sums   -> partial / *n_parts exactly as unet_bn_relu_pool_bwd leaves them, nothing else written;
+ *   unet_bn_bwd_premasked(dz = y = dy = NULL) -> dgamma, dbeta and coefs = A, B, K in its workspace;
+ *   unet_bn_relu_pool_bwd_apply  -> forms the same dz again and writes dy = A*dz + B*y + K (dy may alias da_old).
+ * dy, dgamma, dbeta are bit for bit those of unet_bn_relu_pool_bwd + unet_bn_bwd_premasked(dy = dz). */
+int32_t unet_bn_relu_pool_bwd_sums(int32_t dtype, const void* y, const void* dpooled, const void* da_old, int32_t n,
+                                   int32_t h, int32_t w, int32_t c, const float* scale, const float* shift,
+                                   const float* mean, float* partial, int32_t* n_parts, void* stream);
+int32_t unet_bn_relu_pool_bwd_apply(int32_t dtype, const void* y, const void* dpooled, const void* da_old, int32_t n,
+                                    int32_t h, int32_t w, int32_t c, const float* scale, const float* shift,
+                                    const float* coefs, void* dy, void* stream);
 
 /* ---- bilinear x2, align_corners=True (nn.Upsample, src/model.py:48) -------------------- */
 int32_t unet_upsample_bilinear2x_fwd(int32_t dtype, const void* x, int32_t n, int32_t h, int32_t w,
@@ -354,6 +365,20 @@ int32_t unet_head_bnrelu_bwd(int32_t dtype, const void* y, const float* bn_scale
                              int32_t c_in, const float* weight, int32_t c_out, int32_t sigmoid, void* dz,
                              float* dweight, float* dbias, float* bn_partial, int32_t* n_parts, void* workspace,
                              size_t workspace_bytes, void* stream);
+/* The same backward without ever storing dz (it is cheap to form again: c_out planes and the filters):
+ *   unet_head_bnrelu_bwd_sums  -> dweight, dbias, bn_partial / *n_parts exactly as unet_head_bnrelu_bwd leaves them;
+ *   unet_bn_bwd_premasked(dz = y = dy = NULL) -> dgamma, dbeta and coefs = A, B, K in its workspace;
+ *   unet_head_bnrelu_bwd_apply -> forms the same dz again and writes dy = A*dz + B*y + K (NHWC compute dtype).
+ * dy, dgamma, dbeta are bit for bit those of unet_head_bnrelu_bwd + unet_bn_bwd_premasked(dy = dz). */
+int32_t unet_head_bnrelu_bwd_sums(int32_t dtype, const void* y, const float* bn_scale, const float* bn_shift,
+                                  const float* bn_mean, const float* out, const float* dout, int32_t n, int32_t h,
+                                  int32_t w, int32_t c_in, const float* weight, int32_t c_out, int32_t sigmoid,
+                                  float* dweight, float* dbias, float* bn_partial, int32_t* n_parts, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int32_t unet_head_bnrelu_bwd_apply(int32_t dtype, const void* y, const float* bn_scale, const float* bn_shift,
+                                   const float* out, const float* dout, int32_t n, int32_t h, int32_t w, int32_t c_in,
+                                   const float* weight, int32_t c_out, int32_t sigmoid, const float* coefs, void* dy,
+                                   void* stream);
 
 /* ---- loss heads (src/train_utils.py) ----------------------------------------------------- */
 size_t unet_loss_workspace(int64_t elems);

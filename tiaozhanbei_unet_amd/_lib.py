@@ -109,12 +109,16 @@ SIGNATURES = {
     "unet_head_bnrelu_fwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p]),
     "unet_head_bnrelu_max_parts": (_z, []),
     "unet_head_bnrelu_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "unet_head_bnrelu_bwd_sums": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
+    "unet_head_bnrelu_bwd_apply": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
     "unet_maxpool2_fwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p]),
     "unet_maxpool2_bwd": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
     "unet_bn_relu_pool_supported": (_i, [_i, _i]),
     "unet_bn_relu_pool_fwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "unet_bn_relu_pool_max_parts": (_z, []),
     "unet_bn_relu_pool_bwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "unet_bn_relu_pool_bwd_sums": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "unet_bn_relu_pool_bwd_apply": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "unet_upsample_bilinear2x_fwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p]),
     "unet_upsample_bilinear2x_bwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p]),
     "unet_head_fwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p, _i, _i, _p, _p]),

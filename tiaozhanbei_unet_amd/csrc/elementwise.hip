@@ -344,12 +344,19 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const T* __restri
 // this layer and the two BatchNorm-backward sums, in one pass: dz = da * [z > 0] (rounded to T exactly like the
 // unfused kernels round da), part[block][2][C] = (sum dz, sum dz * (y - mean)) -> unet_bn_bwd_premasked.  The window's
 // activations are recomputed from y (rounded like the stored ones), so a itself is not read.
-template <typename T, typename IDX>
+// MODE splits the pass so that dz is never stored: POOL_BWD_SUMS leaves only the partial sums (of the rounded dz the
+// full pass would have stored), POOL_BWD_APPLY -- once the BatchNorm-backward coefficients A, B, K are known
+// (coefs[3][C], bn_finalize_bwd_kernel) -- forms the same dz again and writes dy = A*dz + B*y + K, the expression and
+// rounding of bn_bwd_apply_premasked_kernel, to `dz` (no sums).  One body: the three cannot drift apart.  The output
+// may alias da_old in every mode: a thread reads its window's da_old elements before it writes the same addresses.
+enum { POOL_BWD_FULL = 0, POOL_BWD_SUMS = 1, POOL_BWD_APPLY = 2 };
+template <typename T, typename IDX, int MODE = POOL_BWD_FULL>
 __global__ __launch_bounds__(256) void bn_relu_pool_bwd_kernel(const T* __restrict__ y, const T* __restrict__ dpooled,
                                                                const T* da_old, const float* __restrict__ scale,
                                                                const float* __restrict__ shift,
                                                                const float* __restrict__ mean, T* dz,
-                                                               float* __restrict__ part, int N, int H, int W, int C) {
+                                                               float* __restrict__ part, int N, int H, int W, int C,
+                                                               const float* __restrict__ coefs = nullptr) {
   constexpr int PIECE = ET<T>::PIECE;
   typedef IDX idx_t;
   __shared__ float red[2][256][PIECE + 1];
@@ -357,11 +364,15 @@ __global__ __launch_bounds__(256) void bn_relu_pool_bwd_kernel(const T* __restri
   const int WH = (H + 1) / 2, WW = (W + 1) / 2;
   const idx_t total = (idx_t)N * WH * WW * G;
   const int g = threadIdx.x % G;
+  constexpr bool SUM = MODE != POOL_BWD_APPLY, APPLY = MODE == POOL_BWD_APPLY;
   float sc[PIECE], sh[PIECE], mu[PIECE], s0[PIECE], s1[PIECE];
+  float cA[APPLY ? PIECE : 1], cB[APPLY ? PIECE : 1], cK[APPLY ? PIECE : 1];
 #pragma unroll
   for (int j = 0; j < PIECE; ++j) {
-    sc[j] = scale[g * PIECE + j]; sh[j] = shift[g * PIECE + j]; mu[j] = mean[g * PIECE + j];
+    sc[j] = scale[g * PIECE + j]; sh[j] = shift[g * PIECE + j];
+    mu[j] = SUM ? mean[g * PIECE + j] : 0.f;
     s0[j] = 0.f; s1[j] = 0.f;
+    if constexpr (APPLY) { cA[j] = coefs[g * PIECE + j]; cB[j] = coefs[C + g * PIECE + j]; cK[j] = coefs[2 * C + g * PIECE + j]; }
   }
   // The window walk advances by a fixed stride of windows per iteration: its (image, row, column) decomposition is
   // computed once and carried (no divisions in the loop; the element-wise work is what limits this pass).
@@ -414,15 +425,21 @@ __global__ __launch_bounds__(256) void bn_relu_pool_bwd_kernel(const T* __restri
           const float d = f[k] ? od[k][j] + gr[j] : od[k][j];
           const float da = ET<T>::to_f(ET<T>::from_f(d));
           const float v = z[k] > 0.f ? da : 0.f;
-          od[k][j] = v;
-          s0[j] += v;
-          s1[j] = fmaf(v, yv[k][j] - mu[j], s1[j]);
+          if constexpr (SUM) {
+            od[k][j] = v;
+            s0[j] += v;
+            s1[j] = fmaf(v, yv[k][j] - mu[j], s1[j]);
+          } else {
+            od[k][j] = fmaf(cA[j], v, fmaf(cB[j], yv[k][j], cK[j]));
+          }
         }
       }
-      Vec<T>::store(dz + base, od[0]);
-      Vec<T>::store(dz + o1, od[1]);
-      Vec<T>::store(dz + o2, od[2]);
-      Vec<T>::store(dz + o3, od[3]);
+      if constexpr (MODE != POOL_BWD_SUMS) {
+        Vec<T>::store(dz + base, od[0]);
+        Vec<T>::store(dz + o1, od[1]);
+        Vec<T>::store(dz + o2, od[2]);
+        Vec<T>::store(dz + o3, od[3]);
+      }
     } else {
     float yv[4][PIECE], av[4][PIECE], gr[PIECE];
     bool on[4][PIECE];
@@ -464,11 +481,15 @@ __global__ __launch_bounds__(256) void bn_relu_pool_bwd_kernel(const T* __restri
         }
         const float da = ET<T>::to_f(ET<T>::from_f(d[j]));                 // da as the unfused kernels store it
         const float v = ET<T>::to_f(ET<T>::from_f(on[k][j] ? da : 0.f));   // dz as stored
-        d[j] = v;
-        s0[j] += v;
-        s1[j] = fmaf(v, yv[k][j] - mu[j], s1[j]);
+        if constexpr (SUM) {
+          d[j] = v;
+          s0[j] += v;
+          s1[j] = fmaf(v, yv[k][j] - mu[j], s1[j]);
+        } else {
+          d[j] = fmaf(cA[j], v, fmaf(cB[j], yv[k][j], cK[j]));
+        }
       }
-      Vec<T>::store(dz + o, d);
+      if constexpr (MODE != POOL_BWD_SUMS) Vec<T>::store(dz + o, d);
     }
     }
     // next window of this thread
@@ -478,6 +499,7 @@ __global__ __launch_bounds__(256) void bn_relu_pool_bwd_kernel(const T* __restri
     if (oy >= WH) { oy -= WH; ++n; }
     n += sn;
   }
+  if constexpr (APPLY) return;
   // block partial: the 256 / G threads of a channel group, in thread order
 #pragma unroll
   for (int j = 0; j < PIECE; ++j) { red[0][threadIdx.x][j] = s0[j]; red[1][threadIdx.x][j] = s1[j]; }
@@ -741,13 +763,18 @@ extern "C" int32_t unet_bn_relu_pool_fwd(int32_t dtype, const void* y, int32_t n
 namespace { constexpr int POOL_BWD_MAX_BLOCKS = 256 * 8; }     // = the partial-sum capacity callers allocate
 extern "C" size_t unet_bn_relu_pool_max_parts(void) { return POOL_BWD_MAX_BLOCKS; }
 
-extern "C" int32_t unet_bn_relu_pool_bwd(int32_t dtype, const void* y, const void* dpooled, const void* da_old, int32_t n,
-                                         int32_t h, int32_t w, int32_t c, const float* scale, const float* shift,
-                                         const float* mean, void* dz, float* partial, int32_t* n_parts, void* stream) {
-  UNET_REQUIRE(y && dpooled && scale && shift && mean && dz && partial && n_parts, UNET_ERR_BAD_ARG,
-               "unet_bn_relu_pool_bwd: null pointer");
+// MODE: POOL_BWD_FULL / _SUMS / _APPLY of bn_relu_pool_bwd_kernel.  The grid is the same in every mode -- the partial
+// rows of _SUMS are those of _FULL, and _APPLY walks the windows the same way.
+template <int MODE>
+static int32_t bn_relu_pool_bwd_impl(const char* what, int32_t dtype, const void* y, const void* dpooled, const void* da_old,
+                                     int32_t n, int32_t h, int32_t w, int32_t c, const float* scale, const float* shift,
+                                     const float* mean, void* dst, float* partial, int32_t* n_parts, const float* coefs,
+                                     void* stream) {
+  constexpr bool SUM = MODE != POOL_BWD_APPLY;
+  UNET_REQUIRE(y && dpooled && scale && shift && (dst || MODE == POOL_BWD_SUMS) &&
+               (SUM ? (mean && partial && n_parts) : coefs != nullptr), UNET_ERR_BAD_ARG, "%s: null pointer", what);
   UNET_REQUIRE(n > 0 && h >= 2 && w >= 2 && unet_bn_relu_pool_supported(dtype, c), UNET_ERR_UNSUPPORTED,
-               "unet_bn_relu_pool_bwd: c=%d h=%d w=%d", c, h, w);
+               "%s: c=%d h=%d w=%d", what, c, h, w);
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof(UNET_K_POOL, 0.0, s, "bn_relu_pool_bwd_kernel");
   const long long total = (long long)n * ((h + 1) / 2) * ((w + 1) / 2) * (c / (dtype == UNET_BF16 ? 8 : 4));
@@ -755,17 +782,42 @@ extern "C" int32_t unet_bn_relu_pool_bwd(int32_t dtype, const void* y, const voi
   const bool small = (long long)n * h * w * c < 0x7FFFFFFFLL;
   if (dtype == UNET_BF16) {
     if (small)
-      hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<bf16_t, int>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)y,
-                         (const bf16_t*)dpooled, (const bf16_t*)da_old, scale, shift, mean, (bf16_t*)dz, partial, n, h, w, c);
+      hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<bf16_t, int, MODE>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)y,
+                         (const bf16_t*)dpooled, (const bf16_t*)da_old, scale, shift, mean, (bf16_t*)dst, partial, n, h, w, c,
+                         coefs);
     else
-      hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<bf16_t, long long>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)y,
-                         (const bf16_t*)dpooled, (const bf16_t*)da_old, scale, shift, mean, (bf16_t*)dz, partial, n, h, w, c);
+      hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<bf16_t, long long, MODE>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)y,
+                         (const bf16_t*)dpooled, (const bf16_t*)da_old, scale, shift, mean, (bf16_t*)dst, partial, n, h, w, c,
+                         coefs);
   } else {
-    hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<float, long long>), dim3(blocks), dim3(256), 0, s, (const float*)y,
-                       (const float*)dpooled, (const float*)da_old, scale, shift, mean, (float*)dz, partial, n, h, w, c);
+    hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<float, long long, MODE>), dim3(blocks), dim3(256), 0, s, (const float*)y,
+                       (const float*)dpooled, (const float*)da_old, scale, shift, mean, (float*)dst, partial, n, h, w, c,
+                       coefs);
   }
-  *n_parts = blocks;
+  if (SUM) *n_parts = blocks;
   return unet_check_launch("bn_relu_pool_bwd_kernel");
+}
+
+extern "C" int32_t unet_bn_relu_pool_bwd(int32_t dtype, const void* y, const void* dpooled, const void* da_old, int32_t n,
+                                         int32_t h, int32_t w, int32_t c, const float* scale, const float* shift,
+                                         const float* mean, void* dz, float* partial, int32_t* n_parts, void* stream) {
+  return bn_relu_pool_bwd_impl<POOL_BWD_FULL>("unet_bn_relu_pool_bwd", dtype, y, dpooled, da_old, n, h, w, c, scale, shift,
+                                              mean, dz, partial, n_parts, nullptr, stream);
+}
+
+extern "C" int32_t unet_bn_relu_pool_bwd_sums(int32_t dtype, const void* y, const void* dpooled, const void* da_old,
+                                              int32_t n, int32_t h, int32_t w, int32_t c, const float* scale,
+                                              const float* shift, const float* mean, float* partial, int32_t* n_parts,
+                                              void* stream) {
+  return bn_relu_pool_bwd_impl<POOL_BWD_SUMS>("unet_bn_relu_pool_bwd_sums", dtype, y, dpooled, da_old, n, h, w, c, scale,
+                                              shift, mean, nullptr, partial, n_parts, nullptr, stream);
+}
+
+extern "C" int32_t unet_bn_relu_pool_bwd_apply(int32_t dtype, const void* y, const void* dpooled, const void* da_old,
+                                               int32_t n, int32_t h, int32_t w, int32_t c, const float* scale,
+                                               const float* shift, const float* coefs, void* dy, void* stream) {
+  return bn_relu_pool_bwd_impl<POOL_BWD_APPLY>("unet_bn_relu_pool_bwd_apply", dtype, y, dpooled, da_old, n, h, w, c, scale,
+                                               shift, nullptr, dy, nullptr, nullptr, coefs, stream);
 }
 
 extern "C" int32_t unet_upsample_bilinear2x_fwd(int32_t dtype, const void* x, int32_t n, int32_t h, int32_t w,

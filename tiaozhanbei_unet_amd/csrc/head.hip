@@ -25,6 +25,35 @@ __device__ __forceinline__ void split_pixel(long long p, long long hw, long long
   }
 }
 
+// dlogit of one (pixel, filter) plane element: the gradient at the 1x1 filter's output (through the sigmoid when the
+// head ends in one)
+__device__ __forceinline__ float head_dlogit(const float* __restrict__ dout, const float* __restrict__ out,
+                                             long long idx, int sigm) {
+  float d = dout[idx];
+  if (sigm) { const float o = out[idx]; d *= o * (1.f - o); }
+  return d;
+}
+
+// Gradient w.r.t. one input element of the head: sum over the filters, in filter order.  wr: this channel's column of
+// the CO filters, WS floats apart (a register array of the caller).
+template <int CO, int WS>
+__device__ __forceinline__ float head_dx(const float (&ds)[CO], const float* wr) {
+  float t = 0.f;
+#pragma unroll
+  for (int co = 0; co < CO; ++co) t = fmaf(ds[co], wr[co * WS], t);
+  return t;
+}
+
+// The same gradient behind the ReLU of a conv-BatchNorm-ReLU layer whose RAW output yv the head reads: the mask of
+// z = fma(yv, scale, shift), rounded to T -- dz as head_bwd_kernel<BN> / head_bwd_tile_kernel<BN> store it.  The ONE
+// statement of this value: the kernels that store it, the ones that only sum it (STORE = false) and
+// head_bnrelu_bwd_apply_kernel, which forms it again, all call this function.
+template <typename T, int CO, int WS>
+__device__ __forceinline__ float head_dz(const float (&ds)[CO], const float* wr, float yv, float scale, float shift) {
+  const float t = head_dx<CO, WS>(ds, wr);
+  return ET<T>::to_f(ET<T>::from_f(fmaf(yv, scale, shift) > 0.f ? t : 0.f));
+}
+
 // A wave works on 64 CONSECUTIVE pixels per iteration.  Phase 1: TPP lanes cooperate on a pixel (16 B of channels
 // each, a pixel's NHWC row is one contiguous read / write), S = TPP sub-steps cover the 64 pixels and their loads
 // are all in flight together.  Phase 2: lane = pixel, so the NCHW fp32 planes (out, dout) are read and written as
@@ -149,7 +178,9 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ x, 
 // the gradient w.r.t. the activation gets the ReLU mask at once (dx = dz = da * [fma(y, scale, shift) > 0], rounded to
 // T) and the two per-channel sums the BatchNorm backward needs -- sum dz and sum dz * (y - mean) of the ROUNDED dz --
 // leave as one ordered partial per block (bn_part[block][2][Cin]): no separate reduction pass over (y, da).
-template <typename T, int TPP, int CO, bool BN = false>
+// STORE = false (BN only): everything but the store of dz -- the sums are those of the rounded values it would have
+// stored; head_bnrelu_bwd_apply_kernel forms dz again once the BatchNorm-backward coefficients are known.
+template <typename T, int TPP, int CO, bool BN = false, bool STORE = true>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const T* __restrict__ x, const float* __restrict__ out,
                                                        const float* __restrict__ dout, long long pixels,
                                                        long long hw, int Cin, const float* __restrict__ w,
@@ -198,8 +229,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const T* __restrict__ x, 
         split_pixel(p, hw, n, q);
 #pragma unroll
         for (int co = 0; co < CO; ++co) {
-          float d = dout[(n * CO + co) * hw + q];
-          if (sigm) { const float o = out[(n * CO + co) * hw + q]; d *= o * (1.f - o); }
+          const float d = head_dlogit(dout, out, (n * CO + co) * hw + q, sigm);
           dl[co] = d;
           dbacc[co] += d;
         }
@@ -222,37 +252,28 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const T* __restrict__ x, 
         float ds[CO], d[PIECE];
 #pragma unroll
         for (int co = 0; co < CO; ++co) ds[co] = __shfl(dl[co], s * PPW + sub);
-#pragma unroll
-        for (int j = 0; j < PIECE; ++j) d[j] = 0.f;
         float av[PIECE];                       // the activation the 1x1 filter saw
-        bool on[PIECE];
 #pragma unroll
         for (int j = 0; j < PIECE; ++j) {
-          if constexpr (BN) {
-            const float z = fmaf(v[i][j], sc[j], sh[j]);
-            on[j] = z > 0.f;
-            av[j] = ET<T>::to_f(ET<T>::from_f(fmaxf(z, 0.f)));
-          } else {
-            on[j] = true;
-            av[j] = v[i][j];
-          }
+          if constexpr (BN) av[j] = ET<T>::to_f(ET<T>::from_f(fmaxf(fmaf(v[i][j], sc[j], sh[j]), 0.f)));
+          else av[j] = v[i][j];
         }
 #pragma unroll
         for (int co = 0; co < CO; ++co)
 #pragma unroll
-          for (int j = 0; j < PIECE; ++j) {
-            d[j] = fmaf(ds[co], wr[co][j], d[j]);
-            dwacc[co][j] = fmaf(ds[co], av[j], dwacc[co][j]);        // ds is 0 past the end
-          }
-        if constexpr (BN) {
+          for (int j = 0; j < PIECE; ++j) dwacc[co][j] = fmaf(ds[co], av[j], dwacc[co][j]);        // ds is 0 past the end
 #pragma unroll
-          for (int j = 0; j < PIECE; ++j) {
-            d[j] = ET<T>::to_f(ET<T>::from_f(on[j] ? d[j] : 0.f));     // dz as stored
+        for (int j = 0; j < PIECE; ++j) {
+          if constexpr (BN) {
+            d[j] = head_dz<T, CO, PIECE>(ds, &wr[0][j], v[i][j], sc[j], sh[j]);     // dz as stored
             bs0[j] += d[j];
             bs1[j] = fmaf(d[j], v[i][j] - mu[j], bs1[j]);
+          } else {
+            d[j] = head_dx<CO, PIECE>(ds, &wr[0][j]);
           }
         }
-        if (p < pixels) Vec<T>::store(dx + p * Cin + g * PIECE, d);
+        if constexpr (STORE)
+          if (p < pixels) Vec<T>::store(dx + p * Cin + g * PIECE, d);
       }
     }
   }
@@ -332,8 +353,9 @@ __global__ __launch_bounds__(256) void head_bwd_finalize_kernel(const float* __r
 //      channels (2*CO + 4 accumulators) and writes dx back over the tile in place;
 //   3. the tile goes LDS -> global with eight coalesced 16-byte stores per lane.
 // ~50 VGPRs, 33 KB LDS per block: four blocks per CU keep the memory pipes full.  Same outputs and partial-sum
-// formats as head_bwd_kernel (the finalize kernels are shared).
-template <typename T, int CO, bool BN>
+// formats as head_bwd_kernel (the finalize kernels are shared).  STORE = false: see head_bwd_kernel -- the tile stays
+// as loaded and step 3 does not exist.
+template <typename T, int CO, bool BN, bool STORE = true>
 __global__ __launch_bounds__(256) void head_bwd_tile_kernel(const T* __restrict__ x, const float* __restrict__ out,
                                                             const float* __restrict__ dout, long long pixels,
                                                             long long hw, const float* __restrict__ w, int sigm,
@@ -390,8 +412,7 @@ __global__ __launch_bounds__(256) void head_bwd_tile_kernel(const T* __restrict_
         split_pixel(p, hw, n, q);
 #pragma unroll
         for (int co = 0; co < CO; ++co) {
-          float d = dout[(n * CO + co) * hw + q];
-          if (sigm) { const float o = out[(n * CO + co) * hw + q]; d *= o * (1.f - o); }
+          const float d = head_dlogit(dout, out, (n * CO + co) * hw + q, sigm);
           dl[co] = d;
           dbacc[co] += d;
         }
@@ -423,26 +444,19 @@ __global__ __launch_bounds__(256) void head_bwd_tile_kernel(const T* __restrict_
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         float av = v[j];
-        bool on = true;
-        if constexpr (BN) {
-          const float z = fmaf(v[j], sc[j], sh[j]);
-          on = z > 0.f;
-          av = ET<T>::to_f(ET<T>::from_f(fmaxf(z, 0.f)));       // the activation the 1x1 filter saw
-        }
-        float t = 0.f;
+        if constexpr (BN) av = ET<T>::to_f(ET<T>::from_f(fmaxf(fmaf(v[j], sc[j], sh[j]), 0.f)));   // the activation the 1x1 filter saw
 #pragma unroll
-        for (int co = 0; co < CO; ++co) {
-          t = fmaf(ds[co], wr[co][j], t);
-          dwacc[co][j] = fmaf(ds[co], av, dwacc[co][j]);        // a pixel past the end has ds = 0
-        }
+        for (int co = 0; co < CO; ++co) dwacc[co][j] = fmaf(ds[co], av, dwacc[co][j]);        // a pixel past the end has ds = 0
         if constexpr (BN) {
-          t = ET<T>::to_f(ET<T>::from_f(on ? t : 0.f));         // dz as stored
-          bs0[j] += t;
-          bs1[j] = fmaf(t, v[j] - mu[j], bs1[j]);
+          d[j] = head_dz<T, CO, 2>(ds, &wr[0][j], v[j], sc[j], sh[j]);                    // dz as stored
+          bs0[j] += d[j];
+          bs1[j] = fmaf(d[j], v[j] - mu[j], bs1[j]);
+        } else {
+          d[j] = head_dx<CO, 2>(ds, &wr[0][j]);
         }
-        d[j] = t;
       }
-      if constexpr (sizeof(T) == 2) {
+      if constexpr (!STORE) {
+      } else if constexpr (sizeof(T) == 2) {
         const bf16_t d0 = (bf16_t)d[0], d1 = (bf16_t)d[1];
         const unsigned u = (unsigned)__builtin_bit_cast(unsigned short, d0) | ((unsigned)__builtin_bit_cast(unsigned short, d1) << 16);
         *reinterpret_cast<unsigned*>(tile + p * ROW + c2 * 4) = u;
@@ -454,15 +468,17 @@ __global__ __launch_bounds__(256) void head_bwd_tile_kernel(const T* __restrict_
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     // ---- 3. tile -> global
+    if constexpr (STORE) {
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int q = i * 64 + lane;
-      const long long p = base + q / (ROW / 16);
-      const u32x4 r = *reinterpret_cast<const u32x4*>(tile + q * 16);
-      if (p < pixels) *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(dx) + base * ROW + (size_t)q * 16) = r;
+      for (int i = 0; i < NLD; ++i) {
+        const int q = i * 64 + lane;
+        const long long p = base + q / (ROW / 16);
+        const u32x4 r = *reinterpret_cast<const u32x4*>(tile + q * 16);
+        if (p < pixels) *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(dx) + base * ROW + (size_t)q * 16) = r;
+      }
+      __builtin_amdgcn_wave_barrier();                 // (the next tile's LDS writes must not pass these reads)
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    __builtin_amdgcn_wave_barrier();                 // (the next tile's LDS writes must not pass these reads)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
   // ---- block partials.  dW / BatchNorm sums: the two parity halves hold the same channels; db: lane = pixel partials
 #pragma unroll
@@ -501,18 +517,88 @@ __global__ __launch_bounds__(256) void head_bwd_tile_kernel(const T* __restrict_
   }
 }
 
-template <typename T, int CO, bool BN>
+template <typename T, int CO, bool BN, bool STORE = true>
 int32_t launch_head_bwd_tile(const void* x, const float* out, const float* dout, long long pixels, long long hw,
                              const float* w, int sigm, void* dx, float* part, const float* bn_scale,
                              const float* bn_shift, const float* bn_mean, float* bn_part, int nb, hipStream_t s) {
   constexpr int TILE = 64 * 64 * ET<T>::ES;
   constexpr int LDS = 4 * (TILE + CO * 256);
   static_assert(LDS >= 4 * (CO * 65 + 128) * 4, "reduction scratch fits the tile area");
-  auto kern = head_bwd_tile_kernel<T, CO, BN>;
+  auto kern = head_bwd_tile_kernel<T, CO, BN, STORE>;
   unet_set_max_lds(reinterpret_cast<const void*>(kern), LDS);
   hipLaunchKernelGGL(kern, dim3(nb), dim3(256), LDS, s, (const T*)x, out, dout, pixels, hw, w, sigm, (T*)dx, part,
                      bn_scale, bn_shift, bn_mean, bn_part);
   return unet_check_launch("head_bwd_tile_kernel");
+}
+
+// Phase 2 of the head's conv-BatchNorm-ReLU backward when phase 1 only summed (STORE = false): with the BatchNorm-
+// backward coefficients A, B, K known (coefs[3][Cin], bn_finalize_bwd_kernel), dz is formed again from the NCHW fp32
+// planes and the filters in registers -- head_dz, the value phase 1 summed -- and dy = A*dz + B*y + K leaves in the
+// expression and rounding of bn_bwd_apply_premasked_kernel: the layer tensor dz is never written nor read back.
+// head_bwd_kernel's layout: TPP lanes share a pixel (16 B of channels each, fixed per lane), a wave takes 64 consecutive
+// pixels per iteration; lane = pixel reads the planes coalesced, wave shuffles hand each pixel's dlogits to its lanes.
+template <typename T, int TPP, int CO>
+__global__ __launch_bounds__(256) void head_bnrelu_bwd_apply_kernel(const T* __restrict__ y, const float* __restrict__ out,
+                                                                    const float* __restrict__ dout, long long pixels,
+                                                                    long long hw, int Cin, const float* __restrict__ w,
+                                                                    int sigm, const float* __restrict__ bn_scale,
+                                                                    const float* __restrict__ bn_shift,
+                                                                    const float* __restrict__ coefs, T* __restrict__ dy) {
+  constexpr int PIECE = ET<T>::PIECE;
+  constexpr int PPW = 64 / TPP, S = TPP;
+  constexpr int SB = S < 8 ? S : 8;              // sub-steps whose loads are in flight together
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane % TPP, sub = lane / TPP;
+  float wr[CO][PIECE], sc[PIECE], sh[PIECE], A[PIECE], B[PIECE], K[PIECE];
+#pragma unroll
+  for (int j = 0; j < PIECE; ++j) {
+    const int ch = g * PIECE + j;
+#pragma unroll
+    for (int co = 0; co < CO; ++co) wr[co][j] = w[co * Cin + ch];
+    sc[j] = bn_scale[ch]; sh[j] = bn_shift[ch];
+    A[j] = coefs[ch]; B[j] = coefs[Cin + ch]; K[j] = coefs[2 * Cin + ch];
+  }
+  const long long nw = (long long)gridDim.x * 4;
+  for (long long c = blockIdx.x * 4LL + wave; c * 64 < pixels; c += nw) {
+    const long long base = c * 64;
+    float dl[CO];
+#pragma unroll
+    for (int co = 0; co < CO; ++co) dl[co] = 0.f;
+    {
+      const long long p = base + lane;
+      if (p < pixels) {
+        long long n, q;
+        split_pixel(p, hw, n, q);
+#pragma unroll
+        for (int co = 0; co < CO; ++co) dl[co] = head_dlogit(dout, out, (n * CO + co) * hw + q, sigm);
+      }
+    }
+#pragma unroll 1
+    for (int s0 = 0; s0 < S; s0 += SB) {
+      u32x4 raw[SB];                             // the pieces stay packed until their turn (4 registers each, not PIECE)
+#pragma unroll
+      for (int i = 0; i < SB; ++i) {
+        const long long p = base + (s0 + i) * PPW + sub;
+        raw[i] = u32x4{0u, 0u, 0u, 0u};
+        if (p < pixels) raw[i] = *reinterpret_cast<const u32x4*>(y + p * Cin + g * PIECE);
+      }
+#pragma unroll
+      for (int i = 0; i < SB; ++i) {
+        const int s = s0 + i;
+        const long long p = base + s * PPW + sub;
+        float ds[CO], r[PIECE], v[PIECE];
+        Vec<T>::load(reinterpret_cast<const T*>(&raw[i]), v);
+#pragma unroll
+        for (int co = 0; co < CO; ++co) ds[co] = __shfl(dl[co], s * PPW + sub);
+#pragma unroll
+        for (int j = 0; j < PIECE; ++j) {
+          const float dz = head_dz<T, CO, PIECE>(ds, &wr[0][j], v[j], sc[j], sh[j]);
+          r[j] = fmaf(A[j], dz, fmaf(B[j], v[j], K[j]));
+        }
+        if (p < pixels) Vec<T>::store(dy + p * Cin + g * PIECE, r);     // 16 bytes
+      }
+    }
+  }
 }
 
 inline int head_blocks(long long pixels, int tpp) {
@@ -649,13 +735,15 @@ extern "C" int32_t unet_head_bnrelu_fwd(int32_t dtype, const void* y, int32_t n,
 
 extern "C" size_t unet_head_bnrelu_max_parts(void) { return 1024; }
 
-extern "C" int32_t unet_head_bnrelu_bwd(int32_t dtype, const void* y, const float* bn_scale, const float* bn_shift,
-                                        const float* bn_mean, const float* out, const float* dout, int32_t n, int32_t h,
-                                        int32_t w, int32_t c_in, const float* weight, int32_t c_out, int32_t sigmoid,
-                                        void* dz, float* dweight, float* dbias, float* bn_partial, int32_t* n_parts,
-                                        void* workspace, size_t workspace_bytes, void* stream) {
-  UNET_REQUIRE(y && bn_scale && bn_shift && bn_mean && dout && weight && dz && dweight && dbias && bn_partial && n_parts &&
-               workspace && (out || !sigmoid), UNET_ERR_BAD_ARG, "unet_head_bnrelu_bwd: null pointer");
+// STORE = false: unet_head_bnrelu_bwd_sums (dz is not written and may be NULL)
+template <bool STORE>
+static int32_t head_bnrelu_bwd_impl(int32_t dtype, const void* y, const float* bn_scale, const float* bn_shift,
+                                    const float* bn_mean, const float* out, const float* dout, int32_t n, int32_t h,
+                                    int32_t w, int32_t c_in, const float* weight, int32_t c_out, int32_t sigmoid,
+                                    void* dz, float* dweight, float* dbias, float* bn_partial, int32_t* n_parts,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  UNET_REQUIRE(y && bn_scale && bn_shift && bn_mean && dout && weight && (dz || !STORE) && dweight && dbias && bn_partial &&
+               n_parts && workspace && (out || !sigmoid), UNET_ERR_BAD_ARG, "unet_head_bnrelu_bwd: null pointer");
   UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_head_bnrelu_bwd: bad dims");
   UNET_REQUIRE(c_out >= 1 && c_out <= MAXCO && (c_in == 32 || c_in == 64 || c_in == 128), UNET_ERR_UNSUPPORTED,
                "unet_head_bnrelu_bwd: %d -> %d channels unsupported", c_in, c_out);
@@ -669,23 +757,23 @@ extern "C" int32_t unet_head_bnrelu_bwd(int32_t dtype, const void* y, const floa
     nb = head_blocks(pixels, 8);
     int32_t rc = UNET_OK;
     if (dtype == UNET_BF16) {
-      HEAD_CO_SWITCH(rc = (launch_head_bwd_tile<bf16_t, CO, true>(y, out, dout, pixels, hw, weight, sigmoid, dz, (float*)workspace,
+      HEAD_CO_SWITCH(rc = (launch_head_bwd_tile<bf16_t, CO, true, STORE>(y, out, dout, pixels, hw, weight, sigmoid, dz, (float*)workspace,
                                                                 bn_scale, bn_shift, bn_mean, bn_partial, nb, s)));
     } else {
-      HEAD_CO_SWITCH(rc = (launch_head_bwd_tile<float, CO, true>(y, out, dout, pixels, hw, weight, sigmoid, dz, (float*)workspace,
+      HEAD_CO_SWITCH(rc = (launch_head_bwd_tile<float, CO, true, STORE>(y, out, dout, pixels, hw, weight, sigmoid, dz, (float*)workspace,
                                                                bn_scale, bn_shift, bn_mean, bn_partial, nb, s)));
     }
     if (rc) return rc;
   } else if (dtype == UNET_BF16) {
     const int tpp = tpp_of<bf16_t>(c_in);
     nb = head_blocks(pixels, tpp);
-    HEAD_TPP_SWITCH(bf16_t, tpp, hipLaunchKernelGGL((head_bwd_kernel<bf16_t, TPP, CO, true>), dim3(nb), dim3(256), 0, s,
+    HEAD_TPP_SWITCH(bf16_t, tpp, hipLaunchKernelGGL((head_bwd_kernel<bf16_t, TPP, CO, true, STORE>), dim3(nb), dim3(256), 0, s,
                     (const bf16_t*)y, out, dout, pixels, hw, c_in, weight, sigmoid, (bf16_t*)dz, (float*)workspace,
                     bn_scale, bn_shift, bn_mean, bn_partial));
   } else if (dtype == UNET_F32) {
     const int tpp = tpp_of<float>(c_in);
     nb = head_blocks(pixels, tpp);
-    HEAD_TPP_SWITCH(float, tpp, hipLaunchKernelGGL((head_bwd_kernel<float, TPP, CO, true>), dim3(nb), dim3(256), 0, s,
+    HEAD_TPP_SWITCH(float, tpp, hipLaunchKernelGGL((head_bwd_kernel<float, TPP, CO, true, STORE>), dim3(nb), dim3(256), 0, s,
                     (const float*)y, out, dout, pixels, hw, c_in, weight, sigmoid, (float*)dz, (float*)workspace,
                     bn_scale, bn_shift, bn_mean, bn_partial));
   } else {
@@ -698,4 +786,53 @@ extern "C" int32_t unet_head_bnrelu_bwd(int32_t dtype, const void* y, const floa
   hipLaunchKernelGGL(head_bwd_finalize_kernel, dim3(cdiv(c_out * (c_in + 1), 4)), dim3(256), 0, s,
                      (const float*)workspace, nb, c_out, c_in, dweight, dbias);
   return unet_check_launch("head_bwd_finalize_kernel");
+}
+
+extern "C" int32_t unet_head_bnrelu_bwd(int32_t dtype, const void* y, const float* bn_scale, const float* bn_shift,
+                                        const float* bn_mean, const float* out, const float* dout, int32_t n, int32_t h,
+                                        int32_t w, int32_t c_in, const float* weight, int32_t c_out, int32_t sigmoid,
+                                        void* dz, float* dweight, float* dbias, float* bn_partial, int32_t* n_parts,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  return head_bnrelu_bwd_impl<true>(dtype, y, bn_scale, bn_shift, bn_mean, out, dout, n, h, w, c_in, weight, c_out, sigmoid,
+                                    dz, dweight, dbias, bn_partial, n_parts, workspace, workspace_bytes, stream);
+}
+
+// ---- the same backward with dz never stored: sums, then (after unet_bn_bwd_premasked(dy = NULL)) dy in one pass ----
+extern "C" int32_t unet_head_bnrelu_bwd_sums(int32_t dtype, const void* y, const float* bn_scale, const float* bn_shift,
+                                             const float* bn_mean, const float* out, const float* dout, int32_t n,
+                                             int32_t h, int32_t w, int32_t c_in, const float* weight, int32_t c_out,
+                                             int32_t sigmoid, float* dweight, float* dbias, float* bn_partial,
+                                             int32_t* n_parts, void* workspace, size_t workspace_bytes, void* stream) {
+  return head_bnrelu_bwd_impl<false>(dtype, y, bn_scale, bn_shift, bn_mean, out, dout, n, h, w, c_in, weight, c_out,
+                                     sigmoid, nullptr, dweight, dbias, bn_partial, n_parts, workspace, workspace_bytes,
+                                     stream);
+}
+
+extern "C" int32_t unet_head_bnrelu_bwd_apply(int32_t dtype, const void* y, const float* bn_scale, const float* bn_shift,
+                                              const float* out, const float* dout, int32_t n, int32_t h, int32_t w,
+                                              int32_t c_in, const float* weight, int32_t c_out, int32_t sigmoid,
+                                              const float* coefs, void* dy, void* stream) {
+  UNET_REQUIRE(y && bn_scale && bn_shift && dout && weight && coefs && dy && (out || !sigmoid), UNET_ERR_BAD_ARG,
+               "unet_head_bnrelu_bwd_apply: null pointer");
+  UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_head_bnrelu_bwd_apply: bad dims");
+  UNET_REQUIRE(c_out >= 1 && c_out <= MAXCO && (c_in == 32 || c_in == 64 || c_in == 128), UNET_ERR_UNSUPPORTED,
+               "unet_head_bnrelu_bwd_apply: %d -> %d channels unsupported", c_in, c_out);
+  hipStream_t s = (hipStream_t)stream;
+  const long long pixels = (long long)n * h * w, hw = (long long)h * w;
+  ProfScope prof(UNET_K_HEAD, 2.0 * pixels * c_in * c_out, s);
+  const long long want = cdiv64(pixels, 256);                              // a block takes 256 pixels per iteration
+  const int nb = (int)(want < 2048 ? want : 2048);
+  if (dtype == UNET_BF16) {
+    const int tpp = tpp_of<bf16_t>(c_in);
+    HEAD_TPP_SWITCH(bf16_t, tpp, hipLaunchKernelGGL((head_bnrelu_bwd_apply_kernel<bf16_t, TPP, CO>), dim3(nb), dim3(256), 0, s,
+                    (const bf16_t*)y, out, dout, pixels, hw, c_in, weight, sigmoid, bn_scale, bn_shift, coefs, (bf16_t*)dy));
+  } else if (dtype == UNET_F32) {
+    const int tpp = tpp_of<float>(c_in);
+    HEAD_TPP_SWITCH(float, tpp, hipLaunchKernelGGL((head_bnrelu_bwd_apply_kernel<float, TPP, CO>), dim3(nb), dim3(256), 0, s,
+                    (const float*)y, out, dout, pixels, hw, c_in, weight, sigmoid, bn_scale, bn_shift, coefs, (float*)dy));
+  } else {
+    unet_set_error("unet_head_bnrelu_bwd_apply: dtype %d", dtype);
+    return UNET_ERR_BAD_ARG;
+  }
+  return unet_check_launch("head_bnrelu_bwd_apply_kernel");
 }

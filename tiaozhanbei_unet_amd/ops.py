@@ -687,7 +687,8 @@ class ConvBnRelu(torch.autograd.Function):
         dhw = dhb = None
         link = ctx.out_link
         if ctx.head is not None:
-            # OutConv backward + ReLU mask + BatchNorm-backward sums in one pass, then dy = A*dz + B*y + K in place
+            # OutConv backward + ReLU mask + BatchNorm-backward sums in one pass that stores no dz, the coefficients, then
+            # dy = A*dz + B*y + K written once with dz formed again from dout and the filters
             head_w, out = saved[6], saved[7]
             hc = head_w.shape[0]
             dout = da.contiguous().float()
@@ -698,16 +699,20 @@ class ConvBnRelu(torch.autograd.Function):
             part = torch.empty((lib.unet_head_bnrelu_max_parts(), 2, co), dtype=torch.float32, device=dev)
             nparts = C.c_int32(0)
             ws = _workspace(lib.unet_head_bwd_workspace(n, h, w, co, hc), dev)
-            L.check(lib.unet_head_bnrelu_bwd(dt, _ptr(y), _ptr(coef[2]), _ptr(coef[3]), _ptr(coef[0]), _ptr(out),
-                                             _ptr(dout), n, h, w, co, _ptr(head_w), hc, int(ctx.head), _ptr(dy),
-                                             _ptr(dhw), _ptr(dhb), _ptr(part), C.byref(nparts), _ptr(ws), ws.numel(),
-                                             st), "unet_head_bnrelu_bwd")
-            ws = _workspace(3 * co * 4, dev)
-            L.check(lib.unet_bn_bwd_premasked(dt, _ptr(dy), _ptr(y), pixels, co, _ptr(gamma), _ptr(coef[0]),
-                                              _ptr(coef[1]), _ptr(part), nparts.value, _ptr(dgb[0]), _ptr(dgb[1]),
-                                              _ptr(dy), _ptr(ws), ws.numel(), st), "unet_bn_bwd_premasked")
+            L.check(lib.unet_head_bnrelu_bwd_sums(dt, _ptr(y), _ptr(coef[2]), _ptr(coef[3]), _ptr(coef[0]), _ptr(out),
+                                                  _ptr(dout), n, h, w, co, _ptr(head_w), hc, int(ctx.head), _ptr(dhw),
+                                                  _ptr(dhb), _ptr(part), C.byref(nparts), _ptr(ws), ws.numel(), st),
+                    "unet_head_bnrelu_bwd_sums")
+            cf = _workspace(3 * co * 4, dev)
+            L.check(lib.unet_bn_bwd_premasked(dt, None, None, pixels, co, _ptr(gamma), _ptr(coef[0]), _ptr(coef[1]),
+                                              _ptr(part), nparts.value, _ptr(dgb[0]), _ptr(dgb[1]), None, _ptr(cf),
+                                              cf.numel(), st), "unet_bn_bwd_premasked(coefficients)")
+            L.check(lib.unet_head_bnrelu_bwd_apply(dt, _ptr(y), _ptr(coef[2]), _ptr(coef[3]), _ptr(out), _ptr(dout), n, h,
+                                                   w, co, _ptr(head_w), hc, int(ctx.head), _ptr(cf), _ptr(dy), st),
+                    "unet_head_bnrelu_bwd_apply")
         elif ctx.pool and dpooled is not None:
             # pooled gradient routed + added to the skip's gradient buffer + ReLU mask + BatchNorm-backward sums: one pass
+            # that stores nothing, the coefficients, then the same routing again with dy = A*dz + B*y + K written once
             own = False            # `da` is the GradSink buffer of this skip: nobody else holds it, safe to overwrite
             if da is not None:
                 if ctx.out_sink is not None and ctx.out_sink.buf is not None and \
@@ -722,14 +727,16 @@ class ConvBnRelu(torch.autograd.Function):
             dy = da if own else _nhwc_empty(n, co, h, w, dtype, dev)
             part = torch.empty((lib.unet_bn_relu_pool_max_parts(), 2, co), dtype=torch.float32, device=dev)
             nparts = C.c_int32(0)
-            L.check(lib.unet_bn_relu_pool_bwd(dt, _ptr(y), _ptr(dpooled), _ptr(da), n, h, w, co, _ptr(coef[2]),
-                                              _ptr(coef[3]), _ptr(coef[0]), _ptr(dy), _ptr(part), C.byref(nparts), st),
-                    "unet_bn_relu_pool_bwd")
+            L.check(lib.unet_bn_relu_pool_bwd_sums(dt, _ptr(y), _ptr(dpooled), _ptr(da), n, h, w, co, _ptr(coef[2]),
+                                                   _ptr(coef[3]), _ptr(coef[0]), _ptr(part), C.byref(nparts), st),
+                    "unet_bn_relu_pool_bwd_sums")
             dgb = (grad_out(gamma.shape, dev, gkey), grad_out(gamma.shape, dev, bkey))
-            ws = _workspace(3 * co * 4, dev)
-            L.check(lib.unet_bn_bwd_premasked(dt, _ptr(dy), _ptr(y), pixels, co, _ptr(gamma), _ptr(coef[0]),
-                                              _ptr(coef[1]), _ptr(part), nparts.value, _ptr(dgb[0]), _ptr(dgb[1]),
-                                              _ptr(dy), _ptr(ws), ws.numel(), st), "unet_bn_bwd_premasked")
+            cf = _workspace(3 * co * 4, dev)
+            L.check(lib.unet_bn_bwd_premasked(dt, None, None, pixels, co, _ptr(gamma), _ptr(coef[0]), _ptr(coef[1]),
+                                              _ptr(part), nparts.value, _ptr(dgb[0]), _ptr(dgb[1]), None, _ptr(cf),
+                                              cf.numel(), st), "unet_bn_bwd_premasked(coefficients)")
+            L.check(lib.unet_bn_relu_pool_bwd_apply(dt, _ptr(y), _ptr(dpooled), _ptr(da), n, h, w, co, _ptr(coef[2]),
+                                                    _ptr(coef[3]), _ptr(cf), _ptr(dy), st), "unet_bn_relu_pool_bwd_apply")
         else:
             if da is None:                       # (a pooled pair whose skip half nobody used, and no pooled gradient)
                 da = torch.zeros_like(y)
