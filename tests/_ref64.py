@@ -182,6 +182,27 @@ def bn_relu_apply(y, dtype, scale, shift):
     return (t + _c(shift)).clamp_min(0), t.abs() + _c(shift).abs()
 
 
+def fold_weight(w, scale):
+    """the folded weight of an eval-mode conv + BatchNorm layer as unet_pack_conv_weight_folded(_seg) forms it: ONE fp32
+    product w * scale[co] (no fma), fp32"""
+    return w.detach().float().cpu() * scale.detach().float().cpu()[:, None, None, None]
+
+
+def conv3x3_bias_relu(x, w, scale, shift, dtype, relu=True):
+    """unet_conv3x3_bias_relu on the folded weights (inference, BatchNorm(eval) folded into the layer):
+    value = max(conv(x, fold_weight(w, scale)) + shift, 0) with the folded weight and x read in the compute dtype and
+    the shift in fp32; S = conv(|x|, |w_folded|) + |shift|.  ReLU is 1-Lipschitz, so the bound of the plain convolution
+    holds behind it: half a bf16 ulp + 2^-18 S (assert_bf16), 2^-18 S for fp32 (assert_fp32).  scale / shift: as
+    unet_bn_eval_coeffs returned them (read back from the device -- the coefficient kernel has its own test, and its
+    rounding stays out of this bound).  x: one tensor, or the already concatenated / centre-padded pair.
+    relu=False: the entry point's relu = 0."""
+    xq, wq = rd(x, dtype), rd(fold_weight(w, scale), dtype)
+    sh = _c(shift)
+    v = F.conv2d(xq, wq, padding=1) + sh
+    S = F.conv2d(xq.abs(), wq.abs(), padding=1) + sh.abs()
+    return (v.clamp_min(0) if relu else v), S
+
+
 def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps=1e-5):
     """unet_bn_eval_coeffs(4): istd = (running_var + eps)^-1/2 (fp64, one fp32 store), scale = gamma istd, shift = beta -
     running_mean scale (fp32): bounds as in bn_train_stats with exact statistics (d = d_mean = 0)."""

@@ -4,7 +4,9 @@ block of a weight-gradient reduction at the largest K the suite uses -- are reje
 the references of the streaming and reduction kernels (BatchNorm, pooling, bilinear, Adam), the last part for the
 segmentation loss (seg_loss): torch's float64 operators and autograd agree with the closed forms, and a missing block
 partial, a missing tail pixel, wrong Dice coefficients, a dropped focal derivative term, a clamped cross entropy and the
-two contract slips (Dice sum p skipping ignored pixels, focal averaged over valid pixels) are rejected."""
+two contract slips (Dice sum p skipping ignored pixels, focal averaged over valid pixels) are rejected.  At the end the
+folded-BatchNorm inference convolution (conv3x3_bias_relu): an fp32-accumulating emulation passes, a shift from the wrong
+channel, a misplaced or missing ReLU, the neighbouring row's scale, a bf16-rounded shift and a truncating store do not."""
 import pytest
 import torch
 
@@ -660,3 +662,75 @@ def test_seg_missing_tail_pixel_is_rejected_up_to_the_sweep_limit(c):
         ref = R.seg_loss(z, t, None, 255, 1.0, 1.0, 0.5)
         _, grad = _seg_emulation(z, t, None, 255, (1.0, 1.0, 0.5), "drop_tail")
         assert max(R.assert_seg(ref["loss"][0].float(), grad, ref, "tail pixel at 1024 x 512").values()) < 1.0
+
+
+# ====================================================================== folded BatchNorm inference (conv3x3_bias_relu)
+# An fp32-accumulating emulation of the kernel (bf16 operands, exact products, fp32 sums, fp32 shift, ReLU, one
+# round-to-nearest-even store) passes; a shift from the wrong lane or channel tile, the ReLU on the wrong side of the
+# shift or missing, the scale of the neighbouring row, a shift rounded to bf16 and a truncating store are rejected.
+FOLD_SHAPES = [(2, 128, 128, 16, 32), (1, 512, 128, 16, 16), (1, 64, 192, 9, 21)]      # n, ci, co, h, w
+FOLD_DEFECTS = ("shift_c4", "relu_first", "no_relu", "scale_row1", "shift_bf16", "truncate")
+
+
+def _fold_case(shape):
+    n, ci, co, h, w = shape
+    seed = 1000 + ci + co + h
+    x = _gen(seed, (n, ci, h, w)).float()
+    wt = (_gen(seed + 1, (co, ci, 3, 3)) / (3 * ci ** 0.5)).float()
+    rnd = torch.rand(2, co, generator=torch.Generator().manual_seed(seed + 2), dtype=F64)
+    gamma, rv = (rnd[0] + 0.5).float(), (rnd[1] * 1.5 + 0.25).float()
+    beta, rm = _gen(seed + 3, (co,)).float(), (_gen(seed + 4, (co,)) * 0.5).float()
+    scale = gamma * (rv + 1e-5).rsqrt()                  # fp32, as read back from the coefficient kernel
+    shift = beta - rm * scale                            # of the order of the activations (sigma ~ 1)
+    return x, wt, scale, shift
+
+
+def _fold_emulation(x, wt, scale, shift, defect=None):
+    """the kernel in fp32 arithmetic on the CPU: bf16 operands, fp32 accumulation, shift and ReLU in fp32, one store"""
+    sc = scale.roll(-1) if defect == "scale_row1" else scale
+    wq = R.fold_weight(wt, sc).to(torch.bfloat16).float()
+    acc = F.conv2d(x.to(torch.bfloat16).float(), wq, padding=1)
+    sh = shift.roll(-4) if defect == "shift_c4" else shift.to(torch.bfloat16).float() if defect == "shift_bf16" else shift
+    sh = sh[None, :, None, None]
+    if defect == "relu_first":
+        v = acc.clamp_min(0) + sh
+    elif defect == "no_relu":
+        v = acc + sh
+    else:
+        v = (acc + sh).clamp_min(0)
+    return R.round_bf16_toward_zero(v) if defect == "truncate" else v.to(torch.bfloat16)
+
+
+@pytest.fixture(scope="module", params=FOLD_SHAPES, ids=str)
+def fold_case(request):
+    x, wt, scale, shift = _fold_case(request.param)
+    return x, wt, scale, shift, R.conv3x3_bias_relu(x, wt, scale, shift, torch.bfloat16)
+
+
+def test_folded_conv_reference_matches_torch(fold_case):
+    x, wt, scale, shift, (ref, S) = fold_case
+    xq, wq = x.to(torch.bfloat16).double(), (wt * scale[:, None, None, None]).to(torch.bfloat16).double()
+    assert _close(ref, torch.relu(F.conv2d(xq, wq, shift.double(), padding=1)))
+    assert bool((S >= ref.abs()).all())
+    lin = R.conv3x3_bias_relu(x, wt, scale, shift, torch.bfloat16, relu=False)[0]
+    assert _close(lin.clamp_min(0), ref) and float(lin.min()) < 0
+    # fp32 compute dtype: the folded weight is read unrounded
+    r32 = R.conv3x3_bias_relu(x, wt, scale, shift, torch.float32)[0]
+    assert _close(r32, torch.relu(F.conv2d(x.double(), (wt * scale[:, None, None, None]).double(), shift.double(), padding=1)))
+    # the shift matters: of the order of the activations, distinct per channel
+    assert float(shift.abs().mean()) > 0.3 and shift.unique().numel() == shift.numel()
+
+
+def test_folded_conv_emulation_is_accepted(fold_case):
+    x, wt, scale, shift, rs = fold_case
+    worst = R.assert_bf16(_fold_emulation(x, wt, scale, shift), rs, "fp32-accumulating emulation")
+    assert worst <= 1.0
+    out32 = torch.relu(F.conv2d(x, R.fold_weight(wt, scale), shift, padding=1))
+    R.assert_fp32(out32, R.conv3x3_bias_relu(x, wt, scale, shift, torch.float32), "fp32 emulation")
+
+
+@pytest.mark.parametrize("defect", FOLD_DEFECTS)
+def test_folded_conv_defects_are_rejected(fold_case, defect):
+    x, wt, scale, shift, rs = fold_case
+    with pytest.raises(AssertionError):
+        R.assert_bf16(_fold_emulation(x, wt, scale, shift, defect), rs, defect)

@@ -189,10 +189,14 @@ def test_conv3x3_folded_batchnorm_inference(hip, dtype, case):
     assert float(y.float().min()) >= 0.0
 
 
-@pytest.mark.parametrize("case", [(2, 3, 12, 32), (1, 1, 16, 16), (3, 3, 33, 48), (2, 2, 5, 64)], ids=str)
+@pytest.mark.parametrize("case", [(2, 3, 12, 32), (1, 1, 16, 16), (3, 3, 33, 48), (2, 2, 5, 64),
+                                  (2, 3, 256, 256)],      # N * H * W = R.MAX_WGRAD_K: the longest weight-gradient reduction
+                         ids=str)
 def test_conv3x3_first_layer_kernels(hip, case):
     """unet_conv3x3_first_stats / _first_wgrad (the image layer without the 64-channel padded copy, bf16 mode)
-    against F.conv2d on the bf16-rounded operands: output, fused BatchNorm partial sums, weight gradient."""
+    against F.conv2d on the bf16-rounded operands: output, fused BatchNorm partial sums, weight gradient -- and element
+    by element against the float64 references of _ref64 (y: half a bf16 ulp + 2^-18 S; the two statistics sums over
+    the stored y and dw: 2^-18 S)."""
     L, ops = hip
     n, ci, h, w = case
     co, dtype = 64, torch.bfloat16
@@ -209,11 +213,15 @@ def test_conv3x3_first_layer_kernels(hip, case):
     nparts = C.c_int32(0)
     L.check(L.lib().unet_conv3x3_first_stats(n, h, w, p(xd), ci, p(wd), p(y), p(part), C.byref(nparts), st()), "first fwd")
     check(y, ref, dtype, "first-layer conv fwd")
+    worst_y = R.assert_bf16(y, R.conv3x3(x, wt), "first-layer conv fwd")
     assert 0 < nparts.value <= cap
     sums = part[:nparts.value * 2 * co].view(nparts.value, 2, co).double().sum(0).cpu()
     yf = y.float().cpu().double()
     assert torch.allclose(sums[0], yf.sum((0, 2, 3)), rtol=1e-4, atol=1e-2), "fused sum(y)"
     assert torch.allclose(sums[1], (yf * yf).sum((0, 2, 3)), rtol=1e-4, atol=1e-2), "fused sum(y^2)"
+    assert n * h * w <= R.MAX_STREAM_PIXELS
+    worst_s = max(R.assert_fp32(sums[0], R.sums_over_pixels(yf), "first-layer fused sum(y)"),
+                  R.assert_fp32(sums[1], R.sums_over_pixels(yf * yf), "first-layer fused sum(y^2)"))
     # no statistics requested (eval mode): same output
     y2 = ops._nhwc_empty(n, co, h, w, dtype, dev())
     L.check(L.lib().unet_conv3x3_first_stats(n, h, w, p(xd), ci, p(wd), p(y2), None, None, st()), "first fwd eval")
@@ -224,6 +232,9 @@ def test_conv3x3_first_layer_kernels(hip, case):
     ws = torch.empty(need, dtype=torch.uint8, device=dev())
     L.check(L.lib().unet_conv3x3_first_wgrad(n, h, w, p(xd), ci, p(gd), p(dw), p(ws), need, st()), "first wgrad")
     check(dw, wq.grad, dtype, "first-layer wgrad", bf=5e-3)
+    assert n * h * w <= R.MAX_WGRAD_K
+    worst_w = R.assert_fp32(dw, R.conv3x3_wgrad(x, gy), "first-layer wgrad")
+    print(f"\nREF64 inference image layer {case}: worst err/bound y {worst_y:.3f} sums {worst_s:.3f} dw {worst_w:.3f}", flush=True)
     dw2 = torch.empty_like(dw)
     L.check(L.lib().unet_conv3x3_first_wgrad(n, h, w, p(xd), ci, p(gd), p(dw2), p(ws), need, st()), "first wgrad again")
     assert torch.equal(dw, dw2), "ordered reductions: bitwise reproducible"

@@ -5,7 +5,9 @@ to a multiple of 8, at least 8; ddp.configure_overlap() reserves CUs on every mu
 many work items a block walks and whether its last round is ragged, the channel-tile interleave co_il, block-mode or
 per-tile BatchNorm partials (zdiv), the tpb >= 2 floor and the empty tile ranges padded to a multiple of 8 of the ws
 kernels, the split-K count with the narrow (split < 16) or wide reduce and xcd_chunk of the weight gradients, and the
-nsplit clamp of convt_wgrad_ws.  Each case runs at budgets {full, full-8, 136, 40, 24, 8} and asserts, at every one:
+nsplit clamp of convt_wgrad_ws.  The inference entry point unet_conv3x3_bias_relu (BatchNorm(eval) folded into the
+weights; families bias_relu / bias_relu2) runs in every kernel variant dispatch<> selects for it, each of which adds the
+shift (+ ReLU) with a bias index of its own.  Each case runs at budgets {full, full-8, 136, 40, 24, 8} and asserts, at every one:
 
   * the profiling bracket is the expected kernel (a case cannot silently move to another kernel);
   * every output passes the float64 comparator of _ref64 (half a bf16 ulp + 2^-18 S; fp32 outputs 2^-18 S);
@@ -77,6 +79,24 @@ CASES = [
      "second source at an offset: pdma_dense_src = 0; 18 items"),
     ("dgrad2", "conv3_pdma128_kernel", dict(n=1, cy=256, c0=128, c1=128, h=32, w=80, h1=30, w1=72, oy=1, ox=4),
      "two destinations, the second cropped at an offset: pdma_dense = 0; 10 x 2 items"),
+    # ---- unet_conv3x3_bias_relu: inference, BatchNorm(eval) folded into the weights, shift (+ ReLU) in the epilogue of
+    # every kernel dispatch<> selects (each epilogue has its own hand-written bias index)
+    ("bias_relu", "conv3_pdma128_kernel", dict(n=1, ci=256, co=256, h=32, w=48),
+     "lock-step pdma128, two channel tiles: 12 items, co_il 2 on 16 blocks down to budget 24, co_il 1 ragged at 8"),
+    ("bias_relu", "conv3_pdma128_kernel", dict(n=1, ci=512, co=128, h=32, w=80),
+     "Ctot 512 -> ping-pong: the epilogue runs once per half; 10 items"),
+    ("bias_relu", "conv3_pdma64_kernel", dict(n=3, ci=128, co=64, h=80, w=16), "pair (pdma64x2); 15 items"),
+    ("bias_relu", "conv3_pdma64_kernel", dict(n=3, ci=256, co=64, h=32, w=48, relu=0),
+     "lock-step pdma64, relu = 0 (shift only); 18 items"),
+    ("bias_relu", "conv3_pdma64_kernel", dict(n=1, ci=256, co=192, h=32, w=48),
+     "c_out 192 -> 64-channel tiles, three of them; 6 x 3 items"),
+    ("bias_relu", "conv3_ws_kernel", dict(n=3, ci=64, co=64, h=32, w=80), "ws16, one channel group; 30 tiles"),
+    ("bias_relu", "conv3_ws_kernel", dict(n=1, ci=64, co=128, h=96, w=48), "ws16, two channel groups; 18 tiles x 2"),
+    ("bias_relu", "conv3_ws_kernel", dict(n=5, ci=64, co=64, h=40, w=24), "ragged frame -> conv3_ws_kernel; 30 tiles"),
+    ("bias_relu2", "conv3_pdma128_kernel", dict(n=3, c0=128, c1=128, co=128, h=48, w=32, h1=40, w1=24, oy=4, ox=4),
+     "skip-concat (every Up block in eval mode), second source at an offset, lock-step; 18 items"),
+    ("bias_relu2", "conv3_pdma128_kernel", dict(n=1, c0=256, c1=256, co=128, h=32, w=80, h1=24, w1=72, oy=4, ox=4),
+     "skip-concat on the ping-pong kernel (Ctot 512); 10 items"),
     # ---- unet_conv3x3_dgrad_bnrelu
     ("dgrad_bn", "conv3_pdma128_bnbwd_kernel", dict(n=3, cy=256, cx=128, h=48, w=32), "pdma128_bnbwd; 18 items"),
     ("dgrad_bn", "conv3_pdma128_bnbwd_kernel", dict(n=1, cy=512, cx=128, h=32, w=80), "pp128_bnbwd; 10 items"),
@@ -127,6 +147,11 @@ def plan(case, budget):
         bn = 128 if co % 128 == 0 else 64
         n_tiles = s["n"] * cdiv(s["h"], 16) * cdiv(s["w"], 16)
         nco = co // bn
+        ctot = s["ci"] if "ci" in s else s["cy"] if "cy" in s else s["c0"] + s["c1"]
+        tags.add("pp" if bn == 128 and ctot >= 512 else "pair" if bn == 64 and ctot == 128 else "lockstep")
+        tags.add(f"nco{nco}")
+        if s.get("c1") and fam != "dgrad2":
+            tags.add("two_sources")
         work = n_tiles * nco
         blocks = min(budget, ceil8(work))
         rounds(work, blocks)
@@ -139,6 +164,7 @@ def plan(case, budget):
     elif kern.startswith("conv3_ws"):
         co = s.get("co", s.get("cx"))
         tiles = s["n"] * cdiv(s["h"], 16) * cdiv(s["w"], 16)
+        tags.add(f"ws16_groups{co // 64}" if s["h"] % 16 == 0 and s["w"] % 16 == 0 else "ws_ragged_frame")
         tpb = cdiv(tiles * (co // 64), budget)
         if tpb < 2:
             tags.add("tpb_floor")
@@ -214,6 +240,19 @@ def test_partition_table_reaches_every_budget_branch():
         t = plan(case, 8)
         assert "several_items" in t, (case[1], case[2], t)
         assert "ragged_last_round" in t or "block-mode" in case[3], (case[1], case[2], t)
+    # the inference epilogue (bias_relu / bias_relu2) is entered in every kernel variant dispatch<> can select for it
+    fold = set()
+    for case in CASES:
+        if case[0].startswith("bias_relu"):
+            bn = case[1].split("_")[1] if "pdma" in case[1] else "ws"
+            fold |= {(bn, t) for b in BUDGETS for t in plan(case, budget_value(b, 256))}
+    want = {("pdma128", "lockstep"), ("pdma128", "nco2"), ("pdma128", "pp"), ("pdma128", "co_il2"), ("pdma128", "co_il1"),
+            ("pdma64", "pair"), ("pdma64", "lockstep"), ("pdma64", "nco3"), ("ws", "ws16_groups1"), ("ws", "ws16_groups2"),
+            ("ws", "ws_ragged_frame")}
+    assert want <= fold, sorted(want - fold)
+    two = [plan(c, 256) for c in CASES if c[0] == "bias_relu2"]
+    assert any({"two_sources", "lockstep"} <= t for t in two) and any({"two_sources", "pp"} <= t for t in two)
+    assert sum(1 for c in CASES if c[0].startswith("bias_relu") and c[2].get("relu", 1) == 0) == 1
     # the weight-gradient cases stay within the K the CPU self-test plants its missing block at
     for fam, _, s, _ in CASES:
         if fam in ("wgrad", "convt_wgrad"):
@@ -297,7 +336,27 @@ def bn_coefs(y, cx):
 
 
 # ------------------------------------------------------------------ per-family: inputs + reference, launch
-def make_case(fam, s):
+def eval_coeffs(L, co, tag):
+    """per-channel BatchNorm(eval) parameters, all distinct, with a shift of the order of the activations (sigma ~ 1: a
+    bias from the wrong lane or channel tile moves an element by many bounds), and (scale, shift) as
+    unet_bn_eval_coeffs returns them, read back -- the reference takes those, so that kernel's rounding (held to its own
+    bound here) stays out of the convolution's"""
+    gamma = W.make_input("part:" + tag + "gamma", (co,), kind="uniform") + 0.5
+    beta = W.make_input("part:" + tag + "beta", (co,))
+    rm = W.make_input("part:" + tag + "rm", (co,)) * 0.5
+    rv = W.make_input("part:" + tag + "rv", (co,), kind="uniform") * 1.5 + 0.25
+    g, b, m, v = (t.float().to(dev()).contiguous() for t in (gamma, beta, rm, rv))
+    ss = torch.empty((2, co), dtype=torch.float32, device=dev())
+    L.check(L.lib().unet_bn_eval_coeffs(co, p(g), p(b), p(m), p(v), C.c_float(1e-5), p(ss[0]), p(ss[1]), st()), "coeffs")
+    scale, shift = ss[0].cpu(), ss[1].cpu()
+    want = R.bn_eval_coeffs(gamma.float(), beta.float(), rm.float(), rv.float())
+    R.assert_fp32(scale, want["scale"], "unet_bn_eval_coeffs scale")
+    R.assert_fp32(shift, want["shift"], "unet_bn_eval_coeffs shift")
+    assert float(shift.abs().mean()) > 0.3 and shift.unique().numel() == co and scale.unique().numel() == co
+    return scale, shift
+
+
+def make_case(fam, s, L=None):
     """CPU inputs (bf16-exact fp32) and the float64 references {name: (ref, S, kind, mask)}"""
     tag = fam + str(sorted(s.items()))
     inp, ref = {}, {}
@@ -317,6 +376,22 @@ def make_case(fam, s):
         inp["w"] = rnd(tag + "w", (co, c0 + c1, 3, 3), 1 / (3 * (c0 + c1) ** 0.5))
         x1p = torch.nn.functional.pad(inp["x1"], [s["ox"], w - s["w1"] - s["ox"], s["oy"], h - s["h1"] - s["oy"]])
         r, S = R.conv3x3(torch.cat([inp["x2"], x1p], 1), inp["w"])
+        ref["y"] = (r, S, "bf16", None)
+    elif fam in ("bias_relu", "bias_relu2"):
+        co = s["co"]
+        if fam == "bias_relu":
+            ctot = s["ci"]
+            inp["x"] = xs = rnd(tag + "x", (n, ctot, h, w))
+        else:
+            c0, c1, ctot = s["c0"], s["c1"], s["c0"] + s["c1"]
+            inp["x2"], inp["x1"] = rnd(tag + "x2", (n, c0, h, w)), rnd(tag + "x1", (n, c1, s["h1"], s["w1"]))
+            x1p = torch.nn.functional.pad(inp["x1"], [s["ox"], w - s["w1"] - s["ox"], s["oy"], h - s["h1"] - s["oy"]])
+            xs = torch.cat([inp["x2"], x1p], 1)
+        inp["w"] = W.make_input("part:" + tag + "w", (co, ctot, 3, 3)).float() * (1 / (3 * ctot ** 0.5))     # fp32 operand
+        inp["scale"], inp["shift"] = eval_coeffs(L, co, tag)
+        r, S = R.conv3x3_bias_relu(xs, inp["w"], inp["scale"], inp["shift"], torch.bfloat16, relu=bool(s.get("relu", 1)))
+        if s.get("relu", 1):
+            assert 0.2 < float((r == 0).double().mean()) < 0.8, "the ReLU must clip a good part of the output, not all"
         ref["y"] = (r, S, "bf16", None)
     elif fam == "dgrad2":
         cy, c0, c1 = s["cy"], s["c0"], s["c1"]
@@ -400,6 +475,16 @@ def launch(L, ops, fam, s, d, G):
             L.check(lib.unet_conv3x3(dt, n, h, w, src, p(d["wp"]), co, views(L, [(y, 0, 0), None]), co,
                                      1 if fam == "fwd_acc" else 0, L.K_CONV_FWD, st()), "conv3x3")
         out["y"] = y
+    elif fam in ("bias_relu", "bias_relu2"):
+        co = s["co"]
+        if fam == "bias_relu2":
+            src = views(L, [(d["x2"], 0, 0), (d["x1"], s["oy"], s["ox"])])
+        else:
+            src = views(L, [(d["x"], 0, 0), None])
+        y = G.nhwc(n, co, h, w, "y")
+        L.check(lib.unet_conv3x3_bias_relu(dt, n, h, w, src, p(d["wp"]), co, p(y), p(d["shift"]), int(s.get("relu", 1)),
+                                           st()), "conv3x3 bias relu")
+        out["y"] = y
     elif fam == "dgrad2":
         c0, c1 = s["c0"], s["c1"]
         d2 = G.nhwc(n, c0, h, w, "d2")
@@ -460,13 +545,18 @@ def launch(L, ops, fam, s, d, G):
 def to_device(L, ops, fam, s, inp):
     d = {}
     for k, v in inp.items():
-        if k in ("w", "b", "coef"):
+        if k in ("w", "b", "coef", "scale", "shift"):
             d[k] = v.to(dev()).contiguous()
         else:
             d[k] = to_nhwc(v)
     if "w" in inp:
         wd = d["w"]
-        if fam in ("stats", "fwd_acc", "fwd2"):
+        if fam in ("bias_relu", "bias_relu2"):
+            co, ctot = wd.shape[0], wd.shape[1]
+            d["wp"] = torch.empty(9 * co * ctot, dtype=torch.bfloat16, device=dev())
+            L.check(L.lib().unet_pack_conv_weight_folded(p(wd), p(d["scale"]), p(d["wp"]), co, ctot, co, ctot, L.UNET_BF16,
+                                                         st()), "fold")
+        elif fam in ("stats", "fwd_acc", "fwd2"):
             d["wp"] = ops.pack_weight(wd, L.PACK_CONV_FWD, wd.shape[0], wd.shape[1], torch.bfloat16)
         elif fam in ("dgrad2", "dgrad_bn"):
             d["wp"] = ops.pack_weight(wd, L.PACK_CONV_DGRAD, wd.shape[1], wd.shape[0], torch.bfloat16)
@@ -532,11 +622,11 @@ def test_persistent_launcher_across_cu_budgets(hip, budget, case):
     torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
     key = (fam, tuple(sorted(s.items())))
     if key not in _REFS:
-        _REFS[key] = make_case(fam, s)
+        _REFS[key] = make_case(fam, s, L)
     inp, ref = _REFS[key]
     d = to_device(L, ops, fam, s, inp)
     torch.cuda.synchronize()
-    first, worst, seen = None, {"bf16": 0.0, "fp32": 0.0}, set()
+    first, worst, seen, per_budget = None, {"bf16": 0.0, "fp32": 0.0}, set(), {}
     for b in BUDGETS:
         bv = set_budget(b)
         if bv in seen:
@@ -560,7 +650,9 @@ def test_persistent_launcher_across_cu_budgets(hip, budget, case):
         at = f"[budget {bv}] {fam} {kern}"
         for name, (r, S, kind, mask) in ref.items():
             fn = R.assert_bf16 if kind == "bf16" else R.assert_fp32
-            worst[kind] = max(worst[kind], fn(out[name].float(), (r, S), f"{at} {name}", mask))
+            got = fn(out[name].float(), (r, S), f"{at} {name}", mask)
+            worst[kind] = max(worst[kind], got)
+            per_budget[bv] = max(per_budget.get(bv, 0.0), got)
         if "sums" in out:
             sr, sS = stat_refs(fam, out, d)
             worst["fp32"] = max(worst["fp32"], R.assert_fp32(out["sums"], (sr, sS), f"{at} statistics sums"))
@@ -577,4 +669,4 @@ def test_persistent_launcher_across_cu_budgets(hip, budget, case):
                 Sx = ref[name][1] if name in ref else stat_refs(fam, out, d)[1]
                 R.assert_fp32(v.double(), (v0, 2 * Sx), f"{at} {name} vs budget {first[0]}")
     print(f"[{fam} {kern} {s}] budgets {sorted(seen)}: worst err/bound bf16 {worst['bf16']:.3f} fp32 {worst['fp32']:.3f} "
-          f"({time.time() - t0:.1f} s)")
+          f"per budget {' '.join(f'{b}:{v:.3f}' for b, v in sorted(per_budget.items()))} ({time.time() - t0:.1f} s)")

@@ -283,6 +283,50 @@ def test_eval_after_fused_adam_step_uses_fresh_weights(bilinear, grad_enabled):
     assert maxabs(r1, r2) == 0.0 and maxabs(a1, a2) == 0.0, (maxabs(r1, r2), maxabs(a1, a2))
 
 
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("frozen", ["model_eval", "layers_eval"])
+def test_eval_after_fused_adam_step_with_frozen_batchnorm_uses_fresh_weights(frozen, precision):
+    """The same with every BatchNorm frozen during the step, so that no layer runs a training forward:
+    model_eval  -- fine-tuning with model.eval() and autograd on (the step is followed by another such forward);
+    layers_eval -- model.train() with bn.eval() on every BatchNorm2d.
+    FusedAdam writes the parameters through raw pointers (no version counter moves): the step itself must invalidate the
+    model's packed weights (eval forward with autograd) and the folded BatchNorm packs (eval forward under no_grad).
+    Both forwards must agree bit for bit with a fresh model loaded from the state_dict."""
+    import tiaozhanbei_unet_amd as P
+    torch.manual_seed(11)
+    m = P.AnomalyUNet(3, precision=precision).to(DEV)
+    opt = P.get_optimizer(m, "adam", 5e-2, 0.0)                # a large step: stale weights would be far off
+    assert type(opt).__name__ == "FusedAdam"
+    x = W.make_input("fresh:x", (2, 3, 32, 32)).to(DEV)
+    mask = W.make_input("fresh:mask", (2, 1, 32, 32), kind="bernoulli").to(DEV)
+    m.eval()
+    with torch.no_grad():
+        m(x)                                                    # the folded packs are built and cached
+    if frozen == "layers_eval":
+        m.train()
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.BatchNorm2d):
+                mod.eval()
+    recon, amap = m(x)                                          # packed weights built / refreshed, autograd on
+    P.CombinedLoss()(recon, amap, x, mask)["total_loss"].backward()
+    before = {k: v.detach().clone() for k, v in m.named_parameters()}
+    opt.step()
+    assert any(not torch.equal(v, before[k]) for k, v in m.named_parameters()), "the step changed nothing"
+    m.eval()
+    got = [m(x)]
+    with torch.no_grad():
+        got.append(m(x))
+    fresh = P.AnomalyUNet(3, precision=precision).to(DEV)
+    fresh.load_state_dict(m.state_dict())
+    fresh.eval()
+    want = [fresh(x)]
+    with torch.no_grad():
+        want.append(fresh(x))
+    diff = {mode: (maxabs(r1, r2), maxabs(a1, a2))
+            for mode, (r1, a1), (r2, a2) in zip(("autograd on", "no_grad (folded)"), got, want)}
+    assert all(d == (0.0, 0.0) for d in diff.values()), (frozen, diff)
+
+
 # ------------------------------------------------------------------ data parallel on one card
 def test_data_parallel_gradients_equal_mean_of_shard_gradients(tmp_path):
     """2 ranks stacked on this card over gloo, DataParallel(AnomalyUNet) with the two decoder streams on, bs = 2 per

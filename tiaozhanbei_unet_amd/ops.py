@@ -327,8 +327,9 @@ class PackCache:
     def refresh(self, force=False):
         """``force``: repack regardless of the version counters (fused optimisers update parameters without
         moving them, so a training forward always repacks: one ~0.1 ms launch).  An eval-mode forward repacks when
-        any training forward happened since the last pack (``_train_generation`` moved): the optimiser step that
-        followed it changed the weights through raw pointers that no version counter sees."""
+        ``_train_generation`` moved since the last pack: a fused optimiser step (``parameters_written``) changed the
+        weights through raw pointers that no version counter sees -- also when every BatchNorm was frozen during the
+        step, so that no layer ran a training forward."""
         if not self.items:
             return
         if self.table is None or self.ptrs != [w.data_ptr() for (w, _, _, _, _) in self.items]:
@@ -428,14 +429,25 @@ def share_grad(t: torch.Tensor) -> torch.Tensor:
 
 FOLD_EVAL_BN = __import__("os").environ.get("UNET_FOLD_BN", "1") != "0"
 _folded = {}                                             # id(weight) -> (weakref to it, {(dtype, ctot): (stamp, payload)})
-_train_generation = 0                                    # bumped by every training forward (see below)
+_train_generation = 0                                    # bumped by every training forward (see below) and by
+                                                         # parameters_written()
+
+
+def parameters_written():
+    """To be called by whatever updates parameters (or BatchNorm buffers) through raw pointers, where no autograd version
+    counter moves (optim.FusedAdam.step): every packed copy of them -- PackCache, the folded BatchNorm packs -- is stale
+    from here on.  A training forward does the same for the running statistics its kernels write.  Both are host-side
+    counters: an update replayed from a captured graph does not run them, so whoever replays one calls this after it."""
+    global _train_generation
+    _train_generation += 1
 
 
 def _folded_pack(weight, gamma, beta, running_mean, running_var, co, ctot, dtype, rows=None, split=0):
     """(packed folded weights, shift) of an eval-mode conv+BN layer.  Cached per weight Parameter; an entry is valid
     while the autograd version counters of the five tensors AND the training generation are unchanged -- the HIP
     kernels update running statistics (and fused optimisers update parameters) through raw pointers, which no version
-    counter sees, so any training forward in between invalidates every entry.  ``rows`` (> co for a narrow layer:
+    counter sees, so any training forward or fused optimiser step (``parameters_written``) in between invalidates
+    every entry.  ``rows`` (> co for a narrow layer:
     zero-padded BatchNorm coefficients, zero weight rows) and ``split`` (segment map of the input channels) give the
     padded layer's pack."""
     stamp = (_train_generation, weight._version, gamma._version, beta._version, running_mean._version,

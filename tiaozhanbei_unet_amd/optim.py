@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import ops
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -120,6 +121,7 @@ class FusedAdam(torch.optim.Optimizer):
                                             tab["n_chunks"], float(group["lr"]), float(b1), float(b2),
                                             float(group["eps"]), float(group["weight_decay"]), float(self.grad_scale),
                                             step, int(group["decoupled"]), st), "unet_adam_multi")
+            ops.parameters_written()           # raw-pointer update: no version counter moved, the packed copies are stale
             for s_ in states:
                 s_["step"] += 1
         return loss
