@@ -698,6 +698,33 @@ size_t unet_color_jitter_workspace(int32_t n);
 int32_t unet_color_jitter_normalize_u8(const uint8_t* images_hwc, int32_t n, int32_t h, int32_t w,
                                        const unet_jitter_desc* desc, const float* mean3, const float* std3,
                                        float* out_nchw, void* workspace, size_t workspace_bytes, void* stream);
+/* Synthetic anomalies for the MVTec trainer (DRAEM / CutPaste style), one launch per batch: inside a smooth random mask
+ * the clean image is blended with a shifted, channel-permuted image of the same batch.  There is no reference code for
+ * this -- the reference trains on train/good alone, so its masks are all zero and its reconstruction target is the
+ * network's input -- hence the definition is this library's own: it is written out at the top of csrc/synth.hip and
+ * restated independently in tests/_synth_ref.py, which the kernel equals bit for bit (fp32, no contraction).
+ * images / corrupted [n][3][h][w] fp32 (normalised, distinct buffers), masks_in [n][1][h][w] fp32 or NULL, masks_out
+ * [n][1][h][w] = max(masks_in, m) with m in {0, 1}.  Per image (desc: DEVICE array of n; desc_host: the same n structs in
+ * HOST memory, read before the launch to check them): m = apply && noise(seed, cells_y, cells_x) > threshold; where m,
+ * corrupted[ch] = beta * x[ch] + one_minus_beta * images[src][perm(ch)][(y + shift_y) % h][(x + shift_x) % w], elsewhere
+ * corrupted = x bit for bit.  perm 0..5 = the permutations of (0, 1, 2) in lexicographic order.  Tables (DEVICE):
+ * ycell [7][h] int32 and ytf [7][2][h] fp32 = cell index, then fraction t and fade(t), of every row for 1, 2, .. 64 cells;
+ * xcell / xtf the same for the columns; gradients [256][2] = (cos, sin)(2 pi k / 256).  c != 3, n, h, w < 1, a side >=
+ * 32768, src outside the batch, cells not a power of two in 1..64, a shift outside the frame or perm outside 0..5:
+ * UNET_ERR_UNSUPPORTED before any launch.  No atomics, no workspace, no synchronisation. */
+typedef struct unet_synth_desc {
+  int32_t apply;              /* 0 leaves the image (and its mask) as it is */
+  uint32_t seed;
+  int32_t cells_y, cells_x;
+  float threshold;
+  float beta, one_minus_beta; /* both set by the caller: nothing recomputes 1 - beta */
+  int32_t src, shift_y, shift_x, perm;
+  int32_t reserved;
+} unet_synth_desc;
+int32_t unet_synth_anomalies(const float* images, const float* masks_in, int32_t n, int32_t c, int32_t h, int32_t w,
+                             const unet_synth_desc* desc, const unet_synth_desc* desc_host, const int32_t* ycell,
+                             const float* ytf, const int32_t* xcell, const float* xtf, const float* gradients,
+                             float* corrupted, float* masks_out, void* stream);
 
 /* One fused step over a flat fp32 parameter arena: L2-coupled weight decay, bias correction,
  * gradient pre-scale (1/world_size under data parallelism). step is 1-based.  The betas are doubles so that 1 - beta is

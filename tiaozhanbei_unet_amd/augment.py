@@ -344,3 +344,142 @@ def polygon_class_histogram(polys, src_sizes, device="cuda") -> torch.Tensor:
                                                  _ptr(hw), n, max(h for h, _ in sizes), max(w for _, w in sizes),
                                                  _ptr(hist), _stream()), "unet_polygon_class_histogram")
     return hist
+
+
+# ------------------------------------------------------------------------------------------------ synthetic anomalies
+SYNTH_DTYPE = np.dtype([("apply", "<i4"), ("seed", "<u4"), ("cells_y", "<i4"), ("cells_x", "<i4"), ("threshold", "<f4"),
+                        ("beta", "<f4"), ("one_minus_beta", "<f4"), ("src", "<i4"), ("shift_y", "<i4"), ("shift_x", "<i4"),
+                        ("perm", "<i4"), ("reserved", "<i4")])          # struct unet_synth_desc
+SYNTH_MAX_CELLS_LOG2 = 6                 # lattices of 1, 2, .. 64 cells per axis
+SYNTH_PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))     # descriptor field `perm`
+
+_synth_tables = {}
+
+
+def _synth_axis_tables(length: int, device):
+    """Where the pixel centres of an axis of ``length`` pixels fall in lattices of 1, 2, .. 64 cells (csrc/synth.hip):
+    cell [7, length] int32 and (t, fade(t)) [7, 2, length] fp32 in device memory, cached per (length, device).  Pixel p
+    of L cells: cell (2pL + L) // (2 length), t = the remainder over 2 length rounded to fp32, fade in fp32 with every
+    operation rounding once."""
+    key = (length, device.index)
+    hit = _synth_tables.get(key)
+    if hit is None:
+        p = np.arange(length, dtype=np.int64)
+        cell = np.empty((SYNTH_MAX_CELLS_LOG2 + 1, length), dtype=np.int32)
+        tf = np.empty((SYNTH_MAX_CELLS_LOG2 + 1, 2, length), dtype=np.float32)
+        for lg in range(SYNTH_MAX_CELLS_LOG2 + 1):
+            num = (2 * p + 1) << lg
+            cell[lg] = num // (2 * length)
+            t = ((num % (2 * length)).astype(np.float64) / np.float64(2 * length)).astype(np.float32)
+            six, fifteen, ten = np.float32(6), np.float32(15), np.float32(10)
+            tf[lg, 0] = t
+            tf[lg, 1] = t * t * t * (t * (t * six - fifteen) + ten)
+        hit = _synth_tables[key] = (torch.from_numpy(cell).to(device), torch.from_numpy(tf).to(device))
+    return hit
+
+
+def _synth_gradients(device):
+    """The 256 unit gradient vectors (cos, sin)(2 pi k / 256), computed in double and rounded to fp32; uploaded once."""
+    key = ("gradients", device.index)
+    hit = _synth_tables.get(key)
+    if hit is None:
+        a = 2.0 * np.pi * np.arange(256, dtype=np.float64) / 256.0
+        hit = _synth_tables[key] = torch.from_numpy(np.stack([np.cos(a), np.sin(a)], 1).astype(np.float32)).to(device)
+    return hit
+
+
+def synth_table(n: int, apply, seed, cells_y, cells_x, threshold, beta, src, shift_y, shift_x, perm) -> np.ndarray:
+    """struct unet_synth_desc[n]; every argument is a scalar or a sequence of n.  ``one_minus_beta`` is set here, as the
+    fp32 difference 1 - fp32(beta)."""
+    rec = np.zeros(n, dtype=SYNTH_DTYPE)
+    rec["apply"] = np.asarray(apply, dtype=bool)
+    rec["seed"] = np.asarray(seed, dtype=np.int64) & 0xFFFFFFFF
+    rec["cells_y"], rec["cells_x"], rec["threshold"] = cells_y, cells_x, threshold
+    rec["beta"] = beta
+    rec["one_minus_beta"] = np.float32(1) - rec["beta"]
+    rec["src"], rec["shift_y"], rec["shift_x"], rec["perm"] = src, shift_y, shift_x, perm
+    return rec
+
+
+def synth_anomalies(images: torch.Tensor, desc: np.ndarray, masks: Optional[torch.Tensor] = None):
+    """Corrupt a batch of normalised fp32 [N, 3, H, W] device images inside per-image Perlin masks (unet_synth_anomalies;
+    the definition is at the top of csrc/synth.hip): where image i's noise exceeds its threshold the pixel becomes
+    ``beta * x + one_minus_beta * donor``, the donor being image ``src`` of the batch, cyclically shifted and with its
+    channels permuted.  ``desc`` = synth_table(...) of the batch size.  Returns (corrupted [N, 3, H, W], mask [N, 1, H, W]
+    fp32) with mask = max(masks, m), m in {0, 1}; one launch, one small host-to-device copy, no synchronisation."""
+    _require_cuda(images, masks)
+    if images.dtype != torch.float32 or images.dim() != 4:
+        raise ValueError("synth_anomalies expects a float32 [N, 3, H, W] device tensor")
+    n, c, h, w = images.shape
+    if not isinstance(desc, np.ndarray) or desc.dtype != SYNTH_DTYPE or desc.shape != (n,):
+        raise ValueError("desc: expected synth_table(...) of the batch size")
+    if masks is not None and (masks.dtype != torch.float32 or tuple(masks.shape) != (n, 1, h, w)):
+        raise ValueError("masks: expected a float32 [N, 1, H, W] device tensor")
+    images = images.contiguous()
+    masks = None if masks is None else masks.contiguous()
+    dev = images.device
+    desc = np.ascontiguousarray(desc)
+    corrupted = torch.empty_like(images)
+    out_masks = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev)
+    if c == 3 and n > 0 and 0 < h < 32768 and 0 < w < 32768:
+        (ycell, ytf), (xcell, xtf) = _synth_axis_tables(h, dev), _synth_axis_tables(w, dev)
+    else:                                    # the library refuses such a batch before it reads any table
+        ycell = ytf = xcell = xtf = out_masks
+    desc_dev = torch.from_numpy(desc.view(np.uint8).reshape(n, -1)).to(dev, non_blocking=True)
+    L.check(L.lib().unet_synth_anomalies(_ptr(images), _ptr(masks), n, c, h, w, _ptr(desc_dev),
+                                         desc.ctypes.data_as(C.c_void_p), _ptr(ycell), _ptr(ytf), _ptr(xcell), _ptr(xtf),
+                                         _ptr(_synth_gradients(dev)), _ptr(corrupted), _ptr(out_masks), _stream()),
+            "unet_synth_anomalies")
+    return corrupted, out_masks
+
+
+class AnomalySynthesizer:
+    """Synthetic anomalies for training on defect-free images (DRAEM / CutPaste style), on the GPU: with probability ``p``
+    an image is corrupted inside a thresholded Perlin-noise mask by blending in another (or the same, shifted) image of
+    its batch, and the mask becomes its segmentation truth.  ``corrupt(images, masks)`` -> (corrupted, masks) is what
+    ``train_utils.train_epoch(..., corrupt=...)`` takes.
+
+    ``draw(n, size)`` makes the per-sample parameters from this object's own generator (``size`` = the frames' (h, w):
+    the shifts are drawn inside it); pass them back as ``params`` to replay a batch (tests do)."""
+
+    def __init__(self, p=0.5, threshold=0.5, beta=(0.1, 0.8), max_cells_log2=SYNTH_MAX_CELLS_LOG2, seed: Optional[int] = None):
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("p must lie in [0, 1]")
+        if not 0 <= int(max_cells_log2) <= SYNTH_MAX_CELLS_LOG2:
+            raise ValueError(f"max_cells_log2 must lie in 0..{SYNTH_MAX_CELLS_LOG2}")
+        self.p, self.threshold = float(p), float(threshold)
+        self.beta = (float(beta[0]), float(beta[1]))
+        self.max_cells_log2 = int(max_cells_log2)
+        self.gen = torch.Generator()
+        if seed is not None:
+            self.gen.manual_seed(int(seed))
+
+    def draw(self, n: int, size) -> dict:
+        h, w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+        g = self.gen
+
+        def ints(high, count=n):
+            return torch.randint(0, high, (count,), generator=g).tolist()
+
+        apply = (torch.rand(n, generator=g) < self.p).tolist()
+        cells_y = [1 << k for k in ints(self.max_cells_log2 + 1)]
+        cells_x = [1 << k for k in ints(self.max_cells_log2 + 1)]
+        beta = torch.empty(n).uniform_(self.beta[0], self.beta[1], generator=g).tolist()
+        src, shift_y, shift_x = ints(n), ints(h), ints(w)
+        perm, seed = ints(6), ints(1 << 32)
+        for i in range(n):
+            if src[i] == i and shift_y[i] == 0 and shift_x[i] == 0:      # a donor equal to the image would change nothing
+                if h * w == 1:
+                    apply[i] = False
+                else:
+                    shift_y[i], shift_x[i] = divmod(1 + ints(h * w - 1, 1)[0], w)
+        return {"apply": apply, "seed": seed, "cells_y": cells_y, "cells_x": cells_x, "beta": beta, "src": src,
+                "shift_y": shift_y, "shift_x": shift_x, "perm": perm}
+
+    def table(self, params: dict) -> np.ndarray:
+        return synth_table(len(params["apply"]), threshold=self.threshold, **params)
+
+    def __call__(self, images: torch.Tensor, masks: Optional[torch.Tensor] = None, params: Optional[dict] = None):
+        if params is None:
+            params = self.draw(images.shape[0], images.shape[-2:])
+        return synth_anomalies(images, self.table(params), masks)

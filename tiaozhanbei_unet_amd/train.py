@@ -6,7 +6,9 @@
     python -m tiaozhanbei_unet_amd.train --category bottle --epochs 2 [--precision bf16] [--synthetic]
     python -m torch.distributed.run --nproc-per-node 8 -m tiaozhanbei_unet_amd.train ...   (data parallel)
 
-Build-only additions: --precision {fp32,bf16}, --synthetic (generate an MVTec-layout toy dataset).
+Build-only additions: --precision {fp32,bf16}, --synthetic (generate an MVTec-layout toy dataset),
+--synthetic_anomalies P (corrupt each training image with probability P inside a Perlin mask, on the GPU, and train the
+network to give the clean image and that mask back: augment.AnomalySynthesizer; 0 = off) with --perlin_threshold T.
 `--model unet` trains the seg-only path (focal on sigmoid(logits)); in the reference that combination crashes
 (train_epoch unpacks two outputs, src/train_utils.py:122).  `--use_ssim` selects the SSIM reconstruction head
 (a dead flag in the reference, src/train.py:191-194).
@@ -47,6 +49,8 @@ FLAGS = [  # name, kwargs  -- reference src/train.py:38-97
     # build-only
     ("--precision", dict(type=str, default="fp32", choices=["fp32", "bf16"])),
     ("--synthetic", dict(action="store_true")),
+    ("--synthetic_anomalies", dict(type=float, default=0.0)),     # probability of corrupting a training image; 0 = off
+    ("--perlin_threshold", dict(type=float, default=0.5)),
 ]
 
 
@@ -147,13 +151,19 @@ def main(argv=None):
         start_epoch = load_checkpoint(core, optimizer, args.resume, device)[0] + 1
     net = DataParallel(model) if world > 1 else model
     hook = net.finish_gradients if world > 1 else None
+    corrupt = None
+    if args.synthetic_anomalies > 0.0:
+        from .augment import AnomalySynthesizer
+        # seeded per rank: data-parallel replicas draw different anomalies
+        corrupt = AnomalySynthesizer(p=args.synthetic_anomalies, threshold=args.perlin_threshold,
+                                     seed=args.seed * 65537 + rank)
 
     train_losses, val_losses, best = [], [], float("inf")
     for epoch in range(start_epoch, args.epochs):
         t0 = time.time()
         if hasattr(train_loader.sampler, "set_epoch"):
             train_loader.sampler.set_epoch(epoch)
-        tm = train_epoch(net, train_loader, criterion, optimizer, device, epoch, step_hook=hook)
+        tm = train_epoch(net, train_loader, criterion, optimizer, device, epoch, step_hook=hook, corrupt=corrupt)
         train_losses.append(tm["total_loss"])
         if scheduler and args.scheduler != "plateau":
             scheduler.step()

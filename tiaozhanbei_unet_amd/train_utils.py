@@ -83,13 +83,18 @@ def _batches(loader, device):
         yield batch, batch["image"].to(device, non_blocking=True), batch["mask"].to(device, non_blocking=True)
 
 
-def train_epoch(model, train_loader, criterion, optimizer, device, epoch, step_hook=None):
-    """One epoch; returns batch-size-weighted means under the reference's keys."""
+def train_epoch(model, train_loader, criterion, optimizer, device, epoch, step_hook=None, corrupt=None):
+    """One epoch; returns batch-size-weighted means under the reference's keys.  ``corrupt`` (None: the reference's loop)
+    = ``(images, masks) -> (inputs, masks)``, e.g. an augment.AnomalySynthesizer: the model sees ``inputs``, the
+    reconstruction target stays the clean ``images`` and the returned masks are the segmentation truth."""
     model.train()
     sums = torch.zeros(3, dtype=torch.float64, device=device)
     count = 0
     for _, images, masks in _batches(train_loader, device):
-        reconstruction, anomaly_map = model(images)
+        inputs = images
+        if corrupt is not None:
+            inputs, masks = corrupt(images, masks)
+        reconstruction, anomaly_map = model(inputs)
         losses = criterion(reconstruction, anomaly_map, images, masks)
         optimizer.zero_grad(set_to_none=True)
         losses["total_loss"].backward()
