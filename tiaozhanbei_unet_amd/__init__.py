@@ -9,7 +9,8 @@ from .model import (AnomalyUNet, DoubleConv, Down, OutConv, SegmentationUNet, UN
                     set_precision)
 from .train_utils import CombinedLoss, SSIMLoss, get_optimizer, get_scheduler, train_epoch, validate_epoch
 from .metrics import CombinedSegmentationLoss, SegmentationMetrics
+from .ops import parameters_written
 
-__all__ = ["AnomalyUNet", "UNet", "SegmentationUNet", "DoubleConv", "Down", "Up", "OutConv", "CombinedLoss", "SSIMLoss",
+__all__ = ["parameters_written","AnomalyUNet", "UNet", "SegmentationUNet", "DoubleConv", "Down", "Up", "OutConv", "CombinedLoss", "SSIMLoss",
            "train_epoch", "validate_epoch", "get_optimizer", "get_scheduler", "set_precision",
            "set_default_precision", "CombinedSegmentationLoss", "SegmentationMetrics"]

@@ -151,6 +151,7 @@ class GradientExchange:
         src = self._src if src is None else src
         for t in tensors:
             dist.broadcast(t.data if isinstance(t, torch.nn.Parameter) else t, src=src, group=self.group)
+        ops.parameters_written()           # ``t.data`` moves no version counter: a replica that already ran keeps no pack
 
     # -- per step ---------------------------------------------------------------------------------
     def _on_grad(self, p: torch.nn.Parameter) -> None:

@@ -51,6 +51,13 @@ class _HipBlock(nn.Module):
     def compute_dtype(self) -> torch.dtype:
         return _DTYPES[self.precision or _default_precision]
 
+    def __getstate__(self):
+        # the pack cache (_pack_cache) is keyed by the identity of THIS model's Parameters and owns a device buffer:
+        # a copy.deepcopy / pickle of the model carries neither and builds its own on its first forward
+        state = self.__dict__.copy()
+        state.pop("_packs", None)
+        return state
+
 
 def _conv_bn_relu(conv: nn.Conv2d, bn: nn.BatchNorm2d, x, x_up, first: bool = False, in_link=None, out_link=None,
                   head=None, pool=False, split=0):
@@ -238,12 +245,16 @@ def _pack_cache(model):
     """One batched weight-pack launch per parameter update for the whole model (ops.PackCache)."""
     dtype = model.compute_dtype
     cache = model.__dict__.get("_packs")
-    if cache is None or cache.dtype != dtype:
+    # the cache follows the model's CURRENT Parameter objects: load_state_dict(assign=True), module.to_empty() and the
+    # like replace them, after which the cached ones are somebody else's (and would be kept alive for nothing)
+    if cache is None or cache.dtype != dtype or any(holder["weight"] is not w for holder, w in cache.owners):
         cache = ops.PackCache(dtype)
+        cache.owners = owners = []       # (the holder module's _parameters dict, the weight the packs were made from)
         for mod in model.modules():
             if isinstance(mod, DoubleConv):
                 for idx in (0, 3):
                     w = mod.double_conv[idx].weight
+                    owners.append((mod.double_conv[idx]._parameters, w))
                     co, ci = ops._pad64(w.shape[0]), w.shape[1]
                     split = mod.skip_split if idx == 0 else 0
                     ctot = ops.seg_cols(ci, split)
@@ -251,9 +262,11 @@ def _pack_cache(model):
                     cache.add(w, ops.L.PACK_CONV_DGRAD, ctot, co, split)
             elif isinstance(mod, Up) and not mod.bilinear:
                 w = mod.up.weight
+                owners.append((mod.up._parameters, w))
                 ci, co = ops._pad64(w.shape[0]), ops._pad64(w.shape[1])
                 cache.add(w, ops.L.PACK_CONVT_FWD, co, ci)
                 cache.add(w, ops.L.PACK_CONVT_DGRAD, ci, co)
+        cache.witnesses = list(model.buffers())
         model.__dict__["_packs"] = cache
     cache.refresh(force=model.training)
     ops.set_active_packs(cache)

@@ -298,6 +298,10 @@ class PackCache:
         self.table = None
         self.ptrs = None
         self.gen = -1          # ops._train_generation when the packs were last written
+        self.wgen = -1         # ops._write_generation then (see get)
+        self.owners = []       # (model.py) where each cached weight lives in its model, to notice a replaced Parameter
+        self.witnesses = []    # (model.py) the model's buffers: a moved version counter of one of them means that
+        self.seen = None       # somebody rewrote the model's state (their counters at the last pack)
 
     def add(self, weight, mode, rows, k, split=0):
         """``split``: segment map of a 3x3 conv weight's input channels (unet_pack_desc.reserved; 0 = contiguous)."""
@@ -329,7 +333,10 @@ class PackCache:
         moving them, so a training forward always repacks: one ~0.1 ms launch).  An eval-mode forward repacks when
         ``_train_generation`` moved since the last pack: a fused optimiser step (``parameters_written``) changed the
         weights through raw pointers that no version counter sees -- also when every BatchNorm was frozen during the
-        step, so that no layer ran a training forward."""
+        step, so that no layer ran a training forward.  It also repacks when a version counter of one of the model's
+        BUFFERS moved: whoever rewrites a model wholesale writes those, too -- torch.optim.swa_utils.AveragedModel
+        syncs or averages them in every update_parameters, while the torch._foreach_lerp_ it averages the weights with
+        moves no version counter on the GPU (torch 2.10)."""
         if not self.items:
             return
         if self.table is None or self.ptrs != [w.data_ptr() for (w, _, _, _, _) in self.items]:
@@ -337,33 +344,41 @@ class PackCache:
             stale = True
         else:
             stale = force or self.gen != _train_generation or \
-                any(self.slots[(id(w), m)][3] != w._version for (w, m, _, _, _) in self.items)
+                any(self.slots[(id(w), m)][3] != w._version for (w, m, _, _, _) in self.items) or \
+                self.seen != [b._version for b in self.witnesses]
         if stale:
             L.check(L.lib().unet_pack_weights_batched(_ptr(self.table), len(self.items), _DT[self.dtype], _stream()),
                     "unet_pack_weights_batched")
             for (w, m, _, _, _) in self.items:
                 self.slots[(id(w), m)][3] = w._version
             self.gen = _train_generation
+            self.wgen = _write_generation
+            self.seen = [b._version for b in self.witnesses]
 
     def get(self, weight, mode, rows, k, split=0):
+        """The pack of ``weight`` if it is current: version counter unchanged and no ``parameters_written()`` since the
+        last refresh (a block of the model called on its own runs no refresh; it then takes a pack of its own)."""
         s_ = self.slots.get((id(weight), mode))
         if s_ is not None and s_[0] is not None and s_[1] == rows and s_[2] == k and s_[3] == weight._version \
-                and s_[4] == split:
+                and s_[4] == split and self.wgen == _write_generation:
             return s_[0]
         return None
 
 
-_active_packs = None
+_active_packs = None       # weak reference to the cache of the model that ran last (the model owns it: a deleted
+                           # model's packs and weights go with it)
 
 
 def set_active_packs(cache):
     global _active_packs
-    _active_packs = cache
+    import weakref
+    _active_packs = None if cache is None else weakref.ref(cache)
 
 
 def packed(weight, mode, rows, k, dtype, split=0):
-    if _active_packs is not None and _active_packs.dtype == dtype:
-        hit = _active_packs.get(weight, mode, rows, k, split)
+    cache = _active_packs() if _active_packs is not None else None
+    if cache is not None and cache.dtype == dtype:
+        hit = cache.get(weight, mode, rows, k, split)
         if hit is not None:
             return hit
     return pack_weight(weight, mode, rows, k, dtype, split)
@@ -431,15 +446,19 @@ FOLD_EVAL_BN = __import__("os").environ.get("UNET_FOLD_BN", "1") != "0"
 _folded = {}                                             # id(weight) -> (weakref to it, {(dtype, ctot): (stamp, payload)})
 _train_generation = 0                                    # bumped by every training forward (see below) and by
                                                          # parameters_written()
+_write_generation = 0                                    # bumped by parameters_written() alone
 
 
 def parameters_written():
     """To be called by whatever updates parameters (or BatchNorm buffers) through raw pointers, where no autograd version
     counter moves (optim.FusedAdam.step): every packed copy of them -- PackCache, the folded BatchNorm packs -- is stale
     from here on.  A training forward does the same for the running statistics its kernels write.  Both are host-side
-    counters: an update replayed from a captured graph does not run them, so whoever replays one calls this after it."""
-    global _train_generation
+    counters: an update replayed from a captured graph does not run them, so whoever replays one calls this after it.
+    The same holds for any write through ``param.data`` (``p.data.copy_()``, ``m.weight.data.normal_()``): it moves no
+    version counter either.  Exported as ``tiaozhanbei_unet_amd.parameters_written``."""
+    global _train_generation, _write_generation
     _train_generation += 1
+    _write_generation += 1
 
 
 def _folded_pack(weight, gamma, beta, running_mean, running_var, co, ctot, dtype, rows=None, split=0):
@@ -1903,3 +1922,4 @@ def adam_step_(param, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, we
     L.check(L.lib().unet_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(),
                                    lr, beta1, beta2, eps, weight_decay, grad_scale, int(step), _stream()),
             "unet_adam_step")
+    parameters_written()                   # raw-pointer update: no version counter moved
