@@ -190,11 +190,13 @@ def test_kolektorsdd_reader_contract(tmp_path):
 
 
 def test_inline_asm_dpp_reductions_keep_their_wait_states():
-    """The statistics epilogues reduce over DPP rows with inline-asm v_add_f32_dpp (csrc/igemm.hip, first.hip: row16_sum_n).
-    hipcc pads nothing inside an asm statement, so the helper's step-major order must leave two instructions between the
-    VALU write of a value and the DPP read of it: compile both sources to assembly (gfx950 cross-compile, no GPU) and scan
-    every DPP add (tools/check_dpp_hazards.py).  The same scan covers the inline-asm y loads of the fused BatchNorm-backward
-    epilogues: nothing may touch a load's destination VGPRs before its hand-counted s_waitcnt."""
+    """The statistics epilogues reduce over DPP rows with inline-asm v_add_f32_dpp (row16_sum_n of csrc/conv_common.h, used
+    by conv3_pdma.hip, conv3_ws.hip and first.hip).  hipcc pads nothing inside an asm statement, so the helper's step-major
+    order must leave two instructions between the VALU write of a value and the DPP read of it: compile the convolution
+    sources and first.hip to assembly (gfx950 cross-compile, no GPU) and scan every DPP add (tools/check_dpp_hazards.py).
+    The same scan covers the inline-asm y loads of the fused BatchNorm-backward epilogues: nothing may touch a load's
+    destination VGPRs before its hand-counted s_waitcnt."""
+    import re
     import shutil
     import subprocess
     if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
@@ -202,11 +204,19 @@ def test_inline_asm_dpp_reductions_keep_their_wait_states():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_dpp_hazards.py")], capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert "igemm.hip: " in r.stdout and " 0 hazards" in r.stdout
-    assert "inline-asm y loads, 0 used before their hand-counted wait" in r.stdout, r.stdout
+    hazards = dict(re.findall(r"^(\w+\.hip): \d+ DPP adds, (\d+) hazards$", r.stdout, re.M))
+    assert set(hazards) == {"igemm.hip", "conv3.hip", "conv3_pdma.hip", "conv3_ws.hip", "convt_ws.hip", "conv_api.hip",
+                            "first.hip"} and set(hazards.values()) == {"0"}, r.stdout
+    # the helper is shared: a file dropped from the scan list would show as missing adds (1280 were in igemm.hip before
+    # it was split by kernel family, 128 in first.hip)
+    assert "convolution files + first.hip: 1408 DPP adds" in r.stdout, r.stdout
+    early = re.findall(r"inline-asm y loads, (\d+) used before their hand-counted wait", r.stdout)
+    assert len(early) == 6 and set(early) == {"0"}, r.stdout
     # ... and the kernels whose vmcnt waits are hand-counted over an exact DMA / load / store sequence do not spill (a scratch
     # access would be one more operation in that sequence)
-    assert "igemm.hip: 16 kernels with hand-counted vmcnt waits, 0 with scratch traffic" in r.stdout, r.stdout
+    spills = re.findall(r"kernels with hand-counted vmcnt waits, (\d+) with scratch traffic", r.stdout)
+    assert len(spills) == 7 and set(spills) == {"0"}, r.stdout
+    assert "convolution files: 12 inline-asm y loads, 16 kernels with hand-counted vmcnt waits" in r.stdout, r.stdout
     assert "wgrad.hip: 2 kernels with hand-counted vmcnt waits, 0 with scratch traffic" in r.stdout, r.stdout
 
 

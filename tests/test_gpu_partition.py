@@ -44,8 +44,8 @@ def ceil8(a):
 
 
 # ------------------------------------------------------------------ the case table
-# family, kernel bracket, shape, note.  Shapes: N, channels, H, W of the launch frame.  Dispatch rules (igemm.hip
-# dispatch<bf16, 9> / launch_pdma, wgrad.hip run<>): 64 input channels on one source -> launch_ws, which takes
+# family, kernel bracket, shape, note.  Shapes: N, channels, H, W of the launch frame.  Dispatch rules (conv_api.hip
+# dispatch<bf16, 9>, conv3_pdma.hip launch_pdma, wgrad.hip run<>): 64 input channels on one source -> conv3_ws.hip:
 # conv3_ws16_kernel on 16-aligned dense frames and conv3_ws_kernel otherwise (one bracket name, "conv3_ws_kernel");
 # >= 128 input channels on 16-aligned frames -> launch_pdma<128> if c_out % 128 == 0 else <64>; in launch_pdma
 # "pp" = BN == 128 && Ctot >= 512 (ping-pong), "pair" = BN == 64 && !pp && Ctot == 128 (pdma64x2), else lock-step --
@@ -132,8 +132,8 @@ IDS = [f"{c[0]}-{c[1].split()[0]}-" + "x".join(str(v) for v in c[2].values()) fo
 
 # ------------------------------------------------------------------ restatement of the launchers' partition (coverage)
 def plan(case, budget):
-    """the budget branches a launch of this case takes (igemm.hip launch_pdma / launch_ws / launch_convt_ws /
-    launch_convt_dgrad_ws, wgrad.hip make_plan / make_plan16 / launch_convt_wgrad_ws), as a set of tags"""
+    """the budget branches a launch of this case takes (conv3_pdma.hip launch_pdma, conv3_ws.hip unet_internal_conv3_ws, convt_ws.hip
+    launch_convt_ws / launch_convt_dgrad_ws, wgrad.hip make_plan / make_plan16 / launch_convt_wgrad_ws), as a set of tags"""
     fam, kern, s, _ = case
     tags = set()
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Outline of a kernel in hipcc -S output: positions of MFMAs, barriers, LDS-DMAs, stores, scratch (spill) traffic.
-    python tools/asm_outline.py /tmp/igemm.s conv3_ws16_kernelILb0ELi2E"""
+    python tools/asm_outline.py /tmp/conv3_ws.s conv3_ws16_kernelILb0ELi2E"""
 import sys
 
 s = open(sys.argv[1]).read()

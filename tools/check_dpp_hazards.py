@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Static checks of hand-scheduled inline asm.
 
-(1) The inline-asm DPP reductions (row16_sum_n in csrc/igemm.hip, first.hip): hipcc pads nothing inside an asm
-statement, so a `v_add_f32_dpp` must not read a VGPR that one of the two preceding instructions wrote (2 wait states).
+(1) The inline-asm DPP reductions (row16_sum_n of csrc/conv_common.h, used by conv3_pdma.hip, conv3_ws.hip and first.hip):
+hipcc pads nothing inside an asm statement, so a `v_add_f32_dpp` must not read a VGPR that one of the two preceding instructions wrote (2 wait states).
 (2) The inline-asm `buffer_load_dwordx4 ... offen` y loads of the fused BatchNorm-backward epilogues (conv3_ws16_kernel<.., 2>,
 conv3_ws_kernel<.., 2>, convt_dgrad_ws_kernel<64, true>): their only ordering against use is a hand-counted `s_waitcnt vmcnt(n)`
 dozens of MFMAs later (hipcc does not count LDS-DMAs, so its own wait would drain them).  The compiler treats the destination as
@@ -11,7 +11,8 @@ any of its destination VGPRs (a register-allocator change would other
 wrong ReLU masks and BatchNorm-backward sums).
 (3) Kernels with hand-counted `s_waitcnt vmcnt(n)` (the LDS-DMA convolution / weight-gradient kernels) must not spill: scratch traffic
 would join the counted stream (scan_no_scratch).
-Compiles the sources to assembly (hipcc -S, gfx950, no GPU needed) and scans.
+Compiles the convolution sources (CONV_SRCS), first.hip and wgrad.hip to assembly (hipcc -S, gfx950, no GPU needed) and
+scans.
 
     python tools/check_dpp_hazards.py          # exit code 1 on a hazard
 """
@@ -135,32 +136,42 @@ NO_SPILL_KERNELS = ("conv3_ws16_kernel", "conv3_pdma", "conv3_pp", "convt_ws_ker
 Y_LOAD_KERNELS = ("conv3_ws16_kernelILb0ELi2E", "conv3_ws_kernelILb0ELi2E", "convt_dgrad_ws_kernelILi64ELb1E")
 
 
+# the convolution kernel families and their entry points
+CONV_SRCS = ("igemm.hip", "conv3.hip", "conv3_pdma.hip", "conv3_ws.hip", "convt_ws.hip", "conv_api.hip")
+
+
 def main():
     total_bad = 0
+    dpp = y_loads = no_spill = 0
     with tempfile.TemporaryDirectory() as tmp:
-        for src in ("igemm.hip", "first.hip"):
+        for src in CONV_SRCS + ("first.hip", "wgrad.hip"):
             out = os.path.join(tmp, src + ".s")
             subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S",
                                    "--cuda-device-only", os.path.join(ROOT, "tiaozhanbei_unet_amd", "csrc", src), "-o", out])
-            n, bad = scan(out)
-            print(f"{src}: {n} DPP adds, {bad} hazards")
-            total_bad += bad
-            if src == "igemm.hip":
+            if src != "wgrad.hip":
+                n, bad = scan(out)
+                print(f"{src}: {n} DPP adds, {bad} hazards")
+                dpp += n
+                total_bad += bad
+            if src in CONV_SRCS:
                 n2, bad2 = scan_inline_loads(out, Y_LOAD_KERNELS)
                 print(f"{src}: {n2} inline-asm y loads, {bad2} used before their hand-counted wait")
+                y_loads += n2
                 total_bad += bad2
-                if n2 < 12:
-                    print("expected at least 12 inline-asm y loads (3 kernel families x 4)")
-                    total_bad += 1
+            if src != "first.hip":
                 n3, bad3 = scan_no_scratch(out, NO_SPILL_KERNELS)
                 print(f"{src}: {n3} kernels with hand-counted vmcnt waits, {bad3} with scratch traffic")
-                total_bad += bad3 + (n3 < 12)
-        out = os.path.join(tmp, "wgrad.hip.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S",
-                               "--cuda-device-only", os.path.join(ROOT, "tiaozhanbei_unet_amd", "csrc", "wgrad.hip"), "-o", out])
-        n3, bad3 = scan_no_scratch(out, NO_SPILL_KERNELS)
-        print(f"wgrad.hip: {n3} kernels with hand-counted vmcnt waits, {bad3} with scratch traffic")
-        total_bad += bad3 + (n3 < 2)
+                total_bad += bad3
+                if src == "wgrad.hip":
+                    total_bad += n3 < 2
+                else:
+                    no_spill += n3
+    print(f"convolution files + first.hip: {dpp} DPP adds")
+    print(f"convolution files: {y_loads} inline-asm y loads, {no_spill} kernels with hand-counted vmcnt waits")
+    if y_loads < 12:
+        print("expected at least 12 inline-asm y loads (3 kernel families x 4)")
+        total_bad += 1
+    total_bad += no_spill < 12
     sys.exit(1 if total_bad else 0)
 
 
