@@ -17,6 +17,7 @@
  *     all work is enqueued on `stream` (a hipStream_t passed as void*).
  *   - return value: UNET_OK (0) or a negative unet_status; unet_last_error() gives the
  *     thread-local text of the last failure.  No C++ exception crosses the ABI.
+ *     A dtype other than UNET_F32 / UNET_BF16 is UNET_ERR_BAD_ARG, reported before anything is launched.
  *   - `unet_view` places an NHWC tensor inside a larger logical frame: it is how the
  *     skip-concat (`torch.cat([x2, x1], 1)`, src/model.py:65) and the centre pad
  *     (`F.pad`, src/model.py:57-61) are expressed without ever materialising them.
@@ -294,7 +295,8 @@ int32_t unet_bn_relu_bwd_frozen(int32_t dtype, const void* da, const void* y, in
  * the two per-channel sums behind (unet_head_bnrelu_bwd, unet_conv3x3_dgrad_bnrelu): dz = da*[z>0] (compute dtype,
  * NHWC), partial = fp32 [n_parts][2][c] holding sum dz and sum dz*(y - mean).  Ordered fp64 finalize -> dgamma, dbeta,
  * then ONE pass dy = A*dz + B*y + K (dy may alias dz).  workspace: 3*c floats = A, B, K on return; dy = NULL skips the
- * pass (dz / y may then be NULL too): the caller's consumer applies the coefficients (unet_conv3x3_first_wgrad_bn). */
+ * pass (dz / y may then be NULL too, and dtype is not looked at): the caller's consumer applies the coefficients
+ * (unet_conv3x3_first_wgrad_bn). */
 int32_t unet_bn_bwd_premasked(int32_t dtype, const void* dz, const void* y, int64_t pixels, int32_t c,
                               const float* gamma, const float* save_mean, const float* save_istd,
                               const float* partial, int32_t n_parts, float* dgamma, float* dbeta, void* dy,

@@ -244,3 +244,74 @@ def test_fused_adam_takes_a_torch_adam_state_dict():
         again = FusedAdam([torch.nn.Parameter(p.detach().clone()) for p in ps], lr=1e-3)
         again.load_state_dict(fused.state_dict())
         assert again.param_groups[0]["decoupled"] is dec
+
+
+def test_every_entry_point_refuses_an_unknown_dtype(libpath):
+    """include/unet_hip.h: a dtype other than UNET_F32 / UNET_BF16 is UNET_ERR_BAD_ARG, reported before anything is
+    launched.  Every entry point that takes a dtype (found in the header, so a new one cannot be forgotten) is called with
+    dtype = 7 and otherwise valid, smallest arguments: status -1, unet_last_error() names the entry point and the dtype,
+    and the _supported queries answer 0.  A launcher that treated 7 as fp32 would get to its launch instead: status -4
+    without a GPU, 0 with one -- where it stays inside the buffers, which are sized for fp32."""
+    from tiaozhanbei_unet_amd import _lib
+    lib = _lib.lib()
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "unet_hip.h")).read(), flags=re.S)
+    entries = {m.group(1): [a.strip() for a in m.group(2).split(",")]
+               for m in re.finditer(r"\b(unet_[a-z0-9_]+)\s*\(([^;{()]*)\)\s*;", header)
+               if re.search(r"\bdtype\b", m.group(2))}
+    assert len(entries) >= 40 and set(entries) <= set(_lib.SIGNATURES)
+
+    dev = "cuda" if torch.cuda.is_available() else "cpu"
+    keep = []                                               # (the buffers live until the end of the test)
+
+    def buf(nbytes=9 * 64 * 64 * 4):                        # one fp32 64 x 64 3x3 weight: the largest tensor of any call
+        keep.append(torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=dev))
+        return keep[-1].data_ptr()
+
+    def views():
+        return _lib.View2(_lib.View(buf(), 64, 2, 2, 0, 0), _lib.View(None, 0, 0, 0, 0, 0))
+
+    ints = {"dtype": 7, "src_dtype": _lib.UNET_F32, "n": 1, "h": 2, "w": 2, "pixels": 4, "hw": 4, "c": 64, "c_pad": 64,
+            "c_in": 64, "c_out": 64, "c_dy": 64, "c_dx": 64, "c_in_param": 64, "rows": 64, "k": 64, "dst_split": 64,
+            "mode": _lib.PACK_CONV_FWD, "split": 0, "accumulate": 0, "kclass": _lib.K_CONV_FWD, "relu": 0, "sigmoid": 0,
+            "n_parts": 1, "momentum": 0.1, "eps": 1e-5}
+    own = {"unet_convt2x2_dgrad_bnrelu": {"c_in": 128}}     # (the one shape it offers: 128 <- 64 channels)
+    own.update({name: {"c_out": 1} for name in entries if name.startswith("unet_head_")})
+    workspace = {"unet_conv3x3_wgrad": lambda v: lib.unet_conv3x3_wgrad_workspace(1, 2, 2, 64, 64),
+                 "unet_convt2x2_wgrad": lambda v: lib.unet_convt2x2_wgrad_workspace(1, 2, 2, 64, 64),
+                 "unet_head_": lambda v: lib.unet_head_bwd_workspace(1, 2, 2, v["c_in"], v["c_out"]),
+                 "unet_bn_": lambda v: lib.unet_bn_workspace(4, 64)}
+    for name, params in sorted(entries.items()):
+        values = dict(ints, **own.get(name, {}))
+        ws_bytes = next((f(values) for prefix, f in workspace.items() if name.startswith(prefix)), 0)
+        args = []
+        for param in params:
+            ptype, pname = re.match(r"(.*?)(\w+)(?:\[2\])?$", param).groups()
+            if "unet_view" in ptype:
+                args.append(views())
+            elif pname == "stream":
+                args.append(None)
+            elif pname == "workspace":
+                args.append(buf(ws_bytes))
+            elif pname == "workspace_bytes":
+                args.append(ws_bytes)
+            elif pname == "strides":                        # (host array: NCHW strides of a [1][64][2][2] tensor)
+                keep.append((ctypes.c_int64 * 4)(256, 4, 2, 1))
+                args.append(ctypes.addressof(keep[-1]))
+            elif pname == "n_parts" and "*" in ptype:       # (host int the launcher writes)
+                keep.append(ctypes.c_int32(0))
+                args.append(ctypes.addressof(keep[-1]))
+            elif pname == "descs":                          # (device table of one unet_pack_desc)
+                rec = [buf(), buf()] + [v << 32 | u for u, v in ((64, 64), (64, 64), (_lib.PACK_CONV_FWD, 0))]
+                keep.append(torch.tensor(rec, dtype=torch.int64, device=dev))
+                args.append(keep[-1].data_ptr())
+            elif "*" in ptype:
+                args.append(buf())
+            else:
+                args.append(values[pname])                  # KeyError: a new parameter name needs a value above
+        assert len(args) == len(_lib.SIGNATURES[name][1]), name
+        rc = getattr(lib, name)(*args)
+        if name.endswith("_supported"):
+            assert rc == 0, name
+        else:
+            err = lib.unet_last_error()
+            assert rc == -1 and name.encode() + b":" in err and b"dtype 7" in err, (name, rc, err)

@@ -381,6 +381,30 @@ int32_t launch_reduce(const void* y, const void* da, long long pixels, int C, co
 
 inline int ew_blocks(long long pieces) { return (int)std::min<long long>(cdiv64(pieces, 512), 256 * 8); }
 
+// The grid of a kernel<T, FAST> family over the 16-byte pieces of a [pixels][c] tensor: launch(fast, grid, pieces) starts
+// the kernel<T, decltype(fast)::value>.  FAST: 256 * PIECE is a multiple of c, so a thread meets the same channels in
+// every iteration and keeps their coefficients in registers.
+template <typename T, typename F>
+void launch_pieces(long long pixels, int c, F&& launch) {
+  const long long pieces = pixels * c / ET<T>::PIECE;
+  const dim3 grid(ew_blocks(pieces));
+  if ((256 * ET<T>::PIECE) % c == 0) launch(std::true_type{}, grid, pieces);
+  else launch(std::false_type{}, grid, pieces);
+}
+
+// dgamma, dbeta and the coefficients (A, B, K) of the apply pass from the partial sums; mode: see bn_finalize_bwd_kernel
+int32_t launch_finalize_bwd(const float* part, int n_parts, int c, int64_t pixels, const float* gamma, const float* mean,
+                            const float* istd, float* dgamma, float* dbeta, float* coefs, int mode, hipStream_t s) {
+  const float inv = (float)(1.0 / (double)pixels);
+  if (n_parts >= 128)      // latency-bound: 64 partial-lanes per channel, fewer dependent loads per thread
+    hipLaunchKernelGGL((bn_finalize_bwd_kernel<64, 4>), dim3(c / 4), dim3(256), 0, s, part, n_parts, c, inv, gamma, mean,
+                       istd, dgamma, dbeta, coefs, mode);
+  else
+    hipLaunchKernelGGL((bn_finalize_bwd_kernel<FL, FC>), dim3(c / FC), dim3(256), 0, s, part, n_parts, c, inv, gamma, mean,
+                       istd, dgamma, dbeta, coefs, mode);
+  return unet_check_launch("bn_finalize_bwd_kernel");
+}
+
 }  // namespace
 
 extern "C" size_t unet_bn_workspace(int64_t pixels, int32_t c) {
@@ -399,23 +423,25 @@ int32_t unet_internal_colsum(int dtype, const void* x, int64_t pixels, int C, fl
     pl.rows_per_block = (int)(cdiv64(cdiv64(pixels, fit), 32) * 32);
     pl.nparts = (int)cdiv64(pixels, pl.rows_per_block);
   }
-  int32_t rc = dtype == UNET_BF16
-                   ? launch_reduce<bf16_t, 2>(x, nullptr, pixels, C, nullptr, nullptr, nullptr, nullptr, ws, pl, s)
-                   : launch_reduce<float, 2>(x, nullptr, pixels, C, nullptr, nullptr, nullptr, nullptr, ws, pl, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(colsum_finalize_kernel, dim3(C / FC), dim3(256), 0, s, ws, pl.nparts, C, out);
-  return unet_check_launch("colsum_finalize_kernel");
+  return with_dtype("colsum", dtype, [&](auto tag) -> int32_t {
+    using T = decltype(tag);
+    int32_t rc = launch_reduce<T, 2>(x, nullptr, pixels, C, nullptr, nullptr, nullptr, nullptr, ws, pl, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(colsum_finalize_kernel, dim3(C / FC), dim3(256), 0, s, ws, pl.nparts, C, out);
+    return unet_check_launch("colsum_finalize_kernel");
+  });
 }
 
 int32_t unet_internal_bn_partials(int dtype, const void* y, int64_t pixels, int C, float* part, int* n_parts,
                                   hipStream_t s) {
   UNET_REQUIRE(C % 64 == 0, UNET_ERR_UNSUPPORTED, "bn partials: channels %d not a multiple of 64", C);
   const RedPlan pl = red_plan(pixels, C);
-  ProfScope prof(UNET_K_BN, 0.0, s);
-  *n_parts = pl.nparts;
-  return dtype == UNET_BF16
-             ? launch_reduce<bf16_t, 0>(y, nullptr, pixels, C, nullptr, nullptr, nullptr, nullptr, part, pl, s)
-             : launch_reduce<float, 0>(y, nullptr, pixels, C, nullptr, nullptr, nullptr, nullptr, part, pl, s);
+  return with_dtype("bn partials", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    ProfScope prof(UNET_K_BN, 0.0, s);
+    *n_parts = pl.nparts;
+    return launch_reduce<T, 0>(y, nullptr, pixels, C, nullptr, nullptr, nullptr, nullptr, part, pl, s);
+  });
 }
 
 extern "C" int32_t unet_bn_finalize_partials(const float* partial, int32_t n_parts, int64_t pixels, int32_t c,
@@ -455,16 +481,17 @@ extern "C" int32_t unet_bn_train_stats(int32_t dtype, const void* y, int64_t pix
   UNET_REQUIRE(workspace_bytes >= (size_t)pl.nparts * 2 * c * sizeof(float), UNET_ERR_WORKSPACE,
                "unet_bn_train_stats: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_BN, 0.0, s);
-  float* part = (float*)workspace;
-  int32_t rc = dtype == UNET_BF16
-                   ? launch_reduce<bf16_t, 0>(y, nullptr, pixels, c, nullptr, nullptr, nullptr, nullptr, part, pl, s)
-                   : launch_reduce<float, 0>(y, nullptr, pixels, c, nullptr, nullptr, nullptr, nullptr, part, pl, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL((bn_finalize_train_kernel<FL, FC>), dim3(c / FC), dim3(256), 0, s, part, pl.nparts, c,
-                     (double)pixels, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_istd, scale,
-                     shift);
-  return unet_check_launch("bn_finalize_train_kernel");
+  return with_dtype("unet_bn_train_stats", dtype, [&](auto tag) -> int32_t {
+    using T = decltype(tag);
+    ProfScope prof(UNET_K_BN, 0.0, s);
+    float* part = (float*)workspace;
+    int32_t rc = launch_reduce<T, 0>(y, nullptr, pixels, c, nullptr, nullptr, nullptr, nullptr, part, pl, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL((bn_finalize_train_kernel<FL, FC>), dim3(c / FC), dim3(256), 0, s, part, pl.nparts, c,
+                       (double)pixels, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_istd,
+                       scale, shift);
+    return unet_check_launch("bn_finalize_train_kernel");
+  });
 }
 
 extern "C" int32_t unet_bn_eval_coeffs(int32_t c, const float* gamma, const float* beta,
@@ -492,89 +519,61 @@ extern "C" int32_t unet_bn_relu_apply(int32_t dtype, const void* y, int64_t pixe
   UNET_REQUIRE(y && scale && shift && a, UNET_ERR_BAD_ARG, "unet_bn_relu_apply: null pointer");
   UNET_REQUIRE(pixels > 0 && c > 0 && c % 8 == 0, UNET_ERR_UNSUPPORTED, "unet_bn_relu_apply: c=%d", c);
   hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_BN, 0.0, s);
-  if (dtype == UNET_BF16) {
-    const long long pieces = pixels * c / 8;
-    if ((256 * 8) % c == 0)
-      hipLaunchKernelGGL((bn_relu_apply_kernel<bf16_t, true>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const bf16_t*)y, pieces, c, scale, shift, (bf16_t*)a);
-    else
-      hipLaunchKernelGGL((bn_relu_apply_kernel<bf16_t, false>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const bf16_t*)y, pieces, c, scale, shift, (bf16_t*)a);
-  } else {
-    const long long pieces = pixels * c / 4;
-    if ((256 * 4) % c == 0)
-      hipLaunchKernelGGL((bn_relu_apply_kernel<float, true>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const float*)y, pieces, c, scale, shift, (float*)a);
-    else
-      hipLaunchKernelGGL((bn_relu_apply_kernel<float, false>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const float*)y, pieces, c, scale, shift, (float*)a);
-  }
-  return unet_check_launch("bn_relu_apply_kernel");
+  return with_dtype("unet_bn_relu_apply", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    ProfScope prof(UNET_K_BN, 0.0, s);
+    launch_pieces<T>(pixels, c, [&](auto fast, dim3 grid, long long pieces) {
+      hipLaunchKernelGGL((bn_relu_apply_kernel<T, decltype(fast)::value>), grid, dim3(256), 0, s, (const T*)y, pieces, c,
+                         scale, shift, (T*)a);
+    });
+    return unet_check_launch("bn_relu_apply_kernel");
+  });
 }
 
-static int32_t bn_relu_bwd_impl(int32_t dtype, const void* da, const void* y, int64_t pixels, int32_t c,
+static int32_t bn_relu_bwd_impl(const char* who, int32_t dtype, const void* da, const void* y, int64_t pixels, int32_t c,
                                 const float* gamma, const float* save_mean, const float* save_istd,
                                 const float* scale, const float* shift, float* dgamma, float* dbeta,
                                 void* dy, void* workspace, size_t workspace_bytes, void* stream, int frozen) {
   UNET_REQUIRE(da && y && gamma && save_mean && save_istd && scale && shift && dgamma && dbeta && dy && workspace,
-               UNET_ERR_BAD_ARG, "unet_bn_relu_bwd: null pointer");
-  UNET_REQUIRE(pixels > 0 && c > 0 && c % 64 == 0, UNET_ERR_UNSUPPORTED, "unet_bn_relu_bwd: c=%d", c);
+               UNET_ERR_BAD_ARG, "%s: null pointer", who);
+  UNET_REQUIRE(pixels > 0 && c > 0 && c % 64 == 0, UNET_ERR_UNSUPPORTED, "%s: c=%d", who, c);
   const RedPlan pl = red_plan(pixels, c);
   const size_t part_bytes = (size_t)pl.nparts * 2 * c * sizeof(float);
   UNET_REQUIRE(workspace_bytes >= part_bytes + (size_t)3 * c * sizeof(float), UNET_ERR_WORKSPACE,
-               "unet_bn_relu_bwd: workspace too small");
+               "%s: workspace too small", who);
   hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_BN, 0.0, s);
-  float* part = (float*)workspace;
-  float* coefs = part + (size_t)pl.nparts * 2 * c;
-  int32_t rc = dtype == UNET_BF16
-                   ? launch_reduce<bf16_t, 1>(y, da, pixels, c, scale, shift, save_mean, save_istd, part, pl, s)
-                   : launch_reduce<float, 1>(y, da, pixels, c, scale, shift, save_mean, save_istd, part, pl, s);
-  if (rc) return rc;
-  const float inv = (float)(1.0 / (double)pixels);
-  if (pl.nparts >= 128)      // latency-bound: 64 partial-lanes per channel
-    hipLaunchKernelGGL((bn_finalize_bwd_kernel<64, 4>), dim3(c / 4), dim3(256), 0, s, part, pl.nparts, c, inv, gamma,
-                       save_mean, save_istd, dgamma, dbeta, coefs, frozen ? 2 : 0);
-  else
-    hipLaunchKernelGGL((bn_finalize_bwd_kernel<FL, FC>), dim3(c / FC), dim3(256), 0, s, part, pl.nparts, c, inv, gamma,
-                       save_mean, save_istd, dgamma, dbeta, coefs, frozen ? 2 : 0);
-  rc = unet_check_launch("bn_finalize_bwd_kernel");
-  if (rc) return rc;
-  if (dtype == UNET_BF16) {
-    const long long pieces = pixels * c / 8;
-    if ((256 * 8) % c == 0)
-      hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<bf16_t, true>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const bf16_t*)da, (const bf16_t*)y, pieces, c, scale, shift, coefs, (bf16_t*)dy);
-    else
-      hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<bf16_t, false>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const bf16_t*)da, (const bf16_t*)y, pieces, c, scale, shift, coefs, (bf16_t*)dy);
-  } else {
-    const long long pieces = pixels * c / 4;
-    if ((256 * 4) % c == 0)
-      hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<float, true>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const float*)da, (const float*)y, pieces, c, scale, shift, coefs, (float*)dy);
-    else
-      hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<float, false>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const float*)da, (const float*)y, pieces, c, scale, shift, coefs, (float*)dy);
-  }
-  return unet_check_launch("bn_relu_bwd_apply_kernel");
+  return with_dtype(who, dtype, [&](auto tag) -> int32_t {
+    using T = decltype(tag);
+    ProfScope prof(UNET_K_BN, 0.0, s);
+    float* part = (float*)workspace;
+    float* coefs = part + (size_t)pl.nparts * 2 * c;
+    int32_t rc = launch_reduce<T, 1>(y, da, pixels, c, scale, shift, save_mean, save_istd, part, pl, s);
+    if (rc) return rc;
+    rc = launch_finalize_bwd(part, pl.nparts, c, pixels, gamma, save_mean, save_istd, dgamma, dbeta, coefs,
+                             frozen ? 2 : 0, s);
+    if (rc) return rc;
+    launch_pieces<T>(pixels, c, [&](auto fast, dim3 grid, long long pieces) {
+      hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<T, decltype(fast)::value>), grid, dim3(256), 0, s, (const T*)da,
+                         (const T*)y, pieces, c, scale, shift, coefs, (T*)dy);
+    });
+    return unet_check_launch("bn_relu_bwd_apply_kernel");
+  });
 }
 
 extern "C" int32_t unet_bn_relu_bwd(int32_t dtype, const void* da, const void* y, int64_t pixels, int32_t c,
                                     const float* gamma, const float* save_mean, const float* save_istd,
                                     const float* scale, const float* shift, float* dgamma, float* dbeta,
                                     void* dy, void* workspace, size_t workspace_bytes, void* stream) {
-  return bn_relu_bwd_impl(dtype, da, y, pixels, c, gamma, save_mean, save_istd, scale, shift, dgamma, dbeta, dy, workspace,
-                          workspace_bytes, stream, 0);
+  return bn_relu_bwd_impl("unet_bn_relu_bwd", dtype, da, y, pixels, c, gamma, save_mean, save_istd, scale, shift, dgamma,
+                          dbeta, dy, workspace, workspace_bytes, stream, 0);
 }
 
 extern "C" int32_t unet_bn_relu_bwd_frozen(int32_t dtype, const void* da, const void* y, int64_t pixels, int32_t c,
                                            const float* gamma, const float* mean, const float* istd, const float* scale,
                                            const float* shift, float* dgamma, float* dbeta, void* dy, void* workspace,
                                            size_t workspace_bytes, void* stream) {
-  return bn_relu_bwd_impl(dtype, da, y, pixels, c, gamma, mean, istd, scale, shift, dgamma, dbeta, dy, workspace,
-                          workspace_bytes, stream, 1);
+  return bn_relu_bwd_impl("unet_bn_relu_bwd_frozen", dtype, da, y, pixels, c, gamma, mean, istd, scale, shift, dgamma,
+                          dbeta, dy, workspace, workspace_bytes, stream, 1);
 }
 
 extern "C" int32_t unet_bn_bwd_premasked(int32_t dtype, const void* dz, const void* y, int64_t pixels, int32_t c,
@@ -586,38 +585,19 @@ extern "C" int32_t unet_bn_bwd_premasked(int32_t dtype, const void* dz, const vo
   UNET_REQUIRE(pixels > 0 && c > 0 && c % FC == 0 && n_parts > 0, UNET_ERR_UNSUPPORTED, "unet_bn_bwd_premasked: c=%d", c);
   UNET_REQUIRE(workspace_bytes >= (size_t)3 * c * sizeof(float), UNET_ERR_WORKSPACE,
                "unet_bn_bwd_premasked: workspace too small");
+  // coefficients only (dy == NULL): nothing of the dtype's is read or written, and it is not looked at
+  UNET_REQUIRE(!dy || dtype_known(dtype), UNET_ERR_BAD_ARG, "unet_bn_bwd_premasked: dtype %d", dtype);
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof(UNET_K_BN, 0.0, s);
   float* coefs = (float*)workspace;
-  const float inv = (float)(1.0 / (double)pixels);
-  if (n_parts >= 128)
-    hipLaunchKernelGGL((bn_finalize_bwd_kernel<64, 4>), dim3(c / 4), dim3(256), 0, s, partial, n_parts, c, inv, gamma,
-                       save_mean, save_istd, dgamma, dbeta, coefs, 1);
-  else
-    hipLaunchKernelGGL((bn_finalize_bwd_kernel<FL, FC>), dim3(c / FC), dim3(256), 0, s, partial, n_parts, c, inv, gamma,
-                       save_mean, save_istd, dgamma, dbeta, coefs, 1);
-  int32_t rc = unet_check_launch("bn_finalize_bwd_kernel");
-  if (rc) return rc;
-  if (!dy) return UNET_OK;       // coefficients only: the consumer of dy applies them itself (unet_conv3x3_first_wgrad_bn)
-  if (dtype == UNET_BF16) {
-    const long long pieces = pixels * c / 8;
-    if ((256 * 8) % c == 0)
-      hipLaunchKernelGGL((bn_bwd_apply_premasked_kernel<bf16_t, true>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const bf16_t*)dz, (const bf16_t*)y, pieces, c, coefs, (bf16_t*)dy);
-    else
-      hipLaunchKernelGGL((bn_bwd_apply_premasked_kernel<bf16_t, false>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const bf16_t*)dz, (const bf16_t*)y, pieces, c, coefs, (bf16_t*)dy);
-  } else if (dtype == UNET_F32) {
-    const long long pieces = pixels * c / 4;
-    if ((256 * 4) % c == 0)
-      hipLaunchKernelGGL((bn_bwd_apply_premasked_kernel<float, true>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const float*)dz, (const float*)y, pieces, c, coefs, (float*)dy);
-    else
-      hipLaunchKernelGGL((bn_bwd_apply_premasked_kernel<float, false>), dim3(ew_blocks(pieces)), dim3(256), 0, s,
-                         (const float*)dz, (const float*)y, pieces, c, coefs, (float*)dy);
-  } else {
-    unet_set_error("unet_bn_bwd_premasked: dtype %d", dtype);
-    return UNET_ERR_BAD_ARG;
-  }
-  return unet_check_launch("bn_bwd_apply_premasked_kernel");
+  int32_t rc = launch_finalize_bwd(partial, n_parts, c, pixels, gamma, save_mean, save_istd, dgamma, dbeta, coefs, 1, s);
+  if (rc || !dy) return rc;      // coefficients only: the consumer of dy applies them itself (unet_conv3x3_first_wgrad_bn)
+  return with_dtype("unet_bn_bwd_premasked", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    launch_pieces<T>(pixels, c, [&](auto fast, dim3 grid, long long pieces) {
+      hipLaunchKernelGGL((bn_bwd_apply_premasked_kernel<T, decltype(fast)::value>), grid, dim3(256), 0, s, (const T*)dz,
+                         (const T*)y, pieces, c, coefs, (T*)dy);
+    });
+    return unet_check_launch("bn_bwd_apply_premasked_kernel");
+  });
 }

@@ -108,6 +108,17 @@ template <> struct Vec<bf16_t> {
   }
 };
 
+static inline bool dtype_known(int dtype) { return dtype == UNET_F32 || dtype == UNET_BF16; }
+// The one way from a runtime dtype to an element type: f(bf16_t{}) or f(float{}), and the callee writes
+// `using T = decltype(tag);`.  Any other dtype is refused here, before f -- so before anything f times or launches.
+template <typename F>
+int32_t with_dtype(const char* who, int dtype, F&& f) {
+  if (dtype == UNET_BF16) return f(bf16_t{});
+  if (dtype == UNET_F32) return f(float{});
+  unet_set_error("%s: dtype %d", who, dtype);
+  return UNET_ERR_BAD_ARG;
+}
+
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

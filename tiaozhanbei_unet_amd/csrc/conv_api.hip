@@ -47,10 +47,7 @@ int32_t dispatch(IgemmParams& P, int kclass, hipStream_t s, int* stat_parts = nu
 
 template <int TAPS>
 int32_t dispatch_dtype(const char* who, int dtype, IgemmParams& P, int kclass, hipStream_t s, int* stat_parts = nullptr) {
-  if (dtype == UNET_BF16) return dispatch<bf16_t, TAPS>(P, kclass, s, stat_parts);
-  if (dtype == UNET_F32) return dispatch<float, TAPS>(P, kclass, s, stat_parts);
-  unet_set_error("%s: dtype %d", who, dtype);
-  return UNET_ERR_BAD_ARG;
+  return with_dtype(who, dtype, [&](auto tag) { return dispatch<decltype(tag), TAPS>(P, kclass, s, stat_parts); });
 }
 
 inline DView in_view(const unet_view& v) { return DView{(const char*)v.ptr, v.c, v.h, v.w, v.off_y, v.off_x}; }
@@ -155,6 +152,7 @@ extern "C" int32_t unet_conv3x3_dgrad_bnrelu(int32_t dtype, int32_t n, int32_t h
   UNET_REQUIRE(dy && w_packed && y_prev && bn_scale && bn_shift && bn_mean && dz && partial && n_parts, UNET_ERR_BAD_ARG,
                "unet_conv3x3_dgrad_bnrelu: null pointer");
   UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_conv3x3_dgrad_bnrelu: bad dims");
+  UNET_REQUIRE(dtype_known(dtype), UNET_ERR_BAD_ARG, "unet_conv3x3_dgrad_bnrelu: dtype %d", dtype);
   UNET_REQUIRE(unet_conv3x3_dgrad_bnrelu_supported(dtype, n, h, w, c_dy, c_dx), UNET_ERR_UNSUPPORTED,
                "unet_conv3x3_dgrad_bnrelu: %d -> %d channels at %dx%d (dtype %d) is not covered; use unet_conv3x3 + "
                "unet_bn_relu_bwd", c_dy, c_dx, h, w, dtype);
@@ -246,6 +244,7 @@ extern "C" int32_t unet_convt2x2_dgrad_bnrelu(int32_t dtype, int32_t n, int32_t 
   UNET_REQUIRE(dy && w_packed && y_prev && bn_scale && bn_shift && bn_mean && dz && partial && n_parts, UNET_ERR_BAD_ARG,
                "unet_convt2x2_dgrad_bnrelu: null pointer");
   UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_convt2x2_dgrad_bnrelu: bad dims");
+  UNET_REQUIRE(dtype_known(dtype), UNET_ERR_BAD_ARG, "unet_convt2x2_dgrad_bnrelu: dtype %d", dtype);
   UNET_REQUIRE(unet_convt2x2_dgrad_bnrelu_supported(dtype, n, h, w, c_in, c_out), UNET_ERR_UNSUPPORTED,
                "unet_convt2x2_dgrad_bnrelu: %d <- %d channels at %dx%d (dtype %d) is not covered; use unet_convt2x2_dgrad + "
                "unet_bn_relu_bwd", c_in, c_out, h, w, dtype);

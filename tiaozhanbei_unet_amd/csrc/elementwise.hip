@@ -623,6 +623,15 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   }
 }
 
+// one kernel over `items` work items, ew_blocks(items) blocks of 256 threads, timed as `kclass`
+template <typename... P, typename... A>
+int32_t ew_launch(const char* name, void (*kernel)(P...), long long items, int kclass, void* stream, A... args) {
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope prof(kclass, 0.0, s);
+  hipLaunchKernelGGL(kernel, dim3(ew_blocks(items)), dim3(256), 0, s, args...);
+  return unet_check_launch(name);
+}
+
 }  // namespace
 
 extern "C" int32_t unet_nchw_to_nhwc(const float* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w,
@@ -630,28 +639,33 @@ extern "C" int32_t unet_nchw_to_nhwc(const float* src, void* dst, int32_t n, int
   UNET_REQUIRE(src && dst, UNET_ERR_BAD_ARG, "unet_nchw_to_nhwc: null pointer");
   UNET_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && c_pad >= c && c_pad % 8 == 0, UNET_ERR_BAD_ARG,
                "unet_nchw_to_nhwc: bad dims (c=%d c_pad=%d, c_pad must be a multiple of 8)", c, c_pad);
-  hipStream_t s = (hipStream_t)stream;
-  const long long total = (long long)n * h * w;
-  ProfScope prof(UNET_K_PACK, 0.0, s);
-  if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(ew_blocks(total)), dim3(256), 0, s, src, (bf16_t*)dst, n, c, h, w, c_pad);
-  else
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, s, src, (float*)dst, n, c, h, w, c_pad);
-  return unet_check_launch("nchw_to_nhwc_kernel");
+  return with_dtype("unet_nchw_to_nhwc", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("nchw_to_nhwc_kernel", nchw_to_nhwc_kernel<T>, (long long)n * h * w, UNET_K_PACK, stream, src, (T*)dst,
+                     n, c, h, w, c_pad);
+  });
 }
 
 extern "C" int32_t unet_nhwc_to_nchw(const void* src, float* dst, int32_t n, int32_t c, int32_t h, int32_t w,
                                      int32_t c_pad, int32_t dtype, void* stream) {
   UNET_REQUIRE(src && dst, UNET_ERR_BAD_ARG, "unet_nhwc_to_nchw: null pointer");
   UNET_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && c_pad >= c, UNET_ERR_BAD_ARG, "unet_nhwc_to_nchw: bad dims");
-  hipStream_t s = (hipStream_t)stream;
-  const long long total = (long long)n * h * w * c;
-  ProfScope prof(UNET_K_PACK, 0.0, s);
-  if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, dim3(ew_blocks(total)), dim3(256), 0, s, (const bf16_t*)src, dst, n, c, h, w, c_pad);
-  else
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, s, (const float*)src, dst, n, c, h, w, c_pad);
-  return unet_check_launch("nhwc_to_nchw_kernel");
+  return with_dtype("unet_nhwc_to_nchw", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("nhwc_to_nchw_kernel", nhwc_to_nchw_kernel<T>, (long long)n * h * w * c, UNET_K_PACK, stream,
+                     (const T*)src, dst, n, c, h, w, c_pad);
+  });
+}
+
+// pack_weight_kernel over taps * rows * k elements; scale (may be NULL): BatchNorm fold per output channel
+static int32_t launch_pack_weight(const char* who, int dtype, const float* w, void* out, int c_out, int c_in, int rows, int k,
+                                  int mode, int taps, const float* scale, void* stream) {
+  const long long total = (long long)taps * rows * k;
+  return with_dtype(who, dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return ew_launch("pack_weight_kernel", pack_weight_kernel<T>, total, UNET_K_PACK, stream, w, (T*)out, c_out, c_in, rows,
+                     k, mode, total, scale);
+  });
 }
 
 extern "C" int32_t unet_pack_weight(const float* w, void* out, int32_t c_out, int32_t c_in, int32_t rows,
@@ -663,101 +677,79 @@ extern "C" int32_t unet_pack_weight(const float* w, void* out, int32_t c_out, in
   const int gemm_k = (mode == UNET_PACK_CONV_FWD || mode == UNET_PACK_CONVT_FWD) ? c_in : c_out;
   UNET_REQUIRE(rows >= gemm_rows && k >= gemm_k, UNET_ERR_BAD_ARG, "unet_pack_weight: padded dims too small");
   const int taps = (mode <= UNET_PACK_CONV_DGRAD) ? 9 : 4;
-  const long long total = (long long)taps * rows * k;
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_PACK, 0.0, s);
-  if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(pack_weight_kernel<bf16_t>, dim3(ew_blocks(total)), dim3(256), 0, s, w, (bf16_t*)out, c_out, c_in, rows, k, mode, total, (const float*)nullptr);
-  else
-    hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, s, w, (float*)out, c_out, c_in, rows, k, mode, total, (const float*)nullptr);
-  return unet_check_launch("pack_weight_kernel");
+  return launch_pack_weight("unet_pack_weight", dtype, w, out, c_out, c_in, rows, k, mode, taps, nullptr, stream);
 }
 
 extern "C" int32_t unet_pack_conv_weight_folded(const float* w, const float* scale, void* out, int32_t c_out, int32_t c_in,
                                                 int32_t rows, int32_t k, int32_t dtype, void* stream) {
   UNET_REQUIRE(w && scale && out, UNET_ERR_BAD_ARG, "unet_pack_conv_weight_folded: null pointer");
   UNET_REQUIRE(c_out > 0 && c_in > 0 && rows >= c_out && k >= c_in, UNET_ERR_BAD_ARG, "unet_pack_conv_weight_folded: bad dims");
-  const long long total = 9LL * rows * k;
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_PACK, 0.0, s);
-  if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(pack_weight_kernel<bf16_t>, dim3(ew_blocks(total)), dim3(256), 0, s, w, (bf16_t*)out, c_out, c_in, rows, k,
-                       (int)UNET_PACK_CONV_FWD, total, scale);
-  else
-    hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, s, w, (float*)out, c_out, c_in, rows, k,
-                       (int)UNET_PACK_CONV_FWD, total, scale);
-  return unet_check_launch("pack_weight_kernel");
+  return launch_pack_weight("unet_pack_conv_weight_folded", dtype, w, out, c_out, c_in, rows, k, UNET_PACK_CONV_FWD, 9, scale,
+                            stream);
 }
 
 extern "C" int32_t unet_pack_weights_batched(const unet_pack_desc* descs, int32_t n, int32_t dtype, void* stream) {
   UNET_REQUIRE(descs && n > 0 && n <= 65535, UNET_ERR_BAD_ARG, "unet_pack_weights_batched: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_PACK, 0.0, s);
-  if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(pack_weights_batched_kernel<bf16_t>, dim3(224, n), dim3(256), 0, s, descs);
-  else
-    hipLaunchKernelGGL(pack_weights_batched_kernel<float>, dim3(224, n), dim3(256), 0, s, descs);
-  return unet_check_launch("pack_weights_batched_kernel");
+  return with_dtype("unet_pack_weights_batched", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    ProfScope prof(UNET_K_PACK, 0.0, s);
+    hipLaunchKernelGGL(pack_weights_batched_kernel<T>, dim3(224, n), dim3(256), 0, s, descs);
+    return unet_check_launch("pack_weights_batched_kernel");
+  });
 }
-
-#define EW_DISPATCH(NAME, KERN, TOTAL, ...)                                                                 \
-  do {                                                                                                        \
-    hipStream_t s = (hipStream_t)stream;                                                                      \
-    ProfScope prof(UNET_K_POOL, 0.0, s);                                                                      \
-    if (dtype == UNET_BF16) {                                                                                 \
-      typedef bf16_t T;                                                                                       \
-      const long long total = (TOTAL) / 8;                                                                    \
-      hipLaunchKernelGGL(KERN<bf16_t>, dim3(ew_blocks(total)), dim3(256), 0, s, __VA_ARGS__);                 \
-    } else {                                                                                                  \
-      typedef float T;                                                                                        \
-      const long long total = (TOTAL) / 4;                                                                    \
-      hipLaunchKernelGGL(KERN<float>, dim3(ew_blocks(total)), dim3(256), 0, s, __VA_ARGS__);                  \
-    }                                                                                                         \
-    return unet_check_launch(NAME);                                                                           \
-  } while (0)
 
 extern "C" int32_t unet_maxpool2_fwd(int32_t dtype, const void* x, int32_t n, int32_t h, int32_t w, int32_t c,
                                      void* y, void* stream) {
   UNET_REQUIRE(x && y, UNET_ERR_BAD_ARG, "unet_maxpool2_fwd: null pointer");
   UNET_REQUIRE(n > 0 && h >= 2 && w >= 2 && c > 0 && c % 8 == 0, UNET_ERR_UNSUPPORTED, "unet_maxpool2_fwd: dims");
-  EW_DISPATCH("maxpool2_fwd_kernel", maxpool2_fwd_kernel, (long long)n * (h / 2) * (w / 2) * c, (const T*)x, (T*)y, n, h, w, c);
+  return with_dtype("unet_maxpool2_fwd", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const long long total = (long long)n * (h / 2) * (w / 2) * c / ET<T>::PIECE;
+    return ew_launch("maxpool2_fwd_kernel", maxpool2_fwd_kernel<T>, total, UNET_K_POOL, stream, (const T*)x, (T*)y, n, h, w, c);
+  });
 }
 
 extern "C" int32_t unet_maxpool2_bwd(int32_t dtype, const void* x, const void* dy, int32_t n, int32_t h,
                                      int32_t w, int32_t c, void* dx, int32_t accumulate, void* stream) {
   UNET_REQUIRE(x && dy && dx, UNET_ERR_BAD_ARG, "unet_maxpool2_bwd: null pointer");
   UNET_REQUIRE(n > 0 && h >= 2 && w >= 2 && c > 0 && c % 8 == 0, UNET_ERR_UNSUPPORTED, "unet_maxpool2_bwd: dims");
-  EW_DISPATCH("maxpool2_bwd_kernel", maxpool2_bwd_kernel, (long long)n * ((h + 1) / 2) * ((w + 1) / 2) * c,
-              (const T*)x, (const T*)dy, (T*)dx, n, h, w, c, accumulate);
+  return with_dtype("unet_maxpool2_bwd", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const long long total = (long long)n * ((h + 1) / 2) * ((w + 1) / 2) * c / ET<T>::PIECE;
+    return ew_launch("maxpool2_bwd_kernel", maxpool2_bwd_kernel<T>, total, UNET_K_POOL, stream, (const T*)x, (const T*)dy,
+                     (T*)dx, n, h, w, c, accumulate);
+  });
 }
-
 
 extern "C" int32_t unet_bn_relu_pool_supported(int32_t dtype, int32_t c) {
-  const int piece = dtype == UNET_BF16 ? 8 : 4;
+  if (!dtype_known(dtype)) return 0;
+  const int piece = dtype == UNET_BF16 ? ET<bf16_t>::PIECE : ET<float>::PIECE;
   return (c > 0 && c % piece == 0 && 256 % (c / piece) == 0) ? 1 : 0;
 }
+
+// index type of the bn_relu_pool kernels for tensors below 2^31 elements: fp32 has the 64-bit kernels only
+template <typename T> using PoolIdx32 = std::conditional_t<sizeof(T) == 2, int, long long>;
 
 extern "C" int32_t unet_bn_relu_pool_fwd(int32_t dtype, const void* y, int32_t n, int32_t h, int32_t w, int32_t c,
                                          const float* scale, const float* shift, void* a, void* pooled, void* stream) {
   UNET_REQUIRE(y && scale && shift && a && pooled, UNET_ERR_BAD_ARG, "unet_bn_relu_pool_fwd: null pointer");
-  UNET_REQUIRE(n > 0 && h >= 2 && w >= 2 && unet_bn_relu_pool_supported(dtype, c), UNET_ERR_UNSUPPORTED,
-               "unet_bn_relu_pool_fwd: c=%d h=%d w=%d", c, h, w);
   hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_BN, 0.0, s, "bn_relu_pool_fwd_kernel");
-  const long long total = (long long)n * ((h + 1) / 2) * ((w + 1) / 2) * (c / (dtype == UNET_BF16 ? 8 : 4));
-  const bool small = (long long)n * h * w * c < 0x7FFFFFFFLL;       // 32-bit element indices (no 64-bit divisions)
-  if (dtype == UNET_BF16) {
-    if (small)
-      hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<bf16_t, int>), dim3(ew_blocks(total)), dim3(256), 0, s, (const bf16_t*)y, scale,
-                         shift, (bf16_t*)a, (bf16_t*)pooled, n, h, w, c);
+  return with_dtype("unet_bn_relu_pool_fwd", dtype, [&](auto tag) -> int32_t {
+    using T = decltype(tag);
+    UNET_REQUIRE(n > 0 && h >= 2 && w >= 2 && unet_bn_relu_pool_supported(dtype, c), UNET_ERR_UNSUPPORTED,
+                 "unet_bn_relu_pool_fwd: c=%d h=%d w=%d", c, h, w);
+    ProfScope prof(UNET_K_BN, 0.0, s, "bn_relu_pool_fwd_kernel");
+    const long long total = (long long)n * ((h + 1) / 2) * ((w + 1) / 2) * (c / ET<T>::PIECE);
+    const dim3 grid(ew_blocks(total));
+    if ((long long)n * h * w * c < 0x7FFFFFFFLL)       // 32-bit element indices (no 64-bit divisions)
+      hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<T, PoolIdx32<T>>), grid, dim3(256), 0, s, (const T*)y, scale, shift, (T*)a,
+                         (T*)pooled, n, h, w, c);
     else
-      hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<bf16_t, long long>), dim3(ew_blocks(total)), dim3(256), 0, s, (const bf16_t*)y,
-                         scale, shift, (bf16_t*)a, (bf16_t*)pooled, n, h, w, c);
-  } else {
-    hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<float, long long>), dim3(ew_blocks(total)), dim3(256), 0, s, (const float*)y, scale,
-                       shift, (float*)a, (float*)pooled, n, h, w, c);
-  }
-  return unet_check_launch("bn_relu_pool_fwd_kernel");
+      hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<T, long long>), grid, dim3(256), 0, s, (const T*)y, scale, shift, (T*)a,
+                         (T*)pooled, n, h, w, c);
+    return unet_check_launch("bn_relu_pool_fwd_kernel");
+  });
 }
 
 namespace { constexpr int POOL_BWD_MAX_BLOCKS = 256 * 8; }     // = the partial-sum capacity callers allocate
@@ -773,29 +765,23 @@ static int32_t bn_relu_pool_bwd_impl(const char* what, int32_t dtype, const void
   constexpr bool SUM = MODE != POOL_BWD_APPLY;
   UNET_REQUIRE(y && dpooled && scale && shift && (dst || MODE == POOL_BWD_SUMS) &&
                (SUM ? (mean && partial && n_parts) : coefs != nullptr), UNET_ERR_BAD_ARG, "%s: null pointer", what);
-  UNET_REQUIRE(n > 0 && h >= 2 && w >= 2 && unet_bn_relu_pool_supported(dtype, c), UNET_ERR_UNSUPPORTED,
-               "%s: c=%d h=%d w=%d", what, c, h, w);
   hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_POOL, 0.0, s, "bn_relu_pool_bwd_kernel");
-  const long long total = (long long)n * ((h + 1) / 2) * ((w + 1) / 2) * (c / (dtype == UNET_BF16 ? 8 : 4));
-  const int blocks = (int)std::min<long long>(cdiv64(total, 256), POOL_BWD_MAX_BLOCKS);   // one partial per block
-  const bool small = (long long)n * h * w * c < 0x7FFFFFFFLL;
-  if (dtype == UNET_BF16) {
-    if (small)
-      hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<bf16_t, int, MODE>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)y,
-                         (const bf16_t*)dpooled, (const bf16_t*)da_old, scale, shift, mean, (bf16_t*)dst, partial, n, h, w, c,
-                         coefs);
+  return with_dtype(what, dtype, [&](auto tag) -> int32_t {
+    using T = decltype(tag);
+    UNET_REQUIRE(n > 0 && h >= 2 && w >= 2 && unet_bn_relu_pool_supported(dtype, c), UNET_ERR_UNSUPPORTED,
+                 "%s: c=%d h=%d w=%d", what, c, h, w);
+    ProfScope prof(UNET_K_POOL, 0.0, s, "bn_relu_pool_bwd_kernel");
+    const long long total = (long long)n * ((h + 1) / 2) * ((w + 1) / 2) * (c / ET<T>::PIECE);
+    const int blocks = (int)std::min<long long>(cdiv64(total, 256), POOL_BWD_MAX_BLOCKS);   // one partial per block
+    if ((long long)n * h * w * c < 0x7FFFFFFFLL)
+      hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<T, PoolIdx32<T>, MODE>), dim3(blocks), dim3(256), 0, s, (const T*)y,
+                         (const T*)dpooled, (const T*)da_old, scale, shift, mean, (T*)dst, partial, n, h, w, c, coefs);
     else
-      hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<bf16_t, long long, MODE>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)y,
-                         (const bf16_t*)dpooled, (const bf16_t*)da_old, scale, shift, mean, (bf16_t*)dst, partial, n, h, w, c,
-                         coefs);
-  } else {
-    hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<float, long long, MODE>), dim3(blocks), dim3(256), 0, s, (const float*)y,
-                       (const float*)dpooled, (const float*)da_old, scale, shift, mean, (float*)dst, partial, n, h, w, c,
-                       coefs);
-  }
-  if (SUM) *n_parts = blocks;
-  return unet_check_launch("bn_relu_pool_bwd_kernel");
+      hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<T, long long, MODE>), dim3(blocks), dim3(256), 0, s, (const T*)y,
+                         (const T*)dpooled, (const T*)da_old, scale, shift, mean, (T*)dst, partial, n, h, w, c, coefs);
+    if (SUM) *n_parts = blocks;
+    return unet_check_launch("bn_relu_pool_bwd_kernel");
+  });
 }
 
 extern "C" int32_t unet_bn_relu_pool_bwd(int32_t dtype, const void* y, const void* dpooled, const void* da_old, int32_t n,
@@ -825,7 +811,12 @@ extern "C" int32_t unet_upsample_bilinear2x_fwd(int32_t dtype, const void* x, in
   UNET_REQUIRE(x && y, UNET_ERR_BAD_ARG, "unet_upsample_bilinear2x_fwd: null pointer");
   UNET_REQUIRE(n > 0 && h > 0 && w > 0 && h <= 32768 && w <= 32768 && c > 0 && c % 8 == 0, UNET_ERR_UNSUPPORTED,
                "unet_upsample_bilinear2x_fwd: dims");
-  EW_DISPATCH("bilinear2x_fwd_kernel", bilinear2x_fwd_kernel, (long long)n * 4 * h * w * c, (const T*)x, (T*)y, n, h, w, c);
+  return with_dtype("unet_upsample_bilinear2x_fwd", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const long long total = (long long)n * 4 * h * w * c / ET<T>::PIECE;
+    return ew_launch("bilinear2x_fwd_kernel", bilinear2x_fwd_kernel<T>, total, UNET_K_POOL, stream, (const T*)x, (T*)y, n, h, w,
+                     c);
+  });
 }
 
 extern "C" int32_t unet_upsample_bilinear2x_bwd(int32_t dtype, const void* dy, int32_t n, int32_t h, int32_t w,
@@ -833,7 +824,12 @@ extern "C" int32_t unet_upsample_bilinear2x_bwd(int32_t dtype, const void* dy, i
   UNET_REQUIRE(dy && dx, UNET_ERR_BAD_ARG, "unet_upsample_bilinear2x_bwd: null pointer");
   UNET_REQUIRE(n > 0 && h > 0 && w > 0 && h <= 32768 && w <= 32768 && c > 0 && c % 8 == 0, UNET_ERR_UNSUPPORTED,
                "unet_upsample_bilinear2x_bwd: dims");
-  EW_DISPATCH("bilinear2x_bwd_kernel", bilinear2x_bwd_kernel, (long long)n * h * w * c, (const T*)dy, (T*)dx, n, h, w, c);
+  return with_dtype("unet_upsample_bilinear2x_bwd", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const long long total = (long long)n * h * w * c / ET<T>::PIECE;
+    return ew_launch("bilinear2x_bwd_kernel", bilinear2x_bwd_kernel<T>, total, UNET_K_POOL, stream, (const T*)dy, (T*)dx, n, h,
+                     w, c);
+  });
 }
 
 // ------------------------------------------------------------------------------- Dropout2d / anomaly score
@@ -897,18 +893,12 @@ extern "C" int32_t unet_channel_scale(int32_t dtype, const void* x, const float*
                                       void* y, void* stream) {
   UNET_REQUIRE(x && scale && y, UNET_ERR_BAD_ARG, "unet_channel_scale: null pointer");
   UNET_REQUIRE(n > 0 && hw > 0 && c > 0 && c % 8 == 0, UNET_ERR_UNSUPPORTED, "unet_channel_scale: c=%d", c);
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_POOL, 0.0, s);
-  if (dtype == UNET_BF16) {
-    const long long total = (long long)n * hw * c / 8;
-    hipLaunchKernelGGL(channel_scale_kernel<bf16_t>, dim3(ew_blocks(total)), dim3(256), 0, s, (const bf16_t*)x, scale,
-                       (bf16_t*)y, (long long)hw, c, total);
-  } else {
-    const long long total = (long long)n * hw * c / 4;
-    hipLaunchKernelGGL(channel_scale_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, s, (const float*)x, scale,
-                       (float*)y, (long long)hw, c, total);
-  }
-  return unet_check_launch("channel_scale_kernel");
+  return with_dtype("unet_channel_scale", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const long long total = (long long)n * hw * c / ET<T>::PIECE;
+    return ew_launch("channel_scale_kernel", channel_scale_kernel<T>, total, UNET_K_POOL, stream, (const T*)x, scale, (T*)y,
+                     (long long)hw, c, total);
+  });
 }
 
 extern "C" size_t unet_anomaly_score_workspace(int32_t n, int64_t hw) {

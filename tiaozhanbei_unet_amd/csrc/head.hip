@@ -609,51 +609,113 @@ inline int head_blocks(long long pixels, int tpp) {
   return (int)b;
 }
 
-template <typename T>
-int tpp_of(int c_in) { return c_in / ET<T>::PIECE; }
+template <int V> using Int = std::integral_constant<int, V>;
+
+// c_out -> f(Int<CO>): the kernels hold CO filters in registers
+template <typename F>
+int32_t head_co_dispatch(int c_out, F&& f) {
+  switch (c_out) {
+    case 1: return f(Int<1>{});
+    case 2: return f(Int<2>{});
+    case 3: return f(Int<3>{});
+    case 4: return f(Int<4>{});
+    default: return f(Int<8>{});
+  }
+}
+
+// (T, c_in, c_out) -> f(Int<TPP>, Int<CO>), TPP = c_in / PIECE lanes per pixel: 4, 8, 16 for bf16 and 8, 16, 32 for fp32,
+// and nothing else is instantiated.  C64 = false (the backward launchers, whose c_in == 64 is head_bwd_tile_kernel's)
+// leaves out c_in == 64 as well.
+template <typename T, bool C64 = true, typename F>
+int32_t head_dispatch(int c_in, int c_out, F&& f) {
+  constexpr int PIECE = ET<T>::PIECE;
+  if (c_in == 32) return head_co_dispatch(c_out, [&](auto co) { return f(Int<32 / PIECE>{}, co); });
+  if (c_in == 128) return head_co_dispatch(c_out, [&](auto co) { return f(Int<128 / PIECE>{}, co); });
+  if constexpr (C64) {
+    if (c_in == 64) return head_co_dispatch(c_out, [&](auto co) { return f(Int<64 / PIECE>{}, co); });
+  }
+  unet_set_error("head: c_in %d unsupported", c_in);
+  return UNET_ERR_UNSUPPORTED;
+}
+
+// What the five entry points share.  `who` names the entry point in the messages, ptrs_ok is its own pointer condition;
+// the forward and apply entry points have no workspace.
+int32_t head_check(const char* who, bool ptrs_ok, int n, int h, int w, int c_in, int c_out,
+                   size_t workspace_bytes = SIZE_MAX) {
+  UNET_REQUIRE(ptrs_ok, UNET_ERR_BAD_ARG, "%s: null pointer", who);
+  UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "%s: bad dims", who);
+  UNET_REQUIRE(c_out >= 1 && c_out <= MAXCO && (c_in == 32 || c_in == 64 || c_in == 128), UNET_ERR_UNSUPPORTED,
+               "%s: %d -> %d channels unsupported (c_out <= 8, c_in in {32,64,128})", who, c_in, c_out);
+  UNET_REQUIRE(workspace_bytes >= unet_head_bwd_workspace(n, h, w, c_in, c_out), UNET_ERR_WORKSPACE,
+               "%s: workspace too small", who);
+  return UNET_OK;
+}
+
+// Both forward entry points; BN: x is the raw convolution output and bn_scale / bn_shift are given
+template <bool BN>
+int32_t head_fwd_impl(const char* who, int32_t dtype, const void* x, int32_t n, int32_t h, int32_t w, int32_t c_in,
+                      const float* bn_scale, const float* bn_shift, const float* weight, const float* bias, int32_t c_out,
+                      int32_t sigmoid, float* out, void* stream) {
+  return with_dtype(who, dtype, [&](auto tag) -> int32_t {
+    using T = decltype(tag);
+    UNET_REQUIRE(c_out <= c_in / ET<T>::PIECE, UNET_ERR_UNSUPPORTED, "%s: c_out %d too wide for c_in %d", who, c_out, c_in);
+    hipStream_t s = (hipStream_t)stream;
+    const long long pixels = (long long)n * h * w, hw = (long long)h * w;
+    ProfScope prof(UNET_K_HEAD, 2.0 * pixels * c_in * c_out, s);
+    return head_dispatch<T>(c_in, c_out, [&](auto tpp, auto co) {
+      constexpr int TPP = decltype(tpp)::value, CO = decltype(co)::value;
+      hipLaunchKernelGGL((head_fwd_kernel<T, TPP, CO, BN>), dim3(head_blocks(pixels, TPP)), dim3(256), 0, s, (const T*)x,
+                         pixels, hw, c_in, weight, bias, sigmoid, out, bn_scale, bn_shift);
+      return unet_check_launch(BN ? "head_fwd_kernel<BN>" : "head_fwd_kernel");
+    });
+  });
+}
+
+// The three backward entry points that leave dW / db: block partials by head_bwd_tile_kernel (c_in == 64) or
+// head_bwd_kernel, then their finalize.  BN: the bn_* arguments are given and bn_partial is written, *n_parts = its rows.
+// STORE = false: unet_head_bnrelu_bwd_sums (dx is not written and may be NULL).
+template <bool BN, bool STORE>
+int32_t head_bwd_impl(const char* who, int32_t dtype, const void* x, const float* bn_scale, const float* bn_shift,
+                      const float* bn_mean, const float* out, const float* dout, int32_t n, int32_t h, int32_t w,
+                      int32_t c_in, const float* weight, int32_t c_out, int32_t sigmoid, void* dx, float* dweight,
+                      float* dbias, float* bn_partial, int32_t* n_parts, void* workspace, void* stream) {
+  return with_dtype(who, dtype, [&](auto tag) -> int32_t {
+    using T = decltype(tag);
+    hipStream_t s = (hipStream_t)stream;
+    const long long pixels = (long long)n * h * w, hw = (long long)h * w;
+    ProfScope prof(UNET_K_HEAD, 4.0 * pixels * c_in * c_out, s);
+    const int nb = head_blocks(pixels, c_in / ET<T>::PIECE);
+    int32_t rc;
+    if (c_in == 64)
+      rc = head_co_dispatch(c_out, [&](auto co) {
+        return launch_head_bwd_tile<T, decltype(co)::value, BN, STORE>(x, out, dout, pixels, hw, weight, sigmoid, dx,
+                                                                       (float*)workspace, bn_scale, bn_shift, bn_mean,
+                                                                       bn_partial, nb, s);
+      });
+    else
+      rc = head_dispatch<T, false>(c_in, c_out, [&](auto tpp, auto co) {
+        constexpr int TPP = decltype(tpp)::value, CO = decltype(co)::value;
+        hipLaunchKernelGGL((head_bwd_kernel<T, TPP, CO, BN, STORE>), dim3(nb), dim3(256), 0, s, (const T*)x, out, dout,
+                           pixels, hw, c_in, weight, sigmoid, (T*)dx, (float*)workspace, bn_scale, bn_shift, bn_mean,
+                           bn_partial);
+        return unet_check_launch(BN ? "head_bwd_kernel<BN>" : "head_bwd_kernel");
+      });
+    if (rc) return rc;
+    if (BN) *n_parts = nb;
+    hipLaunchKernelGGL(head_bwd_finalize_kernel, dim3(cdiv(c_out * (c_in + 1), 4)), dim3(256), 0, s,
+                       (const float*)workspace, nb, c_out, c_in, dweight, dbias);
+    return unet_check_launch("head_bwd_finalize_kernel");
+  });
+}
 
 }  // namespace
-
-#define HEAD_CO_SWITCH(...)                                  \
-  switch (c_out) {                                          \
-    case 1: { constexpr int CO = 1; __VA_ARGS__; } break;          \
-    case 2: { constexpr int CO = 2; __VA_ARGS__; } break;          \
-    case 3: { constexpr int CO = 3; __VA_ARGS__; } break;          \
-    case 4: { constexpr int CO = 4; __VA_ARGS__; } break;          \
-    default: { constexpr int CO = 8; __VA_ARGS__; } break;         \
-  }
-#define HEAD_TPP_SWITCH(T, tpp, ...)                        \
-  switch (tpp) {                                            \
-    case 4: { constexpr int TPP = 4; HEAD_CO_SWITCH(__VA_ARGS__); } break;   \
-    case 8: { constexpr int TPP = 8; HEAD_CO_SWITCH(__VA_ARGS__); } break;   \
-    case 16: { constexpr int TPP = 16; HEAD_CO_SWITCH(__VA_ARGS__); } break; \
-    case 32: { constexpr int TPP = 32; HEAD_CO_SWITCH(__VA_ARGS__); } break; \
-    default:                                                \
-      unet_set_error("head: c_in %d unsupported", c_in);    \
-      return UNET_ERR_UNSUPPORTED;                          \
-  }
 
 extern "C" int32_t unet_head_fwd(int32_t dtype, const void* x, int32_t n, int32_t h, int32_t w, int32_t c_in,
                                  const float* weight, const float* bias, int32_t c_out, int32_t sigmoid,
                                  float* out, void* stream) {
-  UNET_REQUIRE(x && weight && bias && out, UNET_ERR_BAD_ARG, "unet_head_fwd: null pointer");
-  UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_head_fwd: bad dims");
-  UNET_REQUIRE(c_out >= 1 && c_out <= MAXCO && c_in <= 128 && (c_in == 32 || c_in == 64 || c_in == 128), UNET_ERR_UNSUPPORTED,
-               "unet_head_fwd: %d -> %d channels unsupported (c_out <= 8, c_in in {32,64,128})", c_in, c_out);
-  UNET_REQUIRE(c_out <= c_in / (dtype == UNET_BF16 ? 8 : 4), UNET_ERR_UNSUPPORTED, "unet_head_fwd: c_out %d too wide for c_in %d", c_out, c_in);
-  hipStream_t s = (hipStream_t)stream;
-  const long long pixels = (long long)n * h * w, hw = (long long)h * w;
-  ProfScope prof(UNET_K_HEAD, 2.0 * pixels * c_in * c_out, s);
-  if (dtype == UNET_BF16) {
-    const int tpp = tpp_of<bf16_t>(c_in);
-    HEAD_TPP_SWITCH(bf16_t, tpp, hipLaunchKernelGGL((head_fwd_kernel<bf16_t, TPP, CO>), dim3(head_blocks(pixels, TPP)), dim3(256), 0, s,
-                    (const bf16_t*)x, pixels, hw, c_in, weight, bias, sigmoid, out));
-  } else {
-    const int tpp = tpp_of<float>(c_in);
-    HEAD_TPP_SWITCH(float, tpp, hipLaunchKernelGGL((head_fwd_kernel<float, TPP, CO>), dim3(head_blocks(pixels, TPP)), dim3(256), 0, s,
-                    (const float*)x, pixels, hw, c_in, weight, bias, sigmoid, out));
-  }
-  return unet_check_launch("head_fwd_kernel");
+  if (int32_t rc = head_check("unet_head_fwd", x && weight && bias && out, n, h, w, c_in, c_out)) return rc;
+  return head_fwd_impl<false>("unet_head_fwd", dtype, x, n, h, w, c_in, nullptr, nullptr, weight, bias, c_out, sigmoid, out,
+                              stream);
 }
 
 extern "C" size_t unet_head_bwd_workspace(int32_t n, int32_t h, int32_t w, int32_t c_in, int32_t c_out) {
@@ -665,136 +727,34 @@ extern "C" int32_t unet_head_bwd(int32_t dtype, const void* x, const float* out,
                                  int32_t h, int32_t w, int32_t c_in, const float* weight, int32_t c_out,
                                  int32_t sigmoid, void* dx, float* dweight, float* dbias, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-  UNET_REQUIRE(x && dout && weight && dx && dweight && dbias && workspace && (out || !sigmoid), UNET_ERR_BAD_ARG,
-               "unet_head_bwd: null pointer");
-  UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_head_bwd: bad dims");
-  UNET_REQUIRE(c_out >= 1 && c_out <= MAXCO && c_in <= 128 && (c_in == 32 || c_in == 64 || c_in == 128), UNET_ERR_UNSUPPORTED,
-               "unet_head_bwd: %d -> %d channels unsupported", c_in, c_out);
-  UNET_REQUIRE(workspace_bytes >= unet_head_bwd_workspace(n, h, w, c_in, c_out), UNET_ERR_WORKSPACE,
-               "unet_head_bwd: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const long long pixels = (long long)n * h * w, hw = (long long)h * w;
-  ProfScope prof(UNET_K_HEAD, 4.0 * pixels * c_in * c_out, s);
-  int nb = 0;
-  if (c_in == 64 && (dtype == UNET_BF16 || dtype == UNET_F32)) {
-    nb = head_blocks(pixels, 8);
-    int32_t rc = UNET_OK;
-    if (dtype == UNET_BF16) {
-      HEAD_CO_SWITCH(rc = (launch_head_bwd_tile<bf16_t, CO, false>(x, out, dout, pixels, hw, weight, sigmoid, dx, (float*)workspace,
-                                                                 nullptr, nullptr, nullptr, nullptr, nb, s)));
-    } else {
-      HEAD_CO_SWITCH(rc = (launch_head_bwd_tile<float, CO, false>(x, out, dout, pixels, hw, weight, sigmoid, dx, (float*)workspace,
-                                                                nullptr, nullptr, nullptr, nullptr, nb, s)));
-    }
-    if (rc) return rc;
-  } else if (dtype == UNET_BF16) {
-    const int tpp = tpp_of<bf16_t>(c_in);
-    nb = head_blocks(pixels, tpp);
-    HEAD_TPP_SWITCH(bf16_t, tpp, hipLaunchKernelGGL((head_bwd_kernel<bf16_t, TPP, CO>), dim3(nb), dim3(256), 0, s,
-                    (const bf16_t*)x, out, dout, pixels, hw, c_in, weight, sigmoid, (bf16_t*)dx, (float*)workspace));
-  } else {
-    const int tpp = tpp_of<float>(c_in);
-    nb = head_blocks(pixels, tpp);
-    HEAD_TPP_SWITCH(float, tpp, hipLaunchKernelGGL((head_bwd_kernel<float, TPP, CO>), dim3(nb), dim3(256), 0, s,
-                    (const float*)x, out, dout, pixels, hw, c_in, weight, sigmoid, (float*)dx, (float*)workspace));
-  }
-  int32_t rc = unet_check_launch("head_bwd_kernel");
-  if (rc) return rc;
-  hipLaunchKernelGGL(head_bwd_finalize_kernel, dim3(cdiv(c_out * (c_in + 1), 4)), dim3(256), 0, s,
-                     (const float*)workspace, nb, c_out, c_in, dweight, dbias);
-  return unet_check_launch("head_bwd_finalize_kernel");
+  const bool ptrs_ok = x && dout && weight && dx && dweight && dbias && workspace && (out || !sigmoid);
+  if (int32_t rc = head_check("unet_head_bwd", ptrs_ok, n, h, w, c_in, c_out, workspace_bytes)) return rc;
+  return head_bwd_impl<false, true>("unet_head_bwd", dtype, x, nullptr, nullptr, nullptr, out, dout, n, h, w, c_in, weight,
+                                    c_out, sigmoid, dx, dweight, dbias, nullptr, nullptr, workspace, stream);
 }
 
 // ---- OutConv fed by the RAW convolution output of the last conv-BatchNorm-ReLU layer (src/model.py:17-19 -> :72) ----
 extern "C" int32_t unet_head_bnrelu_fwd(int32_t dtype, const void* y, int32_t n, int32_t h, int32_t w, int32_t c_in,
                                         const float* bn_scale, const float* bn_shift, const float* weight,
                                         const float* bias, int32_t c_out, int32_t sigmoid, float* out, void* stream) {
-  UNET_REQUIRE(y && bn_scale && bn_shift && weight && bias && out, UNET_ERR_BAD_ARG, "unet_head_bnrelu_fwd: null pointer");
-  UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_head_bnrelu_fwd: bad dims");
-  UNET_REQUIRE(c_out >= 1 && c_out <= MAXCO && (c_in == 32 || c_in == 64 || c_in == 128), UNET_ERR_UNSUPPORTED,
-               "unet_head_bnrelu_fwd: %d -> %d channels unsupported (c_out <= 8, c_in in {32,64,128})", c_in, c_out);
-  UNET_REQUIRE(c_out <= c_in / (dtype == UNET_BF16 ? 8 : 4), UNET_ERR_UNSUPPORTED,
-               "unet_head_bnrelu_fwd: c_out %d too wide for c_in %d", c_out, c_in);
-  hipStream_t s = (hipStream_t)stream;
-  const long long pixels = (long long)n * h * w, hw = (long long)h * w;
-  ProfScope prof(UNET_K_HEAD, 2.0 * pixels * c_in * c_out, s);
-  if (dtype == UNET_BF16) {
-    const int tpp = tpp_of<bf16_t>(c_in);
-    HEAD_TPP_SWITCH(bf16_t, tpp, hipLaunchKernelGGL((head_fwd_kernel<bf16_t, TPP, CO, true>), dim3(head_blocks(pixels, TPP)),
-                    dim3(256), 0, s, (const bf16_t*)y, pixels, hw, c_in, weight, bias, sigmoid, out, bn_scale, bn_shift));
-  } else if (dtype == UNET_F32) {
-    const int tpp = tpp_of<float>(c_in);
-    HEAD_TPP_SWITCH(float, tpp, hipLaunchKernelGGL((head_fwd_kernel<float, TPP, CO, true>), dim3(head_blocks(pixels, TPP)),
-                    dim3(256), 0, s, (const float*)y, pixels, hw, c_in, weight, bias, sigmoid, out, bn_scale, bn_shift));
-  } else {
-    unet_set_error("unet_head_bnrelu_fwd: dtype %d", dtype);
-    return UNET_ERR_BAD_ARG;
-  }
-  return unet_check_launch("head_fwd_kernel<BN>");
+  const bool ptrs_ok = y && bn_scale && bn_shift && weight && bias && out;
+  if (int32_t rc = head_check("unet_head_bnrelu_fwd", ptrs_ok, n, h, w, c_in, c_out)) return rc;
+  return head_fwd_impl<true>("unet_head_bnrelu_fwd", dtype, y, n, h, w, c_in, bn_scale, bn_shift, weight, bias, c_out,
+                             sigmoid, out, stream);
 }
 
 extern "C" size_t unet_head_bnrelu_max_parts(void) { return 1024; }
-
-// STORE = false: unet_head_bnrelu_bwd_sums (dz is not written and may be NULL)
-template <bool STORE>
-static int32_t head_bnrelu_bwd_impl(int32_t dtype, const void* y, const float* bn_scale, const float* bn_shift,
-                                    const float* bn_mean, const float* out, const float* dout, int32_t n, int32_t h,
-                                    int32_t w, int32_t c_in, const float* weight, int32_t c_out, int32_t sigmoid,
-                                    void* dz, float* dweight, float* dbias, float* bn_partial, int32_t* n_parts,
-                                    void* workspace, size_t workspace_bytes, void* stream) {
-  UNET_REQUIRE(y && bn_scale && bn_shift && bn_mean && dout && weight && (dz || !STORE) && dweight && dbias && bn_partial &&
-               n_parts && workspace && (out || !sigmoid), UNET_ERR_BAD_ARG, "unet_head_bnrelu_bwd: null pointer");
-  UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_head_bnrelu_bwd: bad dims");
-  UNET_REQUIRE(c_out >= 1 && c_out <= MAXCO && (c_in == 32 || c_in == 64 || c_in == 128), UNET_ERR_UNSUPPORTED,
-               "unet_head_bnrelu_bwd: %d -> %d channels unsupported", c_in, c_out);
-  UNET_REQUIRE(workspace_bytes >= unet_head_bwd_workspace(n, h, w, c_in, c_out), UNET_ERR_WORKSPACE,
-               "unet_head_bnrelu_bwd: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const long long pixels = (long long)n * h * w, hw = (long long)h * w;
-  ProfScope prof(UNET_K_HEAD, 4.0 * pixels * c_in * c_out, s);
-  int nb = 0;
-  if (c_in == 64 && (dtype == UNET_BF16 || dtype == UNET_F32)) {
-    nb = head_blocks(pixels, 8);
-    int32_t rc = UNET_OK;
-    if (dtype == UNET_BF16) {
-      HEAD_CO_SWITCH(rc = (launch_head_bwd_tile<bf16_t, CO, true, STORE>(y, out, dout, pixels, hw, weight, sigmoid, dz, (float*)workspace,
-                                                                bn_scale, bn_shift, bn_mean, bn_partial, nb, s)));
-    } else {
-      HEAD_CO_SWITCH(rc = (launch_head_bwd_tile<float, CO, true, STORE>(y, out, dout, pixels, hw, weight, sigmoid, dz, (float*)workspace,
-                                                               bn_scale, bn_shift, bn_mean, bn_partial, nb, s)));
-    }
-    if (rc) return rc;
-  } else if (dtype == UNET_BF16) {
-    const int tpp = tpp_of<bf16_t>(c_in);
-    nb = head_blocks(pixels, tpp);
-    HEAD_TPP_SWITCH(bf16_t, tpp, hipLaunchKernelGGL((head_bwd_kernel<bf16_t, TPP, CO, true, STORE>), dim3(nb), dim3(256), 0, s,
-                    (const bf16_t*)y, out, dout, pixels, hw, c_in, weight, sigmoid, (bf16_t*)dz, (float*)workspace,
-                    bn_scale, bn_shift, bn_mean, bn_partial));
-  } else if (dtype == UNET_F32) {
-    const int tpp = tpp_of<float>(c_in);
-    nb = head_blocks(pixels, tpp);
-    HEAD_TPP_SWITCH(float, tpp, hipLaunchKernelGGL((head_bwd_kernel<float, TPP, CO, true, STORE>), dim3(nb), dim3(256), 0, s,
-                    (const float*)y, out, dout, pixels, hw, c_in, weight, sigmoid, (float*)dz, (float*)workspace,
-                    bn_scale, bn_shift, bn_mean, bn_partial));
-  } else {
-    unet_set_error("unet_head_bnrelu_bwd: dtype %d", dtype);
-    return UNET_ERR_BAD_ARG;
-  }
-  int32_t rc = unet_check_launch("head_bwd_kernel<BN>");
-  if (rc) return rc;
-  *n_parts = nb;
-  hipLaunchKernelGGL(head_bwd_finalize_kernel, dim3(cdiv(c_out * (c_in + 1), 4)), dim3(256), 0, s,
-                     (const float*)workspace, nb, c_out, c_in, dweight, dbias);
-  return unet_check_launch("head_bwd_finalize_kernel");
-}
 
 extern "C" int32_t unet_head_bnrelu_bwd(int32_t dtype, const void* y, const float* bn_scale, const float* bn_shift,
                                         const float* bn_mean, const float* out, const float* dout, int32_t n, int32_t h,
                                         int32_t w, int32_t c_in, const float* weight, int32_t c_out, int32_t sigmoid,
                                         void* dz, float* dweight, float* dbias, float* bn_partial, int32_t* n_parts,
                                         void* workspace, size_t workspace_bytes, void* stream) {
-  return head_bnrelu_bwd_impl<true>(dtype, y, bn_scale, bn_shift, bn_mean, out, dout, n, h, w, c_in, weight, c_out, sigmoid,
-                                    dz, dweight, dbias, bn_partial, n_parts, workspace, workspace_bytes, stream);
+  const bool ptrs_ok = y && bn_scale && bn_shift && bn_mean && dout && weight && dz && dweight && dbias && bn_partial &&
+                       n_parts && workspace && (out || !sigmoid);
+  if (int32_t rc = head_check("unet_head_bnrelu_bwd", ptrs_ok, n, h, w, c_in, c_out, workspace_bytes)) return rc;
+  return head_bwd_impl<true, true>("unet_head_bnrelu_bwd", dtype, y, bn_scale, bn_shift, bn_mean, out, dout, n, h, w, c_in,
+                                   weight, c_out, sigmoid, dz, dweight, dbias, bn_partial, n_parts, workspace, stream);
 }
 
 // ---- the same backward with dz never stored: sums, then (after unet_bn_bwd_premasked(dy = NULL)) dy in one pass ----
@@ -803,36 +763,32 @@ extern "C" int32_t unet_head_bnrelu_bwd_sums(int32_t dtype, const void* y, const
                                              int32_t h, int32_t w, int32_t c_in, const float* weight, int32_t c_out,
                                              int32_t sigmoid, float* dweight, float* dbias, float* bn_partial,
                                              int32_t* n_parts, void* workspace, size_t workspace_bytes, void* stream) {
-  return head_bnrelu_bwd_impl<false>(dtype, y, bn_scale, bn_shift, bn_mean, out, dout, n, h, w, c_in, weight, c_out,
-                                     sigmoid, nullptr, dweight, dbias, bn_partial, n_parts, workspace, workspace_bytes,
-                                     stream);
+  const bool ptrs_ok = y && bn_scale && bn_shift && bn_mean && dout && weight && dweight && dbias && bn_partial && n_parts &&
+                       workspace && (out || !sigmoid);
+  if (int32_t rc = head_check("unet_head_bnrelu_bwd_sums", ptrs_ok, n, h, w, c_in, c_out, workspace_bytes)) return rc;
+  return head_bwd_impl<true, false>("unet_head_bnrelu_bwd_sums", dtype, y, bn_scale, bn_shift, bn_mean, out, dout, n, h, w,
+                                    c_in, weight, c_out, sigmoid, nullptr, dweight, dbias, bn_partial, n_parts, workspace,
+                                    stream);
 }
 
 extern "C" int32_t unet_head_bnrelu_bwd_apply(int32_t dtype, const void* y, const float* bn_scale, const float* bn_shift,
                                               const float* out, const float* dout, int32_t n, int32_t h, int32_t w,
                                               int32_t c_in, const float* weight, int32_t c_out, int32_t sigmoid,
                                               const float* coefs, void* dy, void* stream) {
-  UNET_REQUIRE(y && bn_scale && bn_shift && dout && weight && coefs && dy && (out || !sigmoid), UNET_ERR_BAD_ARG,
-               "unet_head_bnrelu_bwd_apply: null pointer");
-  UNET_REQUIRE(n > 0 && h > 0 && w > 0, UNET_ERR_BAD_ARG, "unet_head_bnrelu_bwd_apply: bad dims");
-  UNET_REQUIRE(c_out >= 1 && c_out <= MAXCO && (c_in == 32 || c_in == 64 || c_in == 128), UNET_ERR_UNSUPPORTED,
-               "unet_head_bnrelu_bwd_apply: %d -> %d channels unsupported", c_in, c_out);
-  hipStream_t s = (hipStream_t)stream;
-  const long long pixels = (long long)n * h * w, hw = (long long)h * w;
-  ProfScope prof(UNET_K_HEAD, 2.0 * pixels * c_in * c_out, s);
-  const long long want = cdiv64(pixels, 256);                              // a block takes 256 pixels per iteration
-  const int nb = (int)(want < 2048 ? want : 2048);
-  if (dtype == UNET_BF16) {
-    const int tpp = tpp_of<bf16_t>(c_in);
-    HEAD_TPP_SWITCH(bf16_t, tpp, hipLaunchKernelGGL((head_bnrelu_bwd_apply_kernel<bf16_t, TPP, CO>), dim3(nb), dim3(256), 0, s,
-                    (const bf16_t*)y, out, dout, pixels, hw, c_in, weight, sigmoid, bn_scale, bn_shift, coefs, (bf16_t*)dy));
-  } else if (dtype == UNET_F32) {
-    const int tpp = tpp_of<float>(c_in);
-    HEAD_TPP_SWITCH(float, tpp, hipLaunchKernelGGL((head_bnrelu_bwd_apply_kernel<float, TPP, CO>), dim3(nb), dim3(256), 0, s,
-                    (const float*)y, out, dout, pixels, hw, c_in, weight, sigmoid, bn_scale, bn_shift, coefs, (float*)dy));
-  } else {
-    unet_set_error("unet_head_bnrelu_bwd_apply: dtype %d", dtype);
-    return UNET_ERR_BAD_ARG;
-  }
-  return unet_check_launch("head_bnrelu_bwd_apply_kernel");
+  const bool ptrs_ok = y && bn_scale && bn_shift && dout && weight && coefs && dy && (out || !sigmoid);
+  if (int32_t rc = head_check("unet_head_bnrelu_bwd_apply", ptrs_ok, n, h, w, c_in, c_out)) return rc;
+  return with_dtype("unet_head_bnrelu_bwd_apply", dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipStream_t s = (hipStream_t)stream;
+    const long long pixels = (long long)n * h * w, hw = (long long)h * w;
+    ProfScope prof(UNET_K_HEAD, 2.0 * pixels * c_in * c_out, s);
+    const long long want = cdiv64(pixels, 256);                              // a block takes 256 pixels per iteration
+    const int nb = (int)(want < 2048 ? want : 2048);
+    return head_dispatch<T>(c_in, c_out, [&](auto tpp, auto co) {
+      constexpr int TPP = decltype(tpp)::value, CO = decltype(co)::value;
+      hipLaunchKernelGGL((head_bnrelu_bwd_apply_kernel<T, TPP, CO>), dim3(nb), dim3(256), 0, s, (const T*)y, out, dout,
+                         pixels, hw, c_in, weight, sigmoid, bn_scale, bn_shift, coefs, (T*)dy);
+      return unet_check_launch("head_bnrelu_bwd_apply_kernel");
+    });
+  });
 }

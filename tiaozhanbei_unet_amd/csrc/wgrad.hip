@@ -957,10 +957,9 @@ extern "C" int32_t unet_conv3x3_wgrad(int32_t dtype, int32_t n, int32_t h, int32
   P.Crow = c_out; P.Ccol = ctot;
   P.partial = (float*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == UNET_BF16) return run<bf16_t, 9>(P, pl, dw, c_out, c_in_param, UNET_K_CONV_WGRAD, s);
-  if (dtype == UNET_F32) return run<float, 9>(P, pl, dw, c_out, c_in_param, UNET_K_CONV_WGRAD, s);
-  unet_set_error("unet_conv3x3_wgrad: dtype %d", dtype);
-  return UNET_ERR_BAD_ARG;
+  return with_dtype("unet_conv3x3_wgrad", dtype, [&](auto tag) {
+    return run<decltype(tag), 9>(P, pl, dw, c_out, c_in_param, UNET_K_CONV_WGRAD, s);
+  });
 }
 
 namespace {
@@ -1242,10 +1241,9 @@ extern "C" int32_t unet_convt2x2_wgrad(int32_t dtype, int32_t n, int32_t h, int3
   P.Crow = c_in; P.Ccol = c_out;
   P.partial = (float*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  int32_t rc;
-  if (dtype == UNET_BF16) rc = run<bf16_t, 4>(P, pl, dw, c_in, c_out, UNET_K_CONVT_WGRAD, s);
-  else if (dtype == UNET_F32) rc = run<float, 4>(P, pl, dw, c_in, c_out, UNET_K_CONVT_WGRAD, s);
-  else { unet_set_error("unet_convt2x2_wgrad: dtype %d", dtype); return UNET_ERR_BAD_ARG; }
+  const int32_t rc = with_dtype("unet_convt2x2_wgrad", dtype, [&](auto tag) {
+    return run<decltype(tag), 4>(P, pl, dw, c_in, c_out, UNET_K_CONVT_WGRAD, s);
+  });
   if (rc) return rc;
   // bias gradient: column sums of dy; the partial slabs above are consumed (stream order), reuse them
   return unet_internal_colsum(dtype, dy, (int64_t)n * 4 * h * w, c_out, db, (float*)workspace, workspace_bytes, s);

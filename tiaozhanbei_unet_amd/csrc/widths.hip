@@ -68,6 +68,20 @@ __global__ __launch_bounds__(256) void widen_channels_kernel(const TI* __restric
   }
 }
 
+// pack_weight_seg_kernel over the 9 * rows * k elements of a packed 3x3 weight; scale (may be NULL): BatchNorm fold
+int32_t launch_pack_seg(const char* who, int dtype, const float* w, void* out, int c_out, int c_in, int rows, int k, int mode,
+                        int split, const float* scale, void* stream) {
+  const long long total = 9LL * rows * k;
+  hipStream_t s = (hipStream_t)stream;
+  return with_dtype(who, dtype, [&](auto tag) {
+    using T = decltype(tag);
+    ProfScope prof(UNET_K_PACK, 0.0, s, "pack_weight_seg_kernel");
+    hipLaunchKernelGGL(pack_weight_seg_kernel<T>, dim3(wd_blocks(total)), dim3(256), 0, s, w, (T*)out, c_out, c_in, rows, k,
+                       mode, split, total, scale);
+    return unet_check_launch("pack_weight_seg_kernel");
+  });
+}
+
 }  // namespace
 
 extern "C" int32_t unet_pack_weight_seg(const float* w, void* out, int32_t c_out, int32_t c_in, int32_t rows, int32_t k,
@@ -79,18 +93,7 @@ extern "C" int32_t unet_pack_weight_seg(const float* w, void* out, int32_t c_out
   const int need_ci = split > 0 ? (split + 63) / 64 * 64 + (c_in - split) : c_in;
   const int gemm_rows = mode == UNET_PACK_CONV_FWD ? c_out : need_ci, gemm_k = mode == UNET_PACK_CONV_FWD ? need_ci : c_out;
   UNET_REQUIRE(rows >= gemm_rows && k >= gemm_k, UNET_ERR_BAD_ARG, "unet_pack_weight_seg: padded dims too small");
-  const long long total = 9LL * rows * k;
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_PACK, 0.0, s, "pack_weight_seg_kernel");
-  if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(pack_weight_seg_kernel<bf16_t>, dim3(wd_blocks(total)), dim3(256), 0, s, w, (bf16_t*)out, c_out, c_in,
-                       rows, k, mode, split, total, (const float*)nullptr);
-  else if (dtype == UNET_F32)
-    hipLaunchKernelGGL(pack_weight_seg_kernel<float>, dim3(wd_blocks(total)), dim3(256), 0, s, w, (float*)out, c_out, c_in,
-                       rows, k, mode, split, total, (const float*)nullptr);
-  else
-    UNET_REQUIRE(false, UNET_ERR_BAD_ARG, "unet_pack_weight_seg: dtype %d", dtype);
-  return unet_check_launch("pack_weight_seg_kernel");
+  return launch_pack_seg("unet_pack_weight_seg", dtype, w, out, c_out, c_in, rows, k, mode, split, nullptr, stream);
 }
 
 extern "C" int32_t unet_pack_conv_weight_folded_seg(const float* w, const float* scale, void* out, int32_t c_out,
@@ -101,18 +104,8 @@ extern "C" int32_t unet_pack_conv_weight_folded_seg(const float* w, const float*
                "unet_pack_conv_weight_folded_seg: bad dims");
   const int need_ci = split > 0 ? (split + 63) / 64 * 64 + (c_in - split) : c_in;
   UNET_REQUIRE(rows >= c_out && k >= need_ci, UNET_ERR_BAD_ARG, "unet_pack_conv_weight_folded_seg: padded dims too small");
-  const long long total = 9LL * rows * k;
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(UNET_K_PACK, 0.0, s, "pack_weight_seg_kernel");
-  if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(pack_weight_seg_kernel<bf16_t>, dim3(wd_blocks(total)), dim3(256), 0, s, w, (bf16_t*)out, c_out, c_in,
-                       rows, k, (int)UNET_PACK_CONV_FWD, split, total, scale);
-  else if (dtype == UNET_F32)
-    hipLaunchKernelGGL(pack_weight_seg_kernel<float>, dim3(wd_blocks(total)), dim3(256), 0, s, w, (float*)out, c_out, c_in,
-                       rows, k, (int)UNET_PACK_CONV_FWD, split, total, scale);
-  else
-    UNET_REQUIRE(false, UNET_ERR_BAD_ARG, "unet_pack_conv_weight_folded_seg: dtype %d", dtype);
-  return unet_check_launch("pack_weight_seg_kernel");
+  return launch_pack_seg("unet_pack_conv_weight_folded_seg", dtype, w, out, c_out, c_in, rows, k, UNET_PACK_CONV_FWD, split,
+                         scale, stream);
 }
 
 extern "C" int32_t unet_remap_batched(const unet_remap_desc* descs, int32_t n, void* stream) {
@@ -146,8 +139,8 @@ extern "C" int32_t unet_widen_channels(const void* src, int32_t src_dtype, const
                                        int32_t h, int32_t w, void* dst, int32_t c_pad, int32_t dtype, void* stream) {
   UNET_REQUIRE(src && strides && dst, UNET_ERR_BAD_ARG, "unet_widen_channels: null pointer");
   UNET_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && c_pad >= c, UNET_ERR_BAD_ARG, "unet_widen_channels: bad dims");
-  UNET_REQUIRE((src_dtype == UNET_F32 || src_dtype == UNET_BF16) && (dtype == UNET_F32 || dtype == UNET_BF16),
-               UNET_ERR_BAD_ARG, "unet_widen_channels: dtype");
+  UNET_REQUIRE(dtype_known(src_dtype), UNET_ERR_BAD_ARG, "unet_widen_channels: src_dtype %d", src_dtype);
+  UNET_REQUIRE(dtype_known(dtype), UNET_ERR_BAD_ARG, "unet_widen_channels: dtype %d", dtype);
   const long long total = (long long)n * h * w * c_pad;
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof(UNET_K_PACK, 0.0, s, "widen_channels_kernel");

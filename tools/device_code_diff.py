@@ -7,6 +7,9 @@ the anonymous namespace ignored (plain_name), so a parameter type may leave it a
 
     hipcc <the Makefile's flags> -S --cuda-device-only a.hip -o old/a.s     # ... for every file of either side
     python tools/device_code_diff.py old/a.s old/b.s -- new/c.s new/d.s     # exit code 1 on any difference
+
+--gone REGEX (before the files) names, by their mangled names, the kernels the change means to drop: those must be missing
+from the new build -- one that is still there counts as a difference, and so does any other missing kernel.
 """
 import re
 import sys
@@ -50,19 +53,29 @@ def kernels(paths):
 
 
 def main():
-    cut = sys.argv.index("--")
-    old, new = kernels(sys.argv[1:cut]), kernels(sys.argv[cut + 1:])
-    bad = 0
+    args = sys.argv[1:]
+    gone = re.compile(args[1]) if args[0] == "--gone" else None
+    args = args[2:] if gone else args
+    cut = args.index("--")
+    old, new = kernels(args[:cut]), kernels(args[cut + 1:])
+    bad = dropped = 0
     for name in sorted(set(old) | set(new)):
-        if name not in old or name not in new:
+        if gone and gone.search(name):
+            if name in new:
+                print("STILL in the new build: " + name)
+                bad += 1
+            dropped += name in old
+        elif name not in old or name not in new:
             print(("MISSING in the new build: " if name in old else "EXTRA in the new build: ") + name)
             bad += 1
         elif old[name] != new[name]:
             what = "instructions" if old[name][0] != new[name][0] else "descriptor " + str((old[name][1], new[name][1]))
             print(f"DIFFERENT ({what}): {name}")
             bad += 1
+    if gone:
+        print(f"{dropped} kernels of the old build dropped as expected")
     print(f"{len(old)} kernels of the old build, {len(new)} of the new, {bad} missing, extra or different; "
-          f"{sum(len(v[0]) for v in old.values())} instructions compared")
+          f"{sum(len(v[0]) for n, v in old.items() if n in new)} instructions compared")
     sys.exit(1 if bad else 0)
 
 
