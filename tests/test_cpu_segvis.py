@@ -105,7 +105,7 @@ def test_lut_index_rule_equals_matplotlib():
 
 def test_product_tables_equal_the_restatement_without_matplotlib():
     from tiaozhanbei_unet_amd import ops
-    for name in ("ops.py", "seg_visualize.py", "visualize_gear.py", "visualize_kolektorsdd.py", "_viridis.py"):
+    for name in ("ops.py", "sheets.py", "seg_visualize.py", "visualize_gear.py", "visualize_kolektorsdd.py", "_viridis.py"):
         src = open(os.path.join(ROOT, "tiaozhanbei_unet_amd", name)).read()
         assert not re.search(r"^\s*(import|from)\s+matplotlib", src, re.M), name
     assert "matplotlib" not in open(os.path.join(ROOT, "tests", "_segvis_ref.py")).read().split('"""', 2)[2]

@@ -7,7 +7,7 @@ defects the model found, how many false alarms per image it raised, which parts 
 
 Takes the flags of ``eval_gear`` / ``eval_kolektorsdd`` for data, model, split, batch, workers, device, precision and
 save_dir, and uses their loaders, device preprocessing, class names and model construction.  Per batch: model forward,
-``metrics.per_image_stats(labels=True)`` for the argmax map, ``ops.ClassRegionMatcher.update`` (csrc/segregions.hip:
+``metrics.per_image_stats(labels=True)`` for the argmax map, ``evaluation.ClassRegionMatcher.update`` (csrc/segregions.hip:
 8-connected regions per class of truth and prediction, and how many pixels of each the other map covers); everything
 is read back once, after the last batch.  ``--min_region_pixels`` drops smaller predicted regions before anything is
 counted; a region counts at a coverage threshold t iff it has a common pixel and ``hit >= t * size``
@@ -60,7 +60,7 @@ def match(model, batches, num_classes, min_pixels):
     """Eval-mode pass over (images, masks, paths) device batches: the matcher's result, the paths, the frame width."""
     import torch
     from .metrics import per_image_stats
-    from .ops import ClassRegionMatcher
+    from .evaluation import ClassRegionMatcher
     model.eval()
     matcher, paths, width = ClassRegionMatcher(num_classes, min_pixels), [], 1
     with torch.no_grad():

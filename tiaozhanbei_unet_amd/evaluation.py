@@ -1,0 +1,387 @@
+"""Evaluation on the device, outside autograd: scores, confusion counts, AUROC / AUPRC, AUPRO, class regions, uint8 input."""
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+from ._hipcall import _ptr, _require_cuda, _stream, _workspace
+
+
+def anomaly_score(reconstruction, original, l1=False):
+    """(score map [N, H, W], image score [N]) of compute_anomaly_score (/root/reference/src/utils.py:205-215)."""
+    _require_cuda(reconstruction, original)
+    r = reconstruction.detach().contiguous().float()
+    o = original.detach().contiguous().float()
+    n, c = r.shape[0], r.shape[1]
+    hw = int(r.numel() // (n * c))
+    score = torch.empty((n,) + tuple(r.shape[2:]), dtype=torch.float32, device=r.device)
+    img = torch.empty(n, dtype=torch.float32, device=r.device)
+    lib = L.lib()
+    ws = _workspace(lib.unet_anomaly_score_workspace(n, hw), r.device)
+    L.check(lib.unet_anomaly_score(_ptr(r), _ptr(o), n, c, hw, 1 if l1 else 0, _ptr(score), _ptr(img), _ptr(ws), ws.numel(),
+                                   _stream()), "unet_anomaly_score")
+    return score, img
+
+
+def threshold_confusion(pred, truth, thresholds, select=None, counts=None):
+    """Confusion counts [K][4] = {tp, fp, fn, tn} (int64 DEVICE tensor; pass it back as ``counts`` to keep accumulating
+    over batches, read it once at the end) of (pred > t) against (truth > 0.5) for each threshold, over the images with
+    select[n] true (None: all): the pixel-metric epilogue of /root/reference/src/test.py:79-106 and
+    src/train_utils.py:232-245 on the device (unet_threshold_confusion)."""
+    _require_cuda(pred)
+    p = pred.detach().contiguous().float()
+    t = truth.detach().to(p.device).contiguous().float()
+    if p.shape != t.shape or p.dim() < 2:
+        raise ValueError("threshold_confusion: prediction / truth shapes differ")
+    n = p.shape[0]
+    per = p.numel() // n
+    values = [float(v) for v in thresholds]
+    if not values:
+        raise ValueError("threshold_confusion: at least one threshold")
+    sel = None if select is None else torch.as_tensor(select).to(device=p.device, dtype=torch.uint8).contiguous()
+    if counts is None:
+        counts = torch.zeros((len(values), 4), dtype=torch.int64, device=p.device)
+    if tuple(counts.shape) != (len(values), 4):
+        raise ValueError("threshold_confusion: counts must be [len(thresholds), 4]")
+    for k in range(0, len(values), 8):           # the kernel takes up to 8 thresholds per pass over the maps
+        thr = torch.tensor(values[k:k + 8], dtype=torch.float32, device=p.device)
+        L.check(L.lib().unet_threshold_confusion(_ptr(p), _ptr(t), _ptr(sel), n, per, _ptr(thr), thr.numel(),
+                                                 _ptr(counts[k:k + 8]), _stream()), "unet_threshold_confusion")
+    return counts
+
+
+def _select_runs(select, n, what):
+    """(runs, device mask) of a per-image selection: a device mask goes to the kernels as it is (one run, all images); a
+    host mask becomes one launch per run of selected images, so nothing is copied and nothing synchronises."""
+    if select is None:
+        return [(0, n)], None
+    sel = torch.as_tensor(select)
+    if sel.numel() != n:
+        raise ValueError(f"{what}: select needs one entry per image")
+    if sel.is_cuda:
+        return [(0, n)], sel.reshape(-1).to(torch.uint8).contiguous()
+    on = sel.reshape(-1).to(torch.bool).tolist() + [False]
+    runs, start = [], None
+    for i, v in enumerate(on):
+        if v and start is None:
+            start = i
+        elif not v and start is not None:
+            runs.append((start, i))
+            start = None
+    return runs, None
+
+
+class BinaryAUC:
+    """Pixel-level AUROC / AUPRC accumulated over batches: the roc_auc_score and auc(precision_recall_curve) that
+    the reference src/utils.py:84-91 computes for calculate_pixel_metrics (:97-108), on the device.  A pixel is
+    positive iff truth > 0.5; ties are float equality (-0.0 == +0.0).  ``update`` appends the selected pixels' scores
+    as sort keys (unet_rank_auc_append) without synchronising; ``compute`` reads the counts once, sorts and ranks
+    (unet_rank_auc).  No positives, no negatives or any NaN / inf score give 0.0 / 0.0, as calculate_metrics does when
+    sklearn refuses.  The result depends only on the multiset of (score, label) pixels, bitwise."""
+
+    def __init__(self):
+        self._chunks = []                     # (keys, capacity, counts): one exactly-sized key chunk per update
+
+    def update(self, pred, truth, select=None):
+        """pred / truth: device tensors of equal shape [N, ...]; select: host or device bool per image (None: all)."""
+        _require_cuda(pred)
+        p = pred.detach().contiguous().float()
+        t = truth.detach().to(p.device).contiguous().float()
+        if p.shape != t.shape or p.dim() < 2:
+            raise ValueError("BinaryAUC.update: prediction / truth shapes differ")
+        n = p.shape[0]
+        per = p.numel() // n
+        runs, sel = _select_runs(select, n, "BinaryAUC.update")
+        cap = sum(b - a for a, b in runs) * per
+        if cap == 0:
+            return
+        keys = torch.empty(cap, dtype=torch.int32, device=p.device)
+        counts = torch.zeros(3, dtype=torch.int64, device=p.device)
+        lib = L.lib()
+        for a, b in runs:
+            L.check(lib.unet_rank_auc_append(_ptr(p[a:b]), _ptr(t[a:b]), _ptr(sel), b - a, per, _ptr(keys), cap,
+                                             _ptr(counts), _stream()), "unet_rank_auc_append")
+        self._chunks.append((keys, cap, counts))
+
+    def compute(self):
+        """{"auroc", "auprc", "positives", "negatives", "nonfinite"} over every pixel passed to update."""
+        totals = [0, 0, 0]
+        if self._chunks:
+            per_chunk = torch.stack([c for _, _, c in self._chunks]).tolist()      # the one read of the counts
+            totals = [sum(c[i] for c in per_chunk) for i in range(3)]
+        n_pos, n_neg, nonfinite = totals
+        res = {"auroc": 0.0, "auprc": 0.0, "positives": n_pos, "negatives": n_neg, "nonfinite": nonfinite}
+        if nonfinite or not n_pos or not n_neg:
+            return res
+        lib = L.lib()
+        nbytes = lib.unet_rank_auc_workspace(n_pos, n_neg)
+        if nbytes == 0:
+            raise RuntimeError(f"BinaryAUC: {n_pos + n_neg} pixels, at most 2^31 - 1 are supported")
+        dev = self._chunks[0][0].device
+        pos = torch.cat([k[:c[0]] for (k, _, _), c in zip(self._chunks, per_chunk)])          # copies: the sort
+        neg = torch.cat([k[cap - c[1]:] for (k, cap, _), c in zip(self._chunks, per_chunk)])  # is in place
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+        L.check(lib.unet_rank_auc(_ptr(pos), n_pos, _ptr(neg), n_neg, _ptr(out), _ptr(ws), nbytes, _stream()),
+                "unet_rank_auc")
+        res["auroc"], res["auprc"] = out.tolist()
+        return res
+
+
+def _image_planes(t, what):
+    """[N, H, W] view of a [N, ..., H, W] tensor with one plane per image ([N, W]: one row)."""
+    if t.dim() < 2:
+        raise ValueError(f"{what}: needs [N, ...] maps")
+    n, w = t.shape[0], t.shape[-1]
+    h = t.shape[-2] if t.dim() >= 3 else 1
+    if n == 0 or t.numel() != n * h * w:
+        raise ValueError(f"{what}: one H x W plane per image, got {tuple(t.shape)}")
+    return t.reshape(n, h, w)
+
+
+def label_regions(truth, select=None, _runs=None):
+    """8-connected regions of the defective pixels (truth > 0.5) of each image of truth [N, (1,) H, W], over the images
+    with select[n] true (None: all): (labels, sizes, counts), all DEVICE tensors.  labels (int32, truth's shape) = 1 +
+    the smallest linear index y * W + x of the pixel's region, sizes (int32) = the region's pixel count at each of its
+    pixels, both 0 elsewhere; counts (int64 [3]) = {regions, defective pixels, ok pixels} of the selected images.
+    scipy.ndimage.label(mask, np.ones((3, 3))) on the device (unet_label_regions); does not synchronise."""
+    _require_cuda(truth)
+    t = _image_planes(truth.detach().contiguous().float(), "label_regions")
+    n, h, w = t.shape
+    runs, sel = _runs if _runs is not None else _select_runs(select, n, "label_regions")
+    lib = L.lib()
+    labels = torch.zeros((n, h, w), dtype=torch.int32, device=t.device)
+    sizes = torch.zeros((n, h, w), dtype=torch.int32, device=t.device)
+    counts = torch.zeros(3, dtype=torch.int64, device=t.device)
+    for a, b in runs:
+        nbytes = lib.unet_label_regions_workspace(b - a, h, w)
+        if nbytes == 0:
+            raise RuntimeError(f"label_regions: {b - a} x {h} x {w} is not supported (n < 65536, at most 2^31 - 1 pixels)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+        L.check(lib.unet_label_regions(_ptr(t[a:b]), _ptr(sel), b - a, h, w, _ptr(labels[a:b]), _ptr(sizes[a:b]),
+                                       _ptr(counts), _ptr(ws), nbytes, _stream()), "unet_label_regions")
+    return labels.reshape(truth.shape), sizes.reshape(truth.shape), counts
+
+
+class RegionOverlapAUC:
+    """AUPRO accumulated over batches: the area below the per-region-overlap curve of the MVTec AD evaluation up to a
+    false-positive rate of ``fpr_limit``, divided by it.  A pixel is defective iff truth > 0.5, a region is an
+    8-connected component of defective pixels of one image, and every region weighs the same: a defective pixel lifts
+    the curve by 1 / (regions * its region's size).  ``update`` labels the batch's regions (unet_label_regions) and
+    appends the selected pixels as sort keys and (key, size) elements (unet_region_auc_append) without synchronising;
+    only those and the counts are kept.  ``compute`` reads the counts once, sorts and integrates (unet_region_auc).
+    No region, no ok pixel or any NaN / inf score give 0.0.  The result depends only on the multiset of (score, region
+    size) pixels, bitwise."""
+
+    def __init__(self, fpr_limit=0.3):
+        self.fpr_limit = float(fpr_limit)
+        if not 0.0 < self.fpr_limit <= 1.0:
+            raise ValueError(f"RegionOverlapAUC: fpr_limit {fpr_limit} is not in (0, 1]")
+        self._chunks = []                     # (slots, capacity, counts[6]): one exactly-sized chunk per update
+        self._max_region = 1
+
+    def update(self, pred, truth, select=None):
+        """pred / truth: device tensors of equal shape [N, (1,) H, W]; select: host or device bool per image."""
+        _require_cuda(pred)
+        p = pred.detach().contiguous().float()
+        t = truth.detach().to(p.device).contiguous().float()
+        if p.shape != t.shape:
+            raise ValueError("RegionOverlapAUC.update: prediction / truth shapes differ")
+        p = _image_planes(p, "RegionOverlapAUC.update")
+        n, per = p.shape[0], p.shape[1] * p.shape[2]
+        runs, sel = _select_runs(select, n, "RegionOverlapAUC.update")
+        cap = sum(b - a for a, b in runs) * per
+        if cap == 0:
+            return
+        _, sizes, regions = label_regions(t, _runs=(runs, sel))
+        sizes = sizes.reshape(p.shape)
+        slots = torch.empty(cap, dtype=torch.int64, device=p.device)
+        counts = torch.zeros(3, dtype=torch.int64, device=p.device)
+        lib = L.lib()
+        for a, b in runs:
+            L.check(lib.unet_region_auc_append(_ptr(p[a:b]), _ptr(sizes[a:b]), _ptr(sel), b - a, per, _ptr(slots), cap,
+                                               _ptr(counts), _stream()), "unet_region_auc_append")
+        self._chunks.append((slots, cap, torch.cat([counts, regions])))
+        self._max_region = max(self._max_region, per)
+
+    def compute(self):
+        """{"aupro", "pro_at_limit", "fpr_limit", "regions", "defective", "ok", "nonfinite"} over every update."""
+        totals = [0] * 6
+        if self._chunks:
+            per_chunk = torch.stack([c for _, _, c in self._chunks]).tolist()      # the one read of the counts
+            totals = [sum(c[i] for c in per_chunk) for i in range(6)]
+        n_pos, n_neg, nonfinite, regions, defective, ok = totals
+        res = {"aupro": 0.0, "pro_at_limit": 0.0, "fpr_limit": self.fpr_limit, "regions": regions,
+               "defective": defective, "ok": ok, "nonfinite": nonfinite}
+        if nonfinite or not regions or not ok:
+            return res
+        lib = L.lib()
+        nbytes = lib.unet_region_auc_workspace(n_pos, n_neg)
+        if nbytes == 0:
+            raise RuntimeError(f"RegionOverlapAUC: {n_pos + n_neg} pixels, at most 2^31 - 1 are supported")
+        dev = self._chunks[0][0].device
+        pos = torch.cat([s[:c[0]] for (s, _, _), c in zip(self._chunks, per_chunk)])          # copies: the sort
+        neg = torch.cat([s.view(torch.int32)[2 * cap - c[1]:]                                 # destroys its input
+                         for (s, cap, _), c in zip(self._chunks, per_chunk)])
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+        L.check(lib.unet_region_auc(_ptr(pos), n_pos, _ptr(neg), n_neg, regions, self._max_region, self.fpr_limit,
+                                    _ptr(out), _ptr(ws), nbytes, _stream()), "unet_region_auc")
+        res["aupro"], res["pro_at_limit"] = out.tolist()
+        return res
+
+
+def _class_maps(labels, what):
+    """uint8 [N, H, W] device maps of integer label maps; values outside 0..254 become 255 (background)."""
+    _require_cuda(labels)
+    t = labels.detach()
+    if t.dtype != torch.uint8:
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise ValueError(f"{what}: integer label maps, got {t.dtype}")
+        t = t.long()
+        t = torch.where((t >= 0) & (t < 255), t, torch.full_like(t, 255)).to(torch.uint8)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"{what}: [N, H, W] label maps, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _class_regions_error(what, n, h, w, num_classes):
+    return RuntimeError(f"{what}: {n} x {h} x {w} maps of {num_classes} classes are not supported (n < 65536, at most "
+                        "2^31 - 1 pixels, 2..255 classes)")
+
+
+def label_class_regions(labels_u8, num_classes):
+    """Class regions of integer label maps [N, H, W]: a pixel has class c iff its value is c with 1 <= c < num_classes
+    (0 and every value >= num_classes, 255 among them, are background), and a class region is an 8-connected component
+    of pixels of one class in one image.  Returns (region, sizes, counts), DEVICE tensors: region (int32 [N, H, W]) =
+    1 + the smallest linear index y * W + x of the pixel's region, sizes (int32) = the region's pixel count at each of
+    its pixels, both 0 on background; counts (int64 [N, num_classes]) = regions per image and class.  Per class,
+    scipy.ndimage.label(map == c, np.ones((3, 3))) on the device (unet_label_class_regions); does not synchronise."""
+    t = _class_maps(labels_u8, "label_class_regions")
+    n, h, w = t.shape
+    c = int(num_classes)
+    lib = L.lib()
+    nbytes = lib.unet_label_class_regions_workspace(n, h, w, c) if 0 <= c < 2 ** 31 else 0
+    if nbytes == 0:
+        raise _class_regions_error("label_class_regions", n, h, w, num_classes)
+    region = torch.empty((n, h, w), dtype=torch.int32, device=t.device)
+    sizes = torch.empty((n, h, w), dtype=torch.int32, device=t.device)
+    counts = torch.zeros((n, c), dtype=torch.int64, device=t.device)
+    ws = _workspace(nbytes, t.device)
+    L.check(lib.unet_label_class_regions(_ptr(t), n, h, w, c, _ptr(region), _ptr(sizes), _ptr(counts), _ptr(ws),
+                                         ws.numel(), _stream()), "unet_label_class_regions")
+    return region, sizes, counts
+
+
+RECORD_FIELDS = ("image", "class", "root", "size", "hit")
+
+
+class ClassRegionMatcher:
+    """Defect-level matching of predicted against true label maps, accumulated over batches.  Regions are those of
+    ``label_class_regions``; a predicted region is kept iff it has at least ``min_pixels`` pixels.  ``hit`` of a truth
+    region = its pixels whose predicted class is the region's and whose predicted region is kept; ``hit`` of a kept
+    predicted region = its pixels whose truth class is its class (unet_match_class_regions; integers throughout).
+
+    ``update`` labels truth and prediction in one call, matches them and keeps only the batch's two record buffers and
+    its counts; it does not synchronise.  The buffers have to hold one record per pixel when they are made (the device
+    alone knows how many regions there are), so the record counts travel to pinned host memory behind the kernels, and a
+    later ``update`` trims every buffer whose counts have arrived, without waiting.  ``compute`` reads everything back
+    once."""
+
+    def __init__(self, num_classes, min_pixels=1):
+        self.num_classes, self.min_pixels = int(num_classes), int(min_pixels)
+        if not 2 <= self.num_classes <= 255:
+            raise ValueError(f"ClassRegionMatcher: {num_classes} classes, 2..255 are supported")
+        if self.min_pixels < 1:
+            raise ValueError(f"ClassRegionMatcher: min_pixels {min_pixels} is below 1")
+        self.images = 0
+        self._chunks = []          # [truth records, pred records, class counts [2n, C], host counts, event or None]
+
+    def _trim(self, wait):
+        for ch in self._chunks:
+            if ch[4] is None or not (wait or ch[4].query()):
+                continue
+            if wait:
+                ch[4].synchronize()
+            kt, kp = ch[3].tolist()
+            if kt > ch[0].shape[0] or kp > ch[1].shape[0]:
+                raise RuntimeError("ClassRegionMatcher: more records than pixels")      # cannot happen
+            ch[0], ch[1], ch[4] = ch[0][:kt].clone(), ch[1][:kp].clone(), None
+
+    def update(self, pred_labels, truth):
+        """pred_labels / truth: integer device label maps of equal shape [N, H, W] (the uint8 argmax of
+        ``metrics.per_image_stats(..., labels=True)`` and the loaders' masks; values outside 0..254 become 255)."""
+        p = _class_maps(pred_labels, "ClassRegionMatcher.update")
+        t = _class_maps(truth.to(p.device), "ClassRegionMatcher.update")
+        if p.shape != t.shape:
+            raise ValueError("ClassRegionMatcher.update: prediction / truth shapes differ")
+        self._trim(wait=False)
+        n, h, w = p.shape
+        c, dev = self.num_classes, p.device
+        region, sizes, class_counts = label_class_regions(torch.cat([t, p]), c)      # one pass labels both
+        lib = L.lib()
+        nbytes = lib.unet_match_class_regions_workspace(n, h, w, c)
+        if nbytes == 0 or self.images + n >= 2 ** 31:
+            raise _class_regions_error("ClassRegionMatcher.update", n, h, w, c)
+        cap = n * h * w
+        records = [torch.empty((cap, len(RECORD_FIELDS)), dtype=torch.int32, device=dev) for _ in range(2)]
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        ws = _workspace(nbytes, dev)
+        L.check(lib.unet_match_class_regions(_ptr(t), _ptr(region[:n]), _ptr(sizes[:n]), _ptr(p), _ptr(region[n:]),
+                                             _ptr(sizes[n:]), n, h, w, c, self.min_pixels, self.images,
+                                             _ptr(records[0]), _ptr(records[1]), cap, _ptr(counts), _ptr(ws),
+                                             ws.numel(), _stream()), "unet_match_class_regions")
+        host = torch.empty(2, dtype=torch.int64, pin_memory=True)
+        host.copy_(counts, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self._chunks.append([records[0], records[1], class_counts, host, done])
+        self.images += n
+
+    def compute(self):
+        """{"truth", "pred"}: int32 [K, 5] numpy records (image, class, root index y * W + x, size, hit), the image index
+        counted over all updates, sorted by (image, root index); {"truth_counts", "pred_counts"}: int64
+        [images, num_classes] regions per image and class (pred_counts before the min_pixels rule); "images"."""
+        import numpy as np
+        c, f = self.num_classes, len(RECORD_FIELDS)
+        empty = np.zeros((0, f), np.int32)
+        res = {"truth": empty, "pred": empty.copy(), "truth_counts": np.zeros((0, c), np.int64),
+               "pred_counts": np.zeros((0, c), np.int64), "images": self.images}
+        if not self._chunks:
+            return res
+        self._trim(wait=True)
+        parts = [ch[0].reshape(-1) for ch in self._chunks] + [ch[1].reshape(-1) for ch in self._chunks]
+        parts += [ch[2].to(torch.int32).reshape(-1) for ch in self._chunks]          # a count is below 2^31 pixels
+        flat = torch.cat(parts).cpu().numpy()                                       # the one read-back
+        kt = sum(ch[0].shape[0] for ch in self._chunks) * f
+        kp = sum(ch[1].shape[0] for ch in self._chunks) * f
+        for key, rec in (("truth", flat[:kt]), ("pred", flat[kt:kt + kp])):
+            rec = rec.reshape(-1, f)
+            res[key] = np.ascontiguousarray(rec[np.lexsort((rec[:, 2], rec[:, 0]))])
+        at, tc, pc = kt + kp, [], []
+        for ch in self._chunks:
+            n = ch[2].shape[0] // 2
+            both = flat[at:at + 2 * n * c].reshape(2, n, c).astype(np.int64)
+            tc.append(both[0]); pc.append(both[1])
+            at += 2 * n * c
+        res["truth_counts"], res["pred_counts"] = np.concatenate(tc), np.concatenate(pc)
+        return res
+
+
+def preprocess_u8(images_u8, flips=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    """uint8 [N, H, W, 3] device batch -> normalised fp32 NCHW (ToTensor + Normalize, optional per-sample horizontal
+    flip): /root/reference/src/dataset.py:134-146, src/kolektorsdd_dataset.py:133-150, on the GPU."""
+    _require_cuda(images_u8)
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3:
+        raise ValueError("preprocess_u8 expects a uint8 [N, H, W, 3] tensor")
+    images_u8 = images_u8.contiguous()
+    n, h, w, _ = images_u8.shape
+    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=images_u8.device)
+    fl = None
+    if flips is not None:
+        fl = flips.to(device=images_u8.device, dtype=torch.uint8).contiguous()
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s_ = (C.c_float * 3)(*[float(v) for v in std])
+    L.check(L.lib().unet_preprocess_u8(_ptr(images_u8), _ptr(fl), _ptr(out), n, h, w, m, s_, _stream()),
+            "unet_preprocess_u8")
+    return out

@@ -1,4 +1,4 @@
-"""Defect-level figures of a segmentation checkpoint from the region records of ``ops.ClassRegionMatcher``: how many
+"""Defect-level figures of a segmentation checkpoint from the region records of ``evaluation.ClassRegionMatcher``: how many
 defects were found, how many false alarms were raised per image, which parts would have been rejected.  Pure numpy on
 the host; every count is an integer and every ratio one float64 division.
 

@@ -2,9 +2,9 @@
 visualize.py and visualize_kolektorsdd.py): load a checkpoint, run the model in eval mode over the first
 ``--num_samples`` samples of the split in loader order, and write the pictures into ``--save_dir``.
 
-Per batch one forward, one ``ops.seg_confidence`` launch (label map and per-pixel confidence, csrc/segvis.hip) and one
+Per batch one forward, one ``sheets.seg_confidence`` launch (label map and per-pixel confidence, csrc/segvis.hip) and one
 ``metrics.per_image_stats`` launch (csrc/segeval.hip); the collected tensors stay on the device, and every picture is
-one ``ops.render_seg_sheet`` launch whose uint8 sheet is read back and encoded once by Pillow.  matplotlib is not
+one ``sheets.render_seg_sheet`` launch whose uint8 sheet is read back and encoded once by Pillow.  matplotlib is not
 used: a sheet is at the native resolution of the tensors, its bytes are a function of the inputs alone, and it
 carries no titles, legend or colour bar -- the text is in the JSON files beside it:
 
@@ -30,7 +30,7 @@ import torch
 GUTTER = 4                  # pixels of white between panels
 OVERLAY_ALPHA = 0.4         # reference visualize.py:138-139
 
-# the panels of a picture by name -> the ops.render_seg_sheet column
+# the panels of a picture by name -> the sheets.render_seg_sheet column
 _COLUMNS = {"image": lambda s, a: ("image",),
             "truth": lambda s, a: ("classes", s["masks"]),
             "prediction": lambda s, a: ("classes", s["labels"]),
@@ -72,7 +72,7 @@ def collect(model, batches, num_samples, want_conf=True):
     (reference visualize.py:351-373).  Returns device tensors ``images`` (n, 3, H, W), ``masks`` int64, ``labels`` uint8,
     ``conf`` float32 or None, ``confusion`` int64 (n, C, C), ``conf_mean`` / ``conf_std`` float64 (n,), and ``paths``;
     None when the split is empty."""
-    from . import ops
+    from . import sheets
     from .metrics import per_image_stats
     model.eval()
     keys = ("images", "masks", "labels", "conf", "confusion", "conf_mean", "conf_std")
@@ -82,7 +82,7 @@ def collect(model, batches, num_samples, want_conf=True):
             if len(paths) >= num_samples:
                 break
             outputs = model(images)
-            labels, conf = ops.seg_confidence(outputs, labels=True, conf=want_conf)
+            labels, conf = sheets.seg_confidence(outputs, labels=True, conf=want_conf)
             st = per_image_stats(outputs, masks)
             take = min(images.shape[0], num_samples - len(paths))
             for k, t in (("images", images), ("masks", masks), ("labels", labels), ("conf", conf),
@@ -103,9 +103,9 @@ def sample_slice(samples, lo, hi):
 
 
 def sheet(samples, panels, palette, per_row=1, alpha=OVERLAY_ALPHA):
-    """One ``ops.render_seg_sheet`` launch: the named ``panels`` of every sample of ``samples``, a device tensor."""
-    from . import ops
-    return ops.render_seg_sheet(samples["images"], [_COLUMNS[p](samples, alpha) for p in panels], gutter=GUTTER,
+    """One ``sheets.render_seg_sheet`` launch: the named ``panels`` of every sample of ``samples``, a device tensor."""
+    from . import sheets
+    return sheets.render_seg_sheet(samples["images"], [_COLUMNS[p](samples, alpha) for p in panels], gutter=GUTTER,
                                 per_row=per_row, palette=palette)
 
 
@@ -117,9 +117,9 @@ def save_png(sheet_u8, path):
 def run(args, title, split_loader, batches, class_names_of, style, log=print):
     """The visualiser body.  split_loader(args) -> (loader of the --split, num_classes); batches(loader, device) ->
     iterable of (images, masks, paths) device batches; class_names_of(dataset, num_classes) -> names; style:
-    ``palette`` (the ops.class_palette mode), ``individual`` / ``grid`` (panel names), ``save_individual`` /
+    ``palette`` (the sheets.class_palette mode), ``individual`` / ``grid`` (panel names), ``save_individual`` /
     ``save_grid`` (bools)."""
-    from . import ops
+    from . import sheets
     from .metrics import image_prediction_stats
     from .train_gear import build_seg_model
     from .utils import load_checkpoint
@@ -148,7 +148,7 @@ def run(args, title, split_loader, batches, class_names_of, style, log=print):
     n = len(samples["paths"])
     log(f"Collected {n} samples for visualization")
 
-    host_palette = ops.class_palette(num_classes, style["palette"])
+    host_palette = sheets.class_palette(num_classes, style["palette"])
     palette = host_palette.to(device)
     stats = [image_prediction_stats(cm, mu, sd, class_names)
              for cm, mu, sd in zip(samples["confusion"].cpu().numpy(), samples["conf_mean"].tolist(),

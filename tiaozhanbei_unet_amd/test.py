@@ -2,7 +2,7 @@
 """Evaluation CLI with the reference's contract (/root/reference/src/test.py: flags :26-61, test_model :66-133,
 `test_metrics.json` / `detailed_results.json` :187-232, `visualizations.png` :315-332) on the HIP path.  The forward
 runs on the GPU; thresholding and metrics are host numpy, as in the reference; the visualisation sheet is rendered on
-the GPU (ops.render_sheet) and only encoded on the host."""
+the GPU (sheets.render_sheet) and only encoded on the host."""
 import argparse
 import json
 import os
@@ -47,14 +47,14 @@ def parse_args(argv=None):
 
 def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None, pro_fpr_limit=0.3,
                binary_masks=False):
-    from . import AnomalyUNet, ops
+    from . import AnomalyUNet, evaluation
     from .utils import compute_anomaly_score, get_optimal_threshold
     model.eval()
     out = {k: [] for k in ("images", "reconstructions", "anomaly_maps", "masks_true", "labels", "anomaly_types",
                            "image_paths", "anomaly_scores")}
     pix = None
-    pix_auc = ops.BinaryAUC()         # pixel AUROC / AUPRC of the anomalous images, ranked on the device (:172-178)
-    pix_pro = ops.RegionOverlapAUC(pro_fpr_limit)     # AUPRO over every test image (good ones supply ok pixels)
+    pix_auc = evaluation.BinaryAUC()  # pixel AUROC / AUPRC of the anomalous images, ranked on the device (:172-178)
+    pix_pro = evaluation.RegionOverlapAUC(pro_fpr_limit)     # AUPRO over every test image (good ones supply ok pixels)
     with torch.no_grad():
         from .train_utils import _batches
         for batch, images, _ in _batches(test_loader, device):     # (raw uint8 batches are transformed on the device)
@@ -65,7 +65,7 @@ def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None
             masks = (batch["mask"] > 0).float() if binary_masks else batch["mask"]
             if pixel_thresholds:          # pixel-level confusion counts of the anomalous images, on the device (:86-101)
                 bad = torch.as_tensor(np.asarray(batch["label"]) == 1)
-                pix = ops.threshold_confusion(amap, masks, pixel_thresholds, select=bad, counts=pix)
+                pix = evaluation.threshold_confusion(amap, masks, pixel_thresholds, select=bad, counts=pix)
                 pix_auc.update(amap, masks, select=bad)
                 pix_pro.update(amap, masks)
             out["anomaly_scores"].extend(compute_anomaly_score(recon, images).cpu().numpy())
@@ -123,10 +123,10 @@ def save_visualizations(results, out_dir, max_samples, with_reconstruction, over
     """`visualizations.png` of the reference (src/test.py:315-332 -> src/utils.py:111-157 visualize_results): a random
     choice of min(max_samples, all) test samples, one row each: original | true mask (gray) | predicted map (hot) |
     reconstruction (with_reconstruction) | map over original (overlay_alpha).  Rendered on the device at native resolution
-    (ops.render_sheet), encoded once with Pillow; no titles or axes: `visualizations.json` beside it names, row by row,
+    (sheets.render_sheet), encoded once with Pillow; no titles or axes: `visualizations.json` beside it names, row by row,
     what matplotlib's titles would.  Returns the path of the PNG (None when there is nothing to draw)."""
     from PIL import Image
-    from . import ops
+    from . import sheets
     total = len(results["images"])
     n = min(max_samples, total)
     if n <= 0:
@@ -141,7 +141,7 @@ def save_visualizations(results, out_dir, max_samples, with_reconstruction, over
         columns.append(("unit", torch.stack([results["reconstructions"][i] for i in indices]).to(dev)))
     if overlay_alpha is not None:
         columns.append(("overlay", images, maps, float(overlay_alpha)))
-    sheet = ops.render_sheet(columns, gutter=VIS_GUTTER)
+    sheet = sheets.render_sheet(columns, gutter=VIS_GUTTER)
     path = os.path.join(out_dir, "visualizations.png")
     Image.fromarray(sheet.cpu().numpy()).save(path)
     names = {"image": "original", "gray": "mask_true", "hot": "anomaly_map", "unit": "reconstruction",

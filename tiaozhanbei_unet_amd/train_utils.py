@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .evaluation import threshold_confusion
 from .utils import AverageMeter, calculate_metrics, compute_anomaly_score, metrics_from_counts
 
 
@@ -137,8 +138,8 @@ def validate_epoch(model, val_loader, criterion, device):
             masks_true.extend(masks.cpu().numpy())
             masks_pred.extend(anomaly_map.cpu().numpy())
             # pixel metrics of the anomalous images (:232-245): confusion counts at the three thresholds on the device
-            pix_counts = ops.threshold_confusion(anomaly_map, masks, PIXEL_THRESHOLDS,
-                                                 select=torch.as_tensor(np.asarray(batch["label"]) == 1), counts=pix_counts)
+            pix_counts = threshold_confusion(anomaly_map, masks, PIXEL_THRESHOLDS,
+                                             select=torch.as_tensor(np.asarray(batch["label"]) == 1), counts=pix_counts)
     labels, scores = np.array(labels), np.array(scores)
     masks_true, masks_pred = np.array(masks_true), np.array(masks_pred)
     predictions = {"labels": labels, "scores": scores, "masks_true": masks_true, "masks_pred": masks_pred}

@@ -60,14 +60,14 @@ def compute_anomaly_score(reconstruction, original, method="mse"):
     if method not in ("mse", "ssim", "l1"):
         raise ValueError(f"Unknown method: {method}")
     if reconstruction.is_cuda and original.is_cuda and reconstruction.dim() == 4:
-        from . import ops
-        return ops.anomaly_score(reconstruction, original, l1=(method == "l1"))[0]
+        from . import evaluation
+        return evaluation.anomaly_score(reconstruction, original, l1=(method == "l1"))[0]
     diff = reconstruction - original
     return diff.abs().mean(dim=1) if method == "l1" else (diff * diff).mean(dim=1)
 
 
 def metrics_from_counts(tp, fp, fn, tn):
-    """calculate_metrics' threshold metrics from confusion counts (the device epilogue, ops.threshold_confusion)."""
+    """calculate_metrics' threshold metrics from confusion counts (the device epilogue, evaluation.threshold_confusion)."""
     m = {"accuracy": (tp + tn) / max(tp + tn + fp + fn, 1),
          "precision": tp / (tp + fp) if tp + fp else 0,
          "recall": tp / (tp + fn) if tp + fn else 0,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Draw a Gear segmentation checkpoint's predictions (reference visualize.py), on the HIP path: workers decode and
-parse, ``gear_dataset.GearPreprocess`` makes images and masks on the GPU, label maps come from ``ops.seg_confidence``
-and every picture from one ``ops.render_seg_sheet`` launch (seg_visualize.py).
+parse, ``gear_dataset.GearPreprocess`` makes images and masks on the GPU, label maps come from ``sheets.seg_confidence``
+and every picture from one ``sheets.render_seg_sheet`` launch (seg_visualize.py).
 
     python -m tiaozhanbei_unet_amd.visualize_gear --checkpoint best_model.pth --data_root datasets/Gear [--split val]
 

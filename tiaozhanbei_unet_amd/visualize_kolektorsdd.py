@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Draw a KolektorSDD segmentation checkpoint's predictions (reference visualize_kolektorsdd.py), on the HIP path:
 workers only decode, ``kolektorsdd_dataset.GpuPreprocess`` makes images and masks on the GPU, label maps and the
-confidence map come from ``ops.seg_confidence`` and every picture from one ``ops.render_seg_sheet`` launch
+confidence map come from ``sheets.seg_confidence`` and every picture from one ``sheets.render_seg_sheet`` launch
 (seg_visualize.py).
 
     python -m tiaozhanbei_unet_amd.visualize_kolektorsdd --checkpoint best_model.pth --save_individual --save_grid
