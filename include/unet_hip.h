@@ -728,6 +728,23 @@ int32_t unet_synth_anomalies(const float* images, const float* masks_in, int32_t
                              const float* ytf, const int32_t* xcell, const float* xtf, const float* gradients,
                              float* corrupted, float* masks_out, void* stream);
 
+/* Smoothing of anomaly maps for the MVTec evaluation (test.py --map_sigma, --image_score map_max; no reference
+ * counterpart: src/test.py:66-133 ranks the raw map), one kernel per batch (csrc/smooth.hip, restated in float64 by
+ * tests/_smooth_ref.py).  src / dst: n contiguous fp32 planes of h x w, distinct and not overlapping.  dst = the separable
+ * correlation of src along W, then along H, with the symmetric kernel taps[|k|], k = -radius .. radius; the border is
+ * scipy's `reflect`, folded as often as needed (index i -> j = i mod 2L, then 2L - 1 - j if j >= L), so sides shorter
+ * than the radius work, down to 1 x 1.  fp32 accumulation: taps[0] * x[0], then fma(taps[k], x[-k] + x[+k], .) for k =
+ * 1 .. radius.  taps: HOST array of radius + 1 finite floats; they travel in the kernel arguments, so nothing is
+ * allocated, copied or synchronised and the call can be captured.  image_max (DEVICE, n floats, or NULL): overwritten
+ * (the caller initialises nothing) with the largest element written to each plane of dst, bit for bit; NaN if any
+ * element of the plane is NaN.  It is filled on the stream ahead of the kernel and raised by integer atomics on the
+ * float's own bits: the same result in every run.  Null src / dst / taps, a negative n, h, w or radius, a non-finite
+ * tap, src == dst or overlapping buffers: UNET_ERR_BAD_ARG; radius > UNET_SMOOTH_MAX_RADIUS or n * h * w > 2^31 - 1:
+ * UNET_ERR_UNSUPPORTED; all before anything is enqueued.  n == 0 or an empty plane: UNET_OK, nothing enqueued. */
+#define UNET_SMOOTH_MAX_RADIUS 32
+int32_t unet_smooth_maps(const float* src, float* dst, int64_t n, int32_t h, int32_t w, const float* taps,
+                         int32_t radius, float* image_max, void* stream);
+
 /* One fused step over a flat fp32 parameter arena: L2-coupled weight decay, bias correction,
  * gradient pre-scale (1/world_size under data parallelism). step is 1-based.  The betas are doubles so that 1 - beta is
  * formed in double before rounding to fp32, as torch.optim.Adam's `value=1 - beta2` is. */

@@ -128,6 +128,49 @@ class BinaryAUC:
         return res
 
 
+SMOOTH_MAX_RADIUS = 32          # UNET_SMOOTH_MAX_RADIUS of include/unet_hip.h
+
+
+class GaussianSmoother:
+    """Gaussian smoothing of anomaly maps and their per-image peak in one launch (unet_smooth_maps): what
+    scipy.ndimage.gaussian_filter(map, sigma, mode="reflect", truncate=truncate) computes plane by plane, in fp32.
+    radius = int(truncate * sigma + 0.5) (scipy's rule); the taps exp(-0.5 (k / sigma)^2), k = 0 .. radius, are normalised
+    over the full 2 radius + 1 window in float64 and then rounded to fp32 (``taps``; ``taps64`` keeps the float64 ones).
+    sigma == 0 is radius 0 with taps [1]: a bit-exact copy and the plain per-image maximum."""
+
+    def __init__(self, sigma, truncate=4.0):
+        import math
+        self.sigma, self.truncate = float(sigma), float(truncate)
+        for name, v in (("sigma", self.sigma), ("truncate", self.truncate)):
+            if not math.isfinite(v) or v < 0.0:
+                raise ValueError(f"GaussianSmoother: {name} {v} must be finite and >= 0")
+        limit = (SMOOTH_MAX_RADIUS + 0.5) / self.truncate if self.truncate > 0 else math.inf
+        if self.truncate * self.sigma + 0.5 >= SMOOTH_MAX_RADIUS + 1:
+            raise ValueError(f"GaussianSmoother: sigma {self.sigma} at truncate {self.truncate} needs a radius above "
+                             f"{SMOOTH_MAX_RADIUS}; the largest sigma that fits is below {limit:g}")
+        self.radius = int(self.truncate * self.sigma + 0.5)
+        import numpy as np
+        k = np.arange(self.radius + 1, dtype=np.float64)
+        g = np.exp(-0.5 * (k / self.sigma) ** 2) if self.radius > 0 else np.ones(1)
+        self.taps64 = g / (g[0] + 2.0 * g[1:].sum())
+        self.taps = self.taps64.astype(np.float32)
+        self._host = (C.c_float * (self.radius + 1))(*self.taps.tolist())
+
+    def __call__(self, maps):
+        """maps: CUDA tensor [N, H, W] or [N, 1, H, W] of any float dtype -> (smoothed fp32 of the same shape, image_max
+        [N] fp32).  Does not synchronise."""
+        _require_cuda(maps)
+        if not maps.is_floating_point() or maps.dim() not in (3, 4) or (maps.dim() == 4 and maps.shape[1] != 1):
+            raise ValueError(f"GaussianSmoother: float maps [N, H, W] or [N, 1, H, W], got {maps.dtype} {tuple(maps.shape)}")
+        x = maps.detach().contiguous().float()
+        n, h, w = x.shape[0], x.shape[-2], x.shape[-1]
+        out = torch.empty_like(x)
+        peak = torch.empty(n, dtype=torch.float32, device=x.device)
+        L.check(L.lib().unet_smooth_maps(_ptr(x), _ptr(out), n, h, w, self._host, self.radius, _ptr(peak), _stream()),
+                "unet_smooth_maps")
+        return out, peak
+
+
 def _image_planes(t, what):
     """[N, H, W] view of a [N, ..., H, W] tensor with one plane per image ([N, W]: one row)."""
     if t.dim() < 2:

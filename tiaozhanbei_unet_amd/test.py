@@ -5,6 +5,7 @@ runs on the GPU; thresholding and metrics are host numpy, as in the reference; t
 the GPU (sheets.render_sheet) and only encoded on the host."""
 import argparse
 import json
+import math
 import os
 
 import numpy as np
@@ -29,6 +30,9 @@ FLAGS = [  # reference src/test.py:26-61
     ("--pro_fpr_limit", dict(type=float, default=0.3)),     # build-only: the PRO curve is integrated up to this fpr
     ("--binary_masks", dict(action="store_true")),          # build-only: masks as (mask > 0) instead of k / 255
     ("--vis_overlay_alpha", dict(type=float, default=None)),    # build-only: adds an anomaly-map-over-image column
+    ("--map_sigma", dict(type=float, default=0.0)),         # build-only: Gaussian smoothing of the anomaly map (0: none)
+    ("--map_truncate", dict(type=float, default=4.0)),      # build-only: the Gaussian is cut at this many sigmas
+    ("--image_score", dict(type=str, default="reconstruction", choices=["reconstruction", "map_max"])),   # build-only
 ]
 VIS_GUTTER = 4              # white pixels between the panels of visualizations.png
 
@@ -42,13 +46,32 @@ def parse_args(argv=None):
         raise SystemExit(f"--pro_fpr_limit must be in (0, 1], got {args.pro_fpr_limit}")
     if args.vis_overlay_alpha is not None and not 0.0 <= args.vis_overlay_alpha <= 1.0:
         raise SystemExit(f"--vis_overlay_alpha must be in [0, 1], got {args.vis_overlay_alpha}")
+    for flag in ("map_sigma", "map_truncate"):
+        if not (math.isfinite(getattr(args, flag)) and getattr(args, flag) >= 0.0):
+            raise SystemExit(f"--{flag} must be finite and >= 0, got {getattr(args, flag)}")
+    try:
+        map_radius(args.map_sigma, args.map_truncate)
+    except ValueError as e:
+        raise SystemExit(f"--map_sigma {args.map_sigma} with --map_truncate {args.map_truncate}: {e}")
     return args
 
 
+def map_radius(map_sigma, map_truncate):
+    """Radius of the smoothing window (scipy's rule); ValueError when the kernel does not cover it."""
+    from .evaluation import GaussianSmoother
+    return GaussianSmoother(map_sigma, map_truncate).radius
+
+
 def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None, pro_fpr_limit=0.3,
-               binary_masks=False):
+               binary_masks=False, *, map_sigma=0.0, map_truncate=4.0, image_score="reconstruction"):
+    """With map_sigma > 0 the anomaly map is smoothed on the device (evaluation.GaussianSmoother) before anything reads
+    it; with image_score == "map_max" an image's score is the peak of that map (the raw one at sigma 0), from the same
+    launch, instead of its mean reconstruction error.  At the defaults nothing is launched."""
     from . import AnomalyUNet, evaluation
     from .utils import compute_anomaly_score, get_optimal_threshold
+    if image_score not in ("reconstruction", "map_max"):
+        raise ValueError(f"test_model: image_score {image_score!r}")
+    smoother = evaluation.GaussianSmoother(map_sigma, map_truncate) if map_sigma > 0 or image_score == "map_max" else None
     model.eval()
     out = {k: [] for k in ("images", "reconstructions", "anomaly_maps", "masks_true", "labels", "anomaly_types",
                            "image_paths", "anomaly_scores")}
@@ -63,12 +86,17 @@ def test_model(model, test_loader, device, threshold=None, pixel_thresholds=None
             else:
                 amap, recon = model(images, sigmoid=True), images      # sigmoid inside the head kernel
             masks = (batch["mask"] > 0).float() if binary_masks else batch["mask"]
+            if smoother is not None:
+                amap, peak = smoother(amap)
             if pixel_thresholds:          # pixel-level confusion counts of the anomalous images, on the device (:86-101)
                 bad = torch.as_tensor(np.asarray(batch["label"]) == 1)
                 pix = evaluation.threshold_confusion(amap, masks, pixel_thresholds, select=bad, counts=pix)
                 pix_auc.update(amap, masks, select=bad)
                 pix_pro.update(amap, masks)
-            out["anomaly_scores"].extend(compute_anomaly_score(recon, images).cpu().numpy())
+            if image_score == "map_max":
+                out["anomaly_scores"].extend(peak.cpu().numpy())
+            else:
+                out["anomaly_scores"].extend(compute_anomaly_score(recon, images).cpu().numpy())
             out["images"].extend(images.cpu()); out["reconstructions"].extend(recon.cpu())
             out["anomaly_maps"].extend(amap.cpu().numpy()); out["masks_true"].extend(masks.cpu().numpy())
             out["labels"].extend(np.asarray(batch["label"])); out["anomaly_types"].extend(batch["anomaly_type"])
@@ -175,7 +203,8 @@ def main(argv=None):
              else UNet(3, 1, args.bilinear, precision=args.precision)).to(device)
     load_checkpoint(model, None, args.checkpoint, device)
     results = test_model(model, loader, device, args.threshold, pixel_thresholds=args.pixel_thresholds,
-                         pro_fpr_limit=args.pro_fpr_limit, binary_masks=args.binary_masks)
+                         pro_fpr_limit=args.pro_fpr_limit, binary_masks=args.binary_masks, map_sigma=args.map_sigma,
+                         map_truncate=args.map_truncate, image_score=args.image_score)
     ev = evaluate_results(results, args.pixel_thresholds)
     print_metrics(ev["image_metrics"], "Image-level")
 
@@ -189,7 +218,12 @@ def main(argv=None):
         return o.tolist() if isinstance(o, np.ndarray) else o
 
     with open(os.path.join(out_dir, "test_metrics.json"), "w") as f:
-        json.dump({**plain(ev), "threshold": float(results["threshold"]), "args": vars(args)}, f, indent=2)
+        post = {}
+        if args.map_sigma > 0 or args.image_score != "reconstruction":          # build-only; absent at the defaults
+            post = {"postprocess": {"map_sigma": args.map_sigma, "map_truncate": args.map_truncate,
+                                    "radius": map_radius(args.map_sigma, args.map_truncate),
+                                    "image_score": args.image_score}}
+        json.dump({**plain(ev), "threshold": float(results["threshold"]), **post, "args": vars(args)}, f, indent=2)
     with open(os.path.join(out_dir, "detailed_results.json"), "w") as f:
         json.dump({"labels": results["labels"].tolist(), "predictions": results["predictions"].tolist(),
                    "anomaly_scores": results["image_scores"].tolist(), "anomaly_types": list(results["anomaly_types"]),
