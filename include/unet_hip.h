@@ -507,6 +507,31 @@ int32_t unet_match_class_regions(const uint8_t* truth, const int32_t* truth_regi
                                  int32_t* truth_records, int32_t* pred_records, int64_t capacity,
                                  int64_t* record_counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Per-defect records of class regions (no reference counterpart: what a predicted defect is on its own terms -- where,
+ * how large, how sure the model was -- for images that have no ground truth).  classes, region and sizes are what
+ * unet_label_class_regions takes and makes; conf: fp32 [n][h][w], the per-pixel confidence of unet_seg_confidence, or
+ * NULL.  Every region with size >= min_pixels (>= 1) yields one record of 12 int64 {image_base + image, class, root
+ * index y * w + x, size, x0, y0, x1, y1, sum_x, sum_y, conf_sum_q, conf_max_q}: the inclusive bounding box, the sums of
+ * the pixels' coordinates (centroid = sum / size), and the sum and the maximum over the region's pixels of
+ * q(v) = (uint32) rint(v * 65536.0f) (ties to even) on v clamped to [0, 1]; finite conf only; both 0 with conf == NULL.
+ * The slot comes from an atomic add on record_count[1] (int64, device; ADDED to: zero it first): the order is arbitrary,
+ * sort by (image, root index).  capacity = records that the buffer holds (<= 2^31 - 1); a record past it is counted and
+ * not written.  Two launches: the root pixels take their slots (one atomic per block), write their own pixel's values
+ * as the record and leave the slot in the workspace, then every other class pixel folds its values into its region's
+ * record with integer atomicMin / atomicMax / atomicAdd -- summed in registers, across the wave and across the block
+ * first where the pixels share a region, so a large region costs one atomic per field and block.  Integer atomics only:
+ * apart from the record order the output is a function of the inputs alone (that is why the confidence is summed in
+ * fixed point).  Any h, w >= 1; n < 65536,
+ * n h w <= 2^31 - 1, 2 <= num_classes <= 255, image_base + n and capacity <= 2^31 - 1, else UNET_ERR_UNSUPPORTED before
+ * any launch (and the workspace query returns 0); min_pixels < 1 is UNET_ERR_BAD_ARG.  Allocates nothing, does not
+ * synchronise. */
+size_t unet_describe_class_regions_workspace(int64_t n, int64_t h, int64_t w, int32_t num_classes);
+int32_t unet_describe_class_regions(const uint8_t* classes, const int32_t* region, const int32_t* sizes,
+                                    const float* conf /* [n][h][w], may be NULL */, int64_t n, int64_t h, int64_t w,
+                                    int32_t num_classes, int32_t min_pixels, int32_t image_base, int64_t* records,
+                                    int64_t capacity, int64_t* record_count, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+
 /* AUPRO: the area below the per-region-overlap curve up to a false-positive rate of fpr_limit, divided by fpr_limit (the
  * localisation metric of the MVTec AD evaluation; no reference counterpart).  With R regions and N ok pixels, walking
  * the distinct scores v downwards from the point (0, 0): fpr = #{ok pixels >= v} / N, pro = sum over the defective

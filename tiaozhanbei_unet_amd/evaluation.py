@@ -411,6 +411,60 @@ class ClassRegionMatcher:
         return res
 
 
+DEFECT_FIELDS = ("image", "class", "root", "size", "x0", "y0", "x1", "y1", "sum_x", "sum_y", "conf_sum_q", "conf_max_q")
+
+
+def describe_class_regions(labels, num_classes, conf=None, min_pixels=1, image_base=0):
+    """One record per class region of integer label maps [N, H, W] that has at least ``min_pixels`` pixels: an int64
+    [K, 12] numpy array of DEFECT_FIELDS, sorted by (image, root).  Regions are those of ``label_class_regions``;
+    ``image`` = image_base + the map's index, ``root`` = the smallest linear index y * W + x of the region, ``x0 .. y1``
+    its inclusive bounding box, ``sum_x`` / ``sum_y`` the sums of its pixels' coordinates.  ``conf``: float device tensor
+    [N, H, W] (the confidence of ``sheets.seg_confidence``), summed over the region as q(v) = rint(clamp(v, 0, 1) * 65536)
+    in ``conf_sum_q`` with its maximum in ``conf_max_q``; both 0 without it (unet_describe_class_regions; integers
+    throughout, so the array is a function of the inputs alone).  Two host reads: the region counts, which bound the
+    records from above and size the buffer, and the records with their count."""
+    import numpy as np
+    _require_cuda(labels)
+    c, min_pixels, image_base = int(num_classes), int(min_pixels), int(image_base)
+    lib = L.lib()
+    if labels.dim() == 3 and labels.numel():           # refused by its shape alone, before anything is converted
+        n, h, w = labels.shape
+        nbytes = lib.unet_describe_class_regions_workspace(n, h, w, c) if 0 <= c < 2 ** 31 else 0
+        if nbytes == 0 or image_base + n >= 2 ** 31:
+            raise _class_regions_error("describe_class_regions", n, h, w, num_classes)
+    t = _class_maps(labels, "describe_class_regions")
+    n, h, w = t.shape
+    if min_pixels < 1:
+        raise ValueError(f"describe_class_regions: min_pixels {min_pixels} is below 1")
+    if image_base < 0:
+        raise ValueError(f"describe_class_regions: image_base {image_base} is negative")
+    cf = None
+    if conf is not None:
+        if not torch.is_tensor(conf) or not conf.is_floating_point() or tuple(conf.shape) != (n, h, w):
+            raise ValueError(f"describe_class_regions: conf is a float tensor {(n, h, w)}, like the labels")
+        _require_cuda(conf)
+        if conf.device != t.device:
+            raise ValueError("describe_class_regions: labels and conf share one device")
+        cf = conf.detach().float().contiguous()
+    region, sizes, counts = label_class_regions(t, c)
+    cap = int(counts.sum())                            # every record is a region: there cannot be more
+    if cap == 0:
+        return np.zeros((0, len(DEFECT_FIELDS)), np.int64)
+    out = torch.empty(cap * len(DEFECT_FIELDS) + 1, dtype=torch.int64, device=t.device)
+    records, count = out[:-1], out[-1:]
+    count.zero_()
+    ws = _workspace(nbytes, t.device)
+    L.check(lib.unet_describe_class_regions(_ptr(t), _ptr(region), _ptr(sizes), _ptr(cf), n, h, w, c, min_pixels,
+                                            image_base, _ptr(records), cap, _ptr(count), _ptr(ws), ws.numel(), _stream()),
+            "unet_describe_class_regions")
+    host = out.cpu().numpy()
+    k = int(host[-1])
+    if k > cap:
+        raise RuntimeError("describe_class_regions: more records than regions")      # cannot happen
+    rec = host[:-1].reshape(cap, len(DEFECT_FIELDS))[:k]
+    return np.ascontiguousarray(rec[np.lexsort((rec[:, 2], rec[:, 0]))])
+
+
 def preprocess_u8(images_u8, flips=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """uint8 [N, H, W, 3] device batch -> normalised fp32 NCHW (ToTensor + Normalize, optional per-sample horizontal
     flip): /root/reference/src/dataset.py:134-146, src/kolektorsdd_dataset.py:133-150, on the GPU."""

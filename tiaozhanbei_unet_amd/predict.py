@@ -1,0 +1,221 @@
+#!/usr/bin/env python3
+"""Run a trained Gear or KolektorSDD segmentation checkpoint on images that have NO labels (no reference counterpart):
+which defects the model sees in each, where, how large and how sure it is, and whether the part would be rejected.
+
+    python -m tiaozhanbei_unet_amd.predict --task gear --checkpoint best_model.pth --input photos/ [--save_overlays]
+    python -m tiaozhanbei_unet_amd.predict --task kolektorsdd --checkpoint best_model.pth --input part.jpg
+
+``--input`` is one image or a directory, walked recursively in sorted order (jpg / jpeg / png / bmp; ``*_label.bmp`` is
+skipped).  Workers decode to RGB uint8; per batch ``augment.DeviceTransform`` resizes and normalises on the GPU (images
+of different sizes are grouped as the loaders' raw batches are), the model runs in eval mode, ``sheets.seg_confidence``
+gives the label map and the per-pixel confidence, and ``evaluation.describe_class_regions`` (csrc/defects.hip) one record
+per predicted 8-connected class region of at least ``--min_region_pixels`` pixels.  Writes into ``--output_dir``:
+
+``predictions.json``   ``args``, ``class_names``, ``frame_size`` [H, W], ``images`` (input order: ``image_path``, ``name``,
+                       ``original_size`` [H0, W0], ``mean_confidence`` of the whole frame, ``defect_pixels`` per class name
+                       over the listed defects, ``defects`` and ``decision``: defects.defect_entries) and ``summary``
+``masks/<name>.png``   the label map, Pillow mode P with the ``sheets.class_palette`` colours; ``--mask_size original``
+                       (default) upsamples it to the image's own size on the device (NEAREST), ``frame`` keeps the frame
+``overlays/<name>.png``  with ``--save_overlays``: image | image with the prediction overlaid, as ``visualize_gear`` draws it
+
+``<name>`` is the image's path relative to ``--input`` with the separators replaced by ``__``.  An image is rejected iff
+it has a defect of one of ``--reject_classes`` (default: every class but the background) whose mean confidence is at
+least ``--min_confidence``; defects below it stay listed with ``"counted": false``.  Nothing here claims any accuracy:
+the numbers are what the given checkpoint predicts.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+
+from . import defects
+
+TASKS = {"gear": {"image_size": (512, 512), "class_names": ["background", "pitting", "spalling", "scrape"],
+                  "palette": "index"},
+         "kolektorsdd": {"image_size": (1024, 512), "class_names": ["background", "defect_type_1", "defect_type_2"],
+                         "palette": "scaled"}}
+HEAD_WEIGHT = "outc.conv.weight"                         # [num_classes, 64, 1, 1] of UNet and SegmentationUNet
+
+FLAGS = [("--task", dict(type=str, required=True, choices=sorted(TASKS))),
+         ("--checkpoint", dict(type=str, required=True)),
+         ("--input", dict(type=str, required=True, help="an image file or a directory of images")),
+         ("--output_dir", dict(type=str, default="predictions")),
+         ("--image_size", dict(type=int, nargs=2, default=None, metavar=("H", "W"),
+                               help="the frame the model runs at; default: the task's trainer default")),
+         ("--model", dict(type=str, default="seg_unet", choices=["unet", "seg_unet"])),
+         ("--bilinear", dict(action="store_true")),
+         ("--dropout", dict(type=float, default=0.1)),
+         ("--precision", dict(type=str, default="fp32", choices=["fp32", "bf16"])),
+         ("--batch_size", dict(type=int, default=8)),
+         ("--num_workers", dict(type=int, default=4)),
+         ("--device", dict(type=str, default="auto")),
+         ("--num_classes", dict(type=int, default=None, help="default: the rows of the checkpoint's head weight")),
+         ("--class_names", dict(type=str, nargs="+", default=None)),
+         ("--min_region_pixels", dict(type=int, default=1)),
+         ("--min_confidence", dict(type=float, default=0.0)),
+         ("--reject_classes", dict(type=str, nargs="+", default=None, help="default: every class but the background")),
+         ("--mask_size", dict(type=str, default="original", choices=["original", "frame"])),
+         ("--save_overlays", dict(action="store_true"))]
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="Defects with boxes and confidence from unlabelled images (MI355X HIP path)")
+    for name, kw in FLAGS:
+        ap.add_argument(name, **kw)
+    args = ap.parse_args(argv)
+    if args.image_size is None:
+        args.image_size = list(TASKS[args.task]["image_size"])
+    if min(args.image_size) < 1:
+        ap.error("--image_size must be positive")
+    if args.min_region_pixels < 1:
+        ap.error("--min_region_pixels must be at least 1")
+    if not 0.0 <= args.min_confidence <= 1.0:
+        ap.error("--min_confidence must lie in 0..1")
+    if args.batch_size < 1:
+        ap.error("--batch_size must be at least 1")
+    return args
+
+
+class ImageFiles:
+    """A map-style dataset over image paths: (decoded RGB uint8 [H, W, 3] tensor, index)."""
+
+    def __init__(self, paths):
+        self.paths = list(paths)
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, idx):
+        import numpy as np
+        import torch
+        from PIL import Image
+        with Image.open(self.paths[idx]) as im:
+            return torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8)), idx
+
+
+def collate_images(samples):
+    """(images, indices): images stacked when they share a size, a list otherwise (gear_dataset.collate_raw's rule)."""
+    import torch
+    imgs, idx = zip(*samples)
+    same = len({tuple(t.shape) for t in imgs}) == 1
+    return (torch.stack(imgs) if same else list(imgs)), list(idx)
+
+
+def predict_batches(model, loader, size, num_classes, min_pixels, device):
+    """Eval-mode pass over ``collate_images`` batches.  Yields per batch (indices, original sizes [(H0, W0)], normalised
+    images, labels uint8 [N, H, W], frame mean confidence list, records with ``image`` = the dataset index).  The records
+    and the means are the batch's host reads."""
+    import numpy as np
+    import torch
+    from . import sheets
+    from .augment import DeviceTransform
+    from .evaluation import describe_class_regions
+    from .metrics import per_image_stats
+    tf = DeviceTransform(tuple(size), train=False)
+    model.eval()
+    with torch.no_grad():
+        for images, idx in loader:
+            sizes = [(int(t.shape[0]), int(t.shape[1])) for t in images]
+            x = tf(images, None, device=device)
+            logits = model(x)
+            labels, conf = sheets.seg_confidence(logits)
+            means = per_image_stats(logits)["conf_mean"]
+            records = describe_class_regions(labels, num_classes, conf, min_pixels)
+            records[:, 0] = np.asarray(idx, np.int64)[records[:, 0]]
+            yield idx, sizes, x, labels, means.tolist(), records
+
+
+def _save_mask(labels_u8, palette_bytes, path):
+    from PIL import Image
+    im = Image.fromarray(labels_u8)                    # mode L; the palette makes it P
+    im.putpalette(palette_bytes)
+    im.save(path)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from .train_gear import build_seg_model, require_gpu
+    device = require_gpu(args)
+    import torch
+    from torch.utils.data import DataLoader
+    from . import augment, sheets
+    from .seg_visualize import GUTTER, OVERLAY_ALPHA, save_png
+
+    task = TASKS[args.task]
+    paths = defects.list_images(args.input)
+    if not paths:
+        raise SystemExit(f"no image files below {args.input}")
+    names = defects.output_names(paths, args.input)
+    ckpt = torch.load(args.checkpoint, map_location=device, weights_only=True)
+    state = ckpt["model_state_dict"]
+    if args.num_classes is None:
+        if HEAD_WEIGHT not in state:
+            raise SystemExit(f"{args.checkpoint} has no {HEAD_WEIGHT}: pass --num_classes")
+        args.num_classes = int(state[HEAD_WEIGHT].shape[0])
+    num_classes = args.num_classes
+    if not 2 <= num_classes <= 8:
+        raise SystemExit(f"{num_classes} classes: the confidence kernel takes 2 to 8")
+    class_names = defects.class_names_for(task["class_names"], num_classes, args.class_names)
+    unknown = sorted(set(args.reject_classes or ()) - set(class_names))
+    if unknown:
+        raise SystemExit(f"--reject_classes {unknown}: the classes are {class_names}")
+    print("=" * 60 + f"\n{args.task.upper()} PREDICTION\n" + "=" * 60)
+    print(f"Device: {device}\nCheckpoint: {os.path.basename(args.checkpoint)}\nImages: {len(paths)}")
+    print(f"Number of classes: {num_classes}\nClass names: {class_names}")
+    model = build_seg_model(args, num_classes, device)
+    model.load_state_dict(state)
+
+    mask_dir = os.path.join(args.output_dir, "masks")
+    os.makedirs(mask_dir, exist_ok=True)
+    overlay_dir = os.path.join(args.output_dir, "overlays")
+    if args.save_overlays:
+        os.makedirs(overlay_dir, exist_ok=True)
+    host_palette = sheets.class_palette(num_classes, task["palette"])
+    palette, palette_bytes = host_palette.to(device), host_palette.numpy().tobytes()
+    loader = DataLoader(ImageFiles(paths), batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers,
+                        pin_memory=True, collate_fn=collate_images)
+    originals, frame_means, records = [None] * len(paths), [None] * len(paths), []
+    for idx, sizes, x, labels, means, rec in predict_batches(model, loader, args.image_size, num_classes,
+                                                             args.min_region_pixels, device):
+        records.append(rec)
+        if args.mask_size == "frame":
+            host = labels.cpu().numpy()
+        for k, i in enumerate(idx):
+            originals[i], frame_means[i] = sizes[k], means[k]
+            if args.mask_size == "frame":
+                mask = host[k]
+            else:
+                mask = augment.resize_nearest_u8(labels[k:k + 1].unsqueeze(-1), *sizes[k])[0, :, :, 0].cpu().numpy()
+            _save_mask(mask, palette_bytes, os.path.join(mask_dir, names[i] + ".png"))
+            if args.save_overlays:
+                sheet = sheets.render_seg_sheet(x[k:k + 1].float(), [("image",), ("overlay", labels[k:k + 1], OVERLAY_ALPHA)],
+                                                gutter=GUTTER, palette=palette)
+                save_png(sheet, os.path.join(overlay_dir, names[i] + ".png"))
+
+    import numpy as np
+    entries = defects.defect_entries(np.concatenate(records), class_names, args.image_size, originals,
+                                     args.min_confidence, args.reject_classes)
+    images = []
+    for i, e in enumerate(entries):
+        pixels = {name: 0 for name in class_names[1:]}
+        for d in e["defects"]:
+            pixels[d["class_name"]] += d["pixels"]
+        images.append({"image_path": paths[i], "name": names[i], "original_size": list(originals[i]),
+                       "mean_confidence": frame_means[i], "defect_pixels": pixels, **e})
+    summary = defects.summarize(entries, class_names)
+    out_path = os.path.join(args.output_dir, "predictions.json")
+    with open(out_path, "w") as f:
+        json.dump({"args": vars(args), "class_names": class_names, "frame_size": list(args.image_size), "images": images,
+                   "summary": summary}, f, indent=2)
+    for im in images:
+        found = ", ".join(f"{d['class_name']} {d['pixels']} px @ {d['mean_confidence']:.2f}" for d in im["defects"][:4])
+        more = f" (+{len(im['defects']) - 4} more)" if len(im["defects"]) > 4 else ""
+        print(f"{im['decision']:>6}  {im['name']}: {found or 'no defects'}{more}")
+    print(f"Images: {summary['images']}  rejected: {summary['rejected']}  defects: {summary['defects']}")
+    print(f"Predictions saved to: {out_path}")
+    return out_path
+
+
+if __name__ == "__main__":
+    main()
