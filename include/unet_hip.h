@@ -770,6 +770,36 @@ int32_t unet_synth_anomalies(const float* images, const float* masks_in, int32_t
 int32_t unet_smooth_maps(const float* src, float* dst, int64_t n, int32_t h, int32_t w, const float* taps,
                          int32_t radius, float* image_max, void* stream);
 
+/* Full-resolution prediction (predict_tiled; no reference counterpart: visualize.py and the evaluators squeeze every
+ * image into the trainer's frame): a frame of h x w is cut into ny x nx overlapping tiles of th x tw that the model runs
+ * at its trained size, tile t = i * nx + j at origin (oy[i], ox[j]), and the tile logits are blended back into one label
+ * map and one confidence map (csrc/tiles.hip, restated by tests/_tiles_ref.py).  oy[ny], ox[nx]: HOST arrays; they travel
+ * in the kernel arguments, so nothing is allocated, copied or synchronised and the calls can be captured.  Each axis must
+ * be a cover of the frame: the first origin 0, the last frame - tile, strictly increasing, no gap larger than the tile;
+ * anything else is UNET_ERR_BAD_ARG, as is a NULL pointer, so no table can send a kernel outside the frame or the tile
+ * buffer.  Both: 1 <= ny, nx <= 64, 1 <= th <= h, 1 <= tw <= w, h w <= 2^31 - 1, else UNET_ERR_UNSUPPORTED; every
+ * refusal is decided on the host before any launch.  One launch each, no atomics, no workspace; a lane owns 4 consecutive
+ * x (16-byte loads and stores) when w, tw and every ox[j] are multiples of 4 and the pointers are 16-byte aligned (labels:
+ * 4), else one pixel.  Allocates nothing, does not synchronise.
+ *
+ * unet_tile_gather: frame fp32 [c][h][w] -> tiles fp32 [ny nx][c][th][tw], tiles[t][ch][ky][kx] = frame[ch][oy[i] + ky]
+ * [ox[j] + kx], bit for bit; any c >= 1.
+ *
+ * unet_tile_blend: tiles = fp32 logits [ny nx][c][th][tw], 2 <= c <= 8 (the limits of unet_seg_confidence), ramps
+ * 1 <= ramp_y, ramp_x <= 256.  Along an axis of tile length L with ramp B the weight of tile offset k is the integer
+ * q(k) = min(k + 1, L - k, B); a tile weighs q_y q_x at a pixel.  Per pixel, over the covering tiles in ascending i, then
+ * ascending j: wsum += q_y q_x in int32 and acc_c = acc_c + (float)(q_y q_x) * z_c from acc_c = 0, the product and the
+ * sum each one fp32 rounding; blended[c][h][w] (fp32, may be NULL) = acc_c / (float)wsum, one conversion and one
+ * correctly rounded division.  A pixel under exactly ONE tile takes that tile's logits unchanged, so a single tile over
+ * the frame gives the bytes of unet_seg_confidence.  labels[h][w] (uint8) and conf[h][w] (fp32) follow from the blended
+ * logits by unet_seg_confidence's rule: the first maximum wins, conf = 1 / sum_j expf(z_j - max z) in class order.  labels
+ * or conf may be NULL (not both).  The outputs are a function of the inputs alone.  The contract covers finite logits. */
+int32_t unet_tile_gather(const float* frame, int32_t c, int32_t h, int32_t w, int32_t th, int32_t tw, const int32_t* oy,
+                         int32_t ny, const int32_t* ox, int32_t nx, float* tiles, void* stream);
+int32_t unet_tile_blend(const float* tiles, int32_t c, int32_t th, int32_t tw, const int32_t* oy, int32_t ny,
+                        const int32_t* ox, int32_t nx, int32_t h, int32_t w, int32_t ramp_y, int32_t ramp_x,
+                        uint8_t* labels, float* conf, float* blended, void* stream);
+
 /* One fused step over a flat fp32 parameter arena: L2-coupled weight decay, bias correction,
  * gradient pre-scale (1/world_size under data parallelism). step is 1-based.  The betas are doubles so that 1 - beta is
  * formed in double before rounding to fp32, as torch.optim.Adam's `value=1 - beta2` is. */

@@ -169,6 +169,8 @@ SIGNATURES = {
     "unet_color_jitter_normalize_u8": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
     "unet_synth_anomalies": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "unet_smooth_maps": (_i, [_p, _p, _l, _i, _i, _p, _i, _p, _p]),
+    "unet_tile_gather": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p]),
+    "unet_tile_blend": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "unet_adam_chunk_elems": (_i, []),
     "unet_adam_multi": (_i, [_p, _p, _i, _f, _d, _d, _f, _f, _f, _i, _i, _p]),
     "unet_adam_step": (_i, [_p, _p, _p, _p, _l, _f, _d, _d, _f, _f, _f, _i, _p]),
