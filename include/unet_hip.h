@@ -800,6 +800,36 @@ int32_t unet_tile_blend(const float* tiles, int32_t c, int32_t th, int32_t tw, c
                         const int32_t* ox, int32_t nx, int32_t h, int32_t w, int32_t ramp_y, int32_t ramp_x,
                         uint8_t* labels, float* conf, float* blended, void* stream);
 
+/* Affine crops of a ragged batch (train_gear_crops; no reference counterpart: the reference trains on squeezed frames):
+ * n_crops crops of out_h x out_w, cut with scale, rotation and flip out of n_images images of DIFFERENT sizes, in one
+ * launch (csrc/crops.hip, restated in numpy int64 by tests/_crops_ref.py).  src: one packed byte buffer of src_bytes
+ * bytes; image i is [h][w][c] bytes at src + src_offset[i] with (h, w) = src_hw[i] ([n_images][2]); c is 1 or 3.
+ * desc[k]: the image of crop k and its matrix {a0 .. a5} in 16.16 fixed point, a2 / a5 ALREADY holding the half-pixel
+ * terms (the convention of the flip / rotate kernel above).  dst: [n_crops][out_h][out_w][c].  src, src_offset, src_hw,
+ * desc and dst are DEVICE arrays.  mode 0 = nearest, 1 = bilinear; fill in 0..255.
+ * Output pixel (y, x) of crop k, all in int64: u = a0 x + a1 y + a2, v = a3 x + a4 y + a5; nx = u >> 16, ny = v >> 16
+ * (arithmetic shift: floor).  The pixel is inside iff 0 <= nx < w and 0 <= ny < h, in BOTH modes; outside every channel
+ * is `fill`, so a mask cropped with the same matrix carries its ignore value exactly where the image carries fill.
+ * Nearest: dst = src[ny][nx][ch].  Bilinear: ub = u - 32768, x0 = ub >> 16, fx = (ub & 0xFFFF) >> 8, x1 = x0 + 1, x0 and
+ * x1 clamped to [0, w - 1]; the same along y; top = (256 - fx) p00 + fx p01, bot likewise from p10 and p11; dst =
+ * ((256 - fy) top + fy bot + 32768) >> 16.  No floating point: the bytes are a function of the inputs alone, and a matrix
+ * that maps pixel centres to pixel centres (unit scale, no rotation, flipped or not) copies bytes in both modes.
+ * Whatever the device tables hold, the kernel stays inside src[0, src_bytes) and dst: a crop whose image is outside
+ * 0..n_images-1, or whose image has src_offset < 0, a side <= 0 or src_offset + h w c > src_bytes, is written as all
+ * `fill`, and every tap is clamped into its image.
+ * Refused on the host before any launch: a NULL pointer (UNET_ERR_BAD_ARG); c not 1 or 3, mode not 0 or 1, fill outside
+ * 0..255, out_h or out_w outside 1..4096, n_crops or n_images outside 1..65535, src_bytes <= 0 (UNET_ERR_UNSUPPORTED).
+ * A lane stores one dword when out_w c is a multiple of 4 and dst is 4-byte aligned, else one byte.  Allocates nothing,
+ * does not synchronise. */
+typedef struct unet_crop_desc {
+  int32_t image;
+  int32_t a[6];
+  int32_t reserved;
+} unet_crop_desc;
+int32_t unet_affine_crop_u8(const uint8_t* src, int64_t src_bytes, const int64_t* src_offset, const int32_t* src_hw,
+                            int32_t n_images, int32_t c, const unet_crop_desc* desc, int32_t n_crops, int32_t out_h,
+                            int32_t out_w, int32_t mode, int32_t fill, uint8_t* dst, void* stream);
+
 /* One fused step over a flat fp32 parameter arena: L2-coupled weight decay, bias correction,
  * gradient pre-scale (1/world_size under data parallelism). step is 1-based.  The betas are doubles so that 1 - beta is
  * formed in double before rounding to fp32, as torch.optim.Adam's `value=1 - beta2` is. */

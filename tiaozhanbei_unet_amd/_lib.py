@@ -55,6 +55,14 @@ class SegPanel(C.Structure):
 
 
 SEG_PANEL_IMAGE, SEG_PANEL_CLASSES, SEG_PANEL_OVERLAY, SEG_PANEL_LUT = range(4)
+
+
+class CropDesc(C.Structure):
+    """struct unet_crop_desc"""
+    _fields_ = [("image", C.c_int32), ("a", C.c_int32 * 6), ("reserved", C.c_int32)]
+
+
+CROP_NEAREST, CROP_BILINEAR = 0, 1
 _i, _l, _f, _p, _z, _d = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes): every symbol include/unet_hip.h declares
@@ -171,6 +179,7 @@ SIGNATURES = {
     "unet_smooth_maps": (_i, [_p, _p, _l, _i, _i, _p, _i, _p, _p]),
     "unet_tile_gather": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p]),
     "unet_tile_blend": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "unet_affine_crop_u8": (_i, [_p, _l, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
     "unet_adam_chunk_elems": (_i, []),
     "unet_adam_multi": (_i, [_p, _p, _i, _f, _d, _d, _f, _f, _f, _i, _i, _p]),
     "unet_adam_step": (_i, [_p, _p, _p, _p, _l, _f, _d, _d, _f, _f, _f, _i, _p]),

@@ -66,13 +66,15 @@ def _seg_batches(loader, preprocess, device):
         yield preprocess(images, polys, sizes, device=device)
 
 
-def train_seg_epoch(model, dataloader, criterion, optimizer, device, epoch, num_classes, preprocess, *, batches=None):
+def train_seg_epoch(model, dataloader, criterion, optimizer, device, epoch, num_classes, preprocess, *, batches=None,
+                    ignore_index=None):
     """One training epoch (reference train.py:118-160): the loss is the UNWEIGHTED mean of the per-batch losses, the
     metrics those of a ``SegmentationMetrics`` updated with every batch.  Losses are summed on the device and read once.
-    ``batches``: an iterable of (images, masks) device batches to use instead of ``dataloader`` + ``preprocess``."""
+    ``batches``: an iterable of (images, masks) device batches to use instead of ``dataloader`` + ``preprocess``.
+    ``ignore_index``: a mask value the metrics leave out (None: none, as the reference)."""
     from .metrics import SegmentationMetrics
     model.train()
-    metrics = SegmentationMetrics(num_classes)
+    metrics = SegmentationMetrics(num_classes, ignore_index=ignore_index)
     total = torch.zeros((), dtype=torch.float64, device=device)
     n_batches = 0
     for images, masks in _seg_batches(dataloader, preprocess, device) if batches is None else batches:
@@ -139,10 +141,12 @@ def build_seg_model(args, num_classes, device):
 
 
 def fit_segmentation(args, exp_dir, dirs, model, train_loader, val_loader, num_classes, device, train_batches,
-                     val_batches):
+                     val_batches, *, ignore_index=None, validate=None):
     """The epoch loop, checkpoints and ``training_results.json`` shared by the Gear and KolektorSDD trainers (reference
     train.py:333-400, train_kolektorsdd.py:370-452).  ``train_batches`` / ``val_batches``: loader -> iterable of
-    (images, masks) device batches."""
+    (images, masks) device batches.  ``ignore_index``: a mask value the loss and the training metrics leave out (None:
+    none).  ``validate``: ``(model, criterion) -> {"loss", "metrics"}`` to use instead of ``validate_seg_epoch`` over
+    ``val_batches`` (which may then be None)."""
     from .metrics import CombinedSegmentationLoss
     from .train_utils import get_optimizer
     from .utils import load_checkpoint, save_checkpoint
@@ -151,7 +155,8 @@ def fit_segmentation(args, exp_dir, dirs, model, train_loader, val_loader, num_c
     print(f"Total parameters: {total_params:,}")
     class_weights = [float(w) for w in args.class_weights.split(",")] if args.class_weights else None
     criterion = CombinedSegmentationLoss(ce_weight=args.ce_weight, dice_weight=args.dice_weight,
-                                         focal_weight=args.focal_weight, class_weights=class_weights)
+                                         focal_weight=args.focal_weight, ignore_index=ignore_index,
+                                         class_weights=class_weights)
     optimizer = get_optimizer(model, args.optimizer, args.learning_rate, args.weight_decay)
     start_epoch = 0
     if args.resume:
@@ -162,13 +167,16 @@ def fit_segmentation(args, exp_dir, dirs, model, train_loader, val_loader, num_c
     for epoch in range(start_epoch, args.epochs):
         t0 = time.time()
         tr = train_seg_epoch(model, train_loader, criterion, optimizer, device, epoch, num_classes, None,
-                             batches=train_batches(train_loader))
+                             batches=train_batches(train_loader), ignore_index=ignore_index)
         train_seconds = time.time() - t0
         train_losses.append(tr["loss"])
         vr = None
         if epoch % args.val_freq == 0 or epoch == args.epochs - 1:
-            vr = validate_seg_epoch(model, val_loader, criterion, device, num_classes, None,
-                                    batches=val_batches(val_loader))
+            if validate is not None:
+                vr = validate(model, criterion)
+            else:
+                vr = validate_seg_epoch(model, val_loader, criterion, device, num_classes, None,
+                                        batches=val_batches(val_loader))
             val_losses.append(vr["loss"])
             if vr["metrics"]["mean_iou"] > best_val_miou:
                 best_val_miou = float(vr["metrics"]["mean_iou"])
