@@ -507,6 +507,34 @@ int32_t unet_match_class_regions(const uint8_t* truth, const int32_t* truth_regi
                                  int32_t* truth_records, int32_t* pred_records, int64_t capacity,
                                  int64_t* record_counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Overlaps of region pairs (no reference counterpart: the sparse contingency table between two region labellings, from
+ * which detection against a confidence threshold, "found with the wrong class" and IoU matching are host arithmetic).
+ * truth_region / pred_region: two `region` arrays of unet_label_class_regions, int32 [n][h][w], 1 + root index, 0 on
+ * background.  A pixel carries the pair (truth id, pred id) iff both are positive, whatever the regions' classes.  The
+ * ids are compared and packed, never used as an index.
+ * unet_region_pair_bound: bound[n] (int64, device; ADDED to: zero it first) += the pixels of image n that carry a pair
+ * and have x == 0 or another pair (or none) to their left.  The row-major first pixel of every distinct pair is one of
+ * them, so bound[n] >= the distinct pairs of image n.
+ * unet_region_pairs: one record of 4 int32 {image_base + image, truth id - 1, pred id - 1, overlap} per distinct pair of
+ * every image, overlap = the pixels that carry it, at the slot that an atomic add on count[1] (int64, device; ADDED to:
+ * zero it first) hands out: the order is arbitrary, sort by (image, truth root, pred root).  record_cap = records that
+ * the buffer holds; a record past it is counted and not written.  The pairs of an image are counted in an
+ * open-addressing table of `capacity` slots (a power of two, else UNET_ERR_BAD_ARG) in the workspace (8-byte aligned),
+ * which the call clears: key = truth id << 32 | pred id (0 = empty), atomicCAS on the key, integer atomicAdd on the
+ * slot's count, linear probing for at most `capacity` steps.  A pixel that finds no slot is dropped and adds 1 to
+ * overflow[1] (int64, device; ADDED to: zero it first): with overflow == 0 and count <= record_cap the records are
+ * complete, which capacity >= bound[n] for every n and record_cap >= their sum guarantee; the pairs that did find a
+ * slot have their full overlap either way.  Integer atomics only: the set of records is a function of the two maps alone.
+ * Any h, w >= 1; n < 65536, n h w <= 2^31 - 1, capacity <= 2^30, n capacity <= 2^40, image_base + n and record_cap
+ * <= 2^31 - 1, else UNET_ERR_UNSUPPORTED before any launch (and the workspace query returns 0, as for a capacity that is
+ * no power of two).  Allocate nothing, do not synchronise. */
+int32_t unet_region_pair_bound(const int32_t* truth_region, const int32_t* pred_region, int64_t n, int64_t h, int64_t w,
+                               int64_t* bound /* [n] */, void* stream);
+size_t unet_region_pairs_workspace(int64_t n, int64_t capacity);
+int32_t unet_region_pairs(const int32_t* truth_region, const int32_t* pred_region, int64_t n, int64_t h, int64_t w,
+                          int64_t capacity, int32_t image_base, int32_t* records, int64_t record_cap, int64_t* count,
+                          int64_t* overflow, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-defect records of class regions (no reference counterpart: what a predicted defect is on its own terms -- where,
  * how large, how sure the model was -- for images that have no ground truth).  classes, region and sizes are what
  * unet_label_class_regions takes and makes; conf: fp32 [n][h][w], the per-pixel confidence of unet_seg_confidence, or

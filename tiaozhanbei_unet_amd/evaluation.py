@@ -450,19 +450,177 @@ def describe_class_regions(labels, num_classes, conf=None, min_pixels=1, image_b
     cap = int(counts.sum())                            # every record is a region: there cannot be more
     if cap == 0:
         return np.zeros((0, len(DEFECT_FIELDS)), np.int64)
+    out = _describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap)
+    return _defect_records(out.cpu().numpy(), cap, "describe_class_regions")
+
+
+def _describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap):
+    """unet_describe_class_regions on maps that are labelled already: the DEVICE int64 buffer of ``cap`` records of
+    DEFECT_FIELDS followed by their count."""
+    n, h, w = t.shape
+    lib = L.lib()
     out = torch.empty(cap * len(DEFECT_FIELDS) + 1, dtype=torch.int64, device=t.device)
     records, count = out[:-1], out[-1:]
     count.zero_()
-    ws = _workspace(nbytes, t.device)
+    ws = _workspace(lib.unet_describe_class_regions_workspace(n, h, w, c), t.device)
     L.check(lib.unet_describe_class_regions(_ptr(t), _ptr(region), _ptr(sizes), _ptr(cf), n, h, w, c, min_pixels,
                                             image_base, _ptr(records), cap, _ptr(count), _ptr(ws), ws.numel(), _stream()),
             "unet_describe_class_regions")
-    host = out.cpu().numpy()
+    return out
+
+
+def _defect_records(host, cap, what):
+    """the sorted records of ``_describe_labelled``'s buffer, read to the host"""
+    import numpy as np
     k = int(host[-1])
     if k > cap:
-        raise RuntimeError("describe_class_regions: more records than regions")      # cannot happen
+        raise RuntimeError(f"{what}: more records than regions")      # cannot happen
     rec = host[:-1].reshape(cap, len(DEFECT_FIELDS))[:k]
     return np.ascontiguousarray(rec[np.lexsort((rec[:, 2], rec[:, 0]))])
+
+
+PAIR_FIELDS = ("image", "truth_root", "pred_root", "overlap")
+
+
+def _pairs_on_device(truth_region, pred_region, image_base, what):
+    """(DEVICE int32 buffer of ``record_cap`` records of PAIR_FIELDS followed by the int64 count and overflow, record_cap)
+    of two region maps; (None, 0) where no pixel carries a pair.  One host read: the bound."""
+    _require_cuda(truth_region, pred_region)
+    for r in (truth_region, pred_region):
+        if r.dtype != torch.int32 or r.dim() != 3 or r.numel() == 0:
+            raise ValueError(f"{what}: int32 [N, H, W] region maps of label_class_regions, got {r.dtype} {tuple(r.shape)}")
+    if truth_region.shape != pred_region.shape or truth_region.device != pred_region.device:
+        raise ValueError(f"{what}: the two region maps differ in shape or device")
+    image_base = int(image_base)
+    if image_base < 0:
+        raise ValueError(f"{what}: image_base {image_base} is negative")
+    tr, pr = truth_region.detach().contiguous(), pred_region.detach().contiguous()
+    n, h, w = tr.shape
+    if n >= 65536 or n * h * w >= 2 ** 31 or image_base + n >= 2 ** 31:
+        raise RuntimeError(f"{what}: {n} x {h} x {w} maps are not supported (n < 65536, at most 2^31 - 1 pixels, image "
+                           "indices below 2^31)")
+    lib = L.lib()
+    bound = torch.zeros(n, dtype=torch.int64, device=tr.device)
+    L.check(lib.unet_region_pair_bound(_ptr(tr), _ptr(pr), n, h, w, _ptr(bound), _stream()), "unet_region_pair_bound")
+    per_image = bound.tolist()                         # >= the distinct pairs of every image
+    record_cap = sum(per_image)
+    if record_cap == 0:
+        return None, 0
+    capacity = 1 << (2 * max(per_image) - 1).bit_length()      # the next power of two: a load factor of at most 1 / 2
+    nbytes = lib.unet_region_pairs_workspace(n, capacity)
+    if nbytes == 0:
+        raise RuntimeError(f"{what}: {n} tables of {capacity} slots are not supported")
+    f = len(PAIR_FIELDS)
+    out = torch.empty(record_cap * f + 4, dtype=torch.int32, device=tr.device)      # 16 bytes a record: the tail is aligned
+    tail = out[record_cap * f:].view(torch.int64)      # {count, overflow}
+    tail.zero_()
+    ws = _workspace(nbytes, tr.device)
+    L.check(lib.unet_region_pairs(_ptr(tr), _ptr(pr), n, h, w, capacity, image_base, _ptr(out), record_cap, _ptr(tail),
+                                  _ptr(tail[1:]), _ptr(ws), ws.numel(), _stream()), "unet_region_pairs")
+    return out, record_cap
+
+
+def _pair_records(host, record_cap, what):
+    """the sorted int64 records of ``_pairs_on_device``'s buffer, read to the host"""
+    import numpy as np
+    f = len(PAIR_FIELDS)
+    count, overflow = (int(v) for v in host[record_cap * f:].view(np.int64))
+    if overflow != 0 or count > record_cap:
+        raise RuntimeError(f"{what}: {overflow} pixels found no slot, {count} records for {record_cap}")     # cannot happen
+    rec = host[:count * f].reshape(count, f).astype(np.int64)
+    return np.ascontiguousarray(rec[np.lexsort((rec[:, 2], rec[:, 1], rec[:, 0]))])
+
+
+def pair_class_regions(truth_region, pred_region, image_base=0):
+    """The overlaps of two region labellings: one record of PAIR_FIELDS per pair of a region of ``truth_region`` and a
+    region of ``pred_region`` (int32 [N, H, W] DEVICE ``region`` maps of ``label_class_regions``: 1 + root index, 0 on
+    background) of the same image that share a pixel, whatever their classes; ``overlap`` = the shared pixels, ``image``
+    = image_base + the map's index.  An int64 [K, 4] numpy array sorted by (image, truth_root, pred_root)
+    (csrc/regionpairs.hip; integers throughout, so the array is a function of the two maps alone).  Two host reads: the
+    bound on the pairs per image, which sizes the hash tables (the next power of two >= twice the largest) and the
+    record buffer, and the records with their count."""
+    import numpy as np
+    out, record_cap = _pairs_on_device(truth_region, pred_region, image_base, "pair_class_regions")
+    if out is None:
+        return np.zeros((0, len(PAIR_FIELDS)), np.int64)
+    return _pair_records(out.cpu().numpy(), record_cap, "pair_class_regions")
+
+
+class DetectionMatcher:
+    """Region records for detection curves over confidence, accumulated over batches: every truth region, every kept
+    predicted region (at least ``min_pixels`` pixels) with its summed confidence, and the overlap of every pair of them
+    that shares a pixel.  ``seg_detection`` turns the three record sets into recall / precision / false alarms as a
+    function of the confidence a predicted region must reach, which ``ClassRegionMatcher``'s one ``hit`` per region
+    cannot give.
+
+    ``update`` labels truth and prediction in one call (``label_class_regions``), describes each half with that
+    labelling (unet_describe_class_regions: truth without confidence and with every region, the prediction with ``conf``
+    and ``min_pixels``) and pairs the two ``region`` halves (``pair_class_regions``' kernels).  Every update may have
+    another (H, W).  It reads the region counts, the pair bound and the records back, so it SYNCHRONISES per update: that
+    is acceptable for an evaluation pass, and it keeps nothing on the device."""
+
+    def __init__(self, num_classes, min_pixels=1):
+        self.num_classes, self.min_pixels = int(num_classes), int(min_pixels)
+        if not 2 <= self.num_classes <= 255:
+            raise ValueError(f"DetectionMatcher: {num_classes} classes, 2..255 are supported")
+        if self.min_pixels < 1:
+            raise ValueError(f"DetectionMatcher: min_pixels {min_pixels} is below 1")
+        self.images = 0
+        self.image_sizes = []
+        self._truth, self._pred, self._pairs = [], [], []
+
+    def update(self, pred_labels, conf, truth):
+        """pred_labels / truth: integer device label maps of equal shape [N, H, W] (values outside 0..254 become 255);
+        conf: float device tensor [N, H, W], the confidence of ``sheets.seg_confidence`` or of ``tiling.blend_tiles``."""
+        import numpy as np
+        what = "DetectionMatcher.update"
+        p = _class_maps(pred_labels, what)
+        t = _class_maps(truth.to(p.device), what)
+        if p.shape != t.shape:
+            raise ValueError(f"{what}: prediction / truth shapes differ")
+        n, h, w = p.shape
+        if not torch.is_tensor(conf) or not conf.is_floating_point() or tuple(conf.shape) != (n, h, w):
+            raise ValueError(f"{what}: conf is a float tensor {(n, h, w)}, like the labels")
+        _require_cuda(conf)
+        if conf.device != p.device:
+            raise ValueError(f"{what}: labels and conf share one device")
+        cf = conf.detach().float().contiguous()
+        c, base = self.num_classes, self.images
+        if L.lib().unet_describe_class_regions_workspace(n, h, w, c) == 0 or base + n >= 2 ** 31:
+            raise _class_regions_error(what, n, h, w, c)
+        region, sizes, counts = label_class_regions(torch.cat([t, p]), c)      # one pass labels both
+        cap_t, cap_p = counts.reshape(2, -1).sum(1).tolist()
+        halves = []
+        for maps, reg, siz, cfd, mp, cap in ((t, region[:n], sizes[:n], None, 1, cap_t),
+                                             (p, region[n:], sizes[n:], cf, self.min_pixels, cap_p)):
+            halves.append(_describe_labelled(maps, reg, siz, cfd, c, mp, base, cap) if cap else None)
+        pairs, record_cap = _pairs_on_device(region[:n], region[n:], base, what)
+        empty = np.zeros((0, len(DEFECT_FIELDS)), np.int64)
+        trec, prec = (_defect_records(o.cpu().numpy(), cap, what) if o is not None else empty
+                      for o, cap in zip(halves, (cap_t, cap_p)))
+        prs = np.zeros((0, len(PAIR_FIELDS)), np.int64)
+        if pairs is not None:
+            prs = _pair_records(pairs.cpu().numpy(), record_cap, what)
+            kept = (prec[:, 0] - base) * (h * w) + prec[:, 2]                   # the kept predicted regions of this update
+            prs = prs[np.isin((prs[:, 0] - base) * (h * w) + prs[:, 2], kept)]
+        self._truth.append(trec)
+        self._pred.append(prec)
+        self._pairs.append(prs)
+        self.image_sizes.extend([(h, w)] * n)
+        self.images += n
+
+    def compute(self):
+        """{"truth": int64 [Kt, 12], "pred": int64 [Kp, 12]} numpy records of DEFECT_FIELDS sorted by (image, root) (truth
+        with conf_sum_q = conf_max_q = 0), "pairs": int64 [K, 4] of PAIR_FIELDS sorted by (image, truth_root, pred_root),
+        without the pairs of predicted regions below ``min_pixels``, "image_sizes": [(H, W)] per image, "images".  The
+        image index counts over all updates; a root index is y * W + x in its own image's width."""
+        import numpy as np
+
+        def cat(parts, fields):
+            return np.concatenate(parts) if parts else np.zeros((0, len(fields)), np.int64)
+
+        return {"truth": cat(self._truth, DEFECT_FIELDS), "pred": cat(self._pred, DEFECT_FIELDS),
+                "pairs": cat(self._pairs, PAIR_FIELDS), "image_sizes": list(self.image_sizes), "images": self.images}
 
 
 def preprocess_u8(images_u8, flips=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
