@@ -560,6 +560,40 @@ int32_t unet_describe_class_regions(const uint8_t* classes, const int32_t* regio
                                     int64_t capacity, int64_t* record_count, void* workspace, size_t workspace_bytes,
                                     void* stream);
 
+/* Outline accuracy of label maps (no reference counterpart): an exact squared Euclidean distance transform of the class
+ * boundaries, and one record per (image, class) of how far the outlines of two maps lie apart (csrc/distance.hip).
+ * classes / truth / pred: uint8 [n][h][w] as unet_label_class_regions takes them; a pixel has class c iff its value is c,
+ * 1 <= c < num_classes.  A pixel of class c is a boundary pixel of c iff at least one of its 4-neighbours INSIDE the frame
+ * has another value: the frame edge makes no boundary, so a class that covers the frame or is absent has none.
+ * unet_boundary_distance_sq: d2_out (int32 [n][num_classes - 1][h][w]) = the minimum of (y - y')^2 + (x - x')^2 over the
+ * boundary pixels (y', x') of class c of image n at [n][c - 1][y][x], UNET_BOUNDARY_NONE everywhere in a plane whose image
+ * has no boundary pixel of the class.  Two launches: columns (vertical distance, all classes from one read of the labels),
+ * then rows in place (a workgroup per row, the row in LDS, an outward search that stops once dx^2 reaches the best
+ * value).  The workspace (4-byte aligned) holds one flag per (image, class); the call clears it.
+ * unet_boundary_stats: records (int64 [n][num_classes - 1][UNET_BOUNDARY_FIELDS], ADDED to: zero them first) = {image_base
+ * + image, class, t_pixels, p_pixels, t_boundary, p_boundary, p_near[4], t_near[4], band_inter, band_union, p_dist_sum_q8,
+ * t_dist_sum_q8, p_dist_max_sq, t_dist_max_sq}: pixels and boundary pixels of the class in truth and prediction;
+ * p_near[i] = predicted boundary pixels with d2_truth <= tol_sq[i] and t_near[i] = truth boundary pixels with d2_pred <=
+ * tol_sq[i] (tol_sq: HOST array of k <= 4 values, the slots from k on stay 0); band_inter / band_union = intersection and
+ * union of {truth pixels of the class with d2_truth <= band_sq} and {predicted pixels of the class with d2_pred <=
+ * band_sq}; the sums over a map's boundary pixels of dist_q8 = floor(256 sqrt(d2)) (exact: isqrt(d2 << 16)) of the OTHER
+ * map's d2, and the maxima of that d2.  A boundary pixel whose other map has no boundary of the class (d2 ==
+ * UNET_BOUNDARY_NONE) adds to t_boundary / p_boundary only.  hist (int64 [num_classes - 1][2][1025], ADDED to): direction
+ * 0 = prediction to truth, 1 = truth to prediction, bin min(isqrt(d2), 1024), from the boundary pixels that feed the
+ * sums.  d2_truth / d2_pred: what unet_boundary_distance_sq made of truth / pred.  Integer atomics only (per block in LDS,
+ * then 64-bit atomicAdd / atomicMax): the outputs are a function of the two maps alone.
+ * Both: 1 <= h, w <= 4096, 2 <= num_classes <= 32, n < 65536, n (num_classes - 1) h w < 2^31 (and image_base + n <=
+ * 2^31 - 1), else UNET_ERR_UNSUPPORTED before any launch (and the workspace query returns 0); k outside 0..4 or a tol_sq /
+ * band_sq outside 0 .. 2^30 - 1 is UNET_ERR_BAD_ARG.  Allocate nothing, do not synchronise. */
+#define UNET_BOUNDARY_NONE (1 << 30)
+#define UNET_BOUNDARY_FIELDS 20
+size_t unet_boundary_distance_sq_workspace(int64_t n, int64_t h, int64_t w, int32_t num_classes);
+int32_t unet_boundary_distance_sq(const uint8_t* classes, int64_t n, int64_t h, int64_t w, int32_t num_classes,
+                                  int32_t* d2_out, void* workspace, size_t workspace_bytes, void* stream);
+int32_t unet_boundary_stats(const uint8_t* truth, const uint8_t* pred, const int32_t* d2_truth, const int32_t* d2_pred,
+                            int64_t n, int64_t h, int64_t w, int32_t num_classes, const int32_t* tol_sq /* host [k] */,
+                            int32_t k, int32_t band_sq, int32_t image_base, int64_t* records, int64_t* hist, void* stream);
+
 /* AUPRO: the area below the per-region-overlap curve up to a false-positive rate of fpr_limit, divided by fpr_limit (the
  * localisation metric of the MVTec AD evaluation; no reference counterpart).  With R regions and N ok pixels, walking
  * the distinct scores v downwards from the point (0, 0): fpr = #{ok pixels >= v} / N, pro = sum over the defective

@@ -623,6 +623,125 @@ class DetectionMatcher:
                 "pairs": cat(self._pairs, PAIR_FIELDS), "image_sizes": list(self.image_sizes), "images": self.images}
 
 
+BOUNDARY_NONE = 1 << 30         # UNET_BOUNDARY_NONE of include/unet_hip.h
+BOUNDARY_MAX_TOLERANCES = 4
+BOUNDARY_HIST_BINS = 1025
+BOUNDARY_FIELDS = (("image", "class", "t_pixels", "p_pixels", "t_boundary", "p_boundary")
+                   + tuple(f"p_near{k}" for k in range(BOUNDARY_MAX_TOLERANCES))
+                   + tuple(f"t_near{k}" for k in range(BOUNDARY_MAX_TOLERANCES))
+                   + ("band_inter", "band_union", "p_dist_sum_q8", "t_dist_sum_q8", "p_dist_max_sq", "t_dist_max_sq"))
+
+
+def _boundary_error(what, n, h, w, num_classes):
+    return RuntimeError(f"{what}: {n} x {h} x {w} maps of {num_classes} classes are not supported (sides up to 4096, 2..32 "
+                        "classes, n < 65536, fewer than 2^31 distances)")
+
+
+def boundary_distance_sq(labels, num_classes):
+    """Exact squared Euclidean distance to the class boundaries of integer label maps [N, H, W]: an int32
+    [N, num_classes - 1, H, W] DEVICE tensor, [n, c - 1, y, x] = the minimum of (y - y')^2 + (x - x')^2 over the boundary
+    pixels (y', x') of class c of image n, BOUNDARY_NONE in a plane whose image has none.  A pixel has class c iff its value
+    is c, 1 <= c < num_classes (everything else is background); it is a boundary pixel of c iff at least one 4-neighbour
+    inside the frame has another value, so the frame edge makes no boundary.  What
+    rint(scipy.ndimage.distance_transform_edt(~boundary) ** 2) gives plane by plane (unet_boundary_distance_sq, integers
+    throughout); does not synchronise."""
+    c = int(num_classes)
+    lib = L.lib()
+    if torch.is_tensor(labels) and labels.dim() == 3 and labels.numel():      # refused by its shape, before any conversion
+        n, h, w = labels.shape
+        if not 0 <= c < 2 ** 31 or lib.unet_boundary_distance_sq_workspace(n, h, w, c) == 0:
+            raise _boundary_error("boundary_distance_sq", n, h, w, num_classes)
+    t = _class_maps(labels, "boundary_distance_sq")
+    n, h, w = t.shape
+    d2 = torch.empty((n, c - 1, h, w), dtype=torch.int32, device=t.device)
+    ws = _workspace(lib.unet_boundary_distance_sq_workspace(n, h, w, c), t.device)
+    L.check(lib.unet_boundary_distance_sq(_ptr(t), n, h, w, c, _ptr(d2), _ptr(ws), ws.numel(), _stream()),
+            "unet_boundary_distance_sq")
+    return d2
+
+
+def boundary_band_width(h, w):
+    """Boundary IoU's default band: 2 % of the image diagonal, at least one pixel"""
+    import math
+    return max(1, round(0.02 * math.sqrt(h * h + w * w)))
+
+
+class BoundaryMatcher:
+    """Outline accuracy of predicted against true label maps, accumulated over batches: one record of BOUNDARY_FIELDS per
+    (image, foreground class) and a pooled histogram of boundary-to-boundary distances (unet_boundary_stats; integers
+    throughout, so both are a function of the label maps alone).  ``p_*`` fields belong to the prediction, ``t_*`` to the
+    truth: pixels and boundary pixels of the class; ``p_near{k}`` = predicted boundary pixels within ``tolerances[k]``
+    pixels (Euclidean) of the truth's boundary of the class, ``t_near{k}`` the other way round, the slots past the last
+    tolerance 0; ``band_inter`` / ``band_union`` = Boundary IoU's counts at the band width; ``p_dist_sum_q8`` = the sum over
+    the predicted boundary pixels of floor(256 * distance to the truth's boundary) and ``p_dist_max_sq`` the largest
+    squared distance among them, ``t_*`` the other way round.  Where the other map has no boundary of the class, a boundary
+    pixel counts in ``p_boundary`` / ``t_boundary`` only: ``seg_boundaries`` reports it as unmatched.
+
+    ``band_width`` = 0 means ``boundary_band_width(H, W)`` of the maps of each update (2 % of the diagonal, as the Boundary
+    IoU paper has it), so images of different sizes get their own.  ``update`` makes one distance call for truth and
+    prediction together and one statistics call, keeps the batch's records on the device and does not synchronise;
+    ``compute`` reads everything back once."""
+
+    def __init__(self, num_classes, tolerances=(1, 2, 4), band_width=0):
+        self.num_classes = int(num_classes)
+        if not 2 <= self.num_classes <= 32:
+            raise ValueError(f"BoundaryMatcher: {num_classes} classes, 2..32 are supported")
+        tol = list(tolerances)
+        if not 1 <= len(tol) <= BOUNDARY_MAX_TOLERANCES:
+            raise ValueError(f"BoundaryMatcher: 1..{BOUNDARY_MAX_TOLERANCES} tolerances, got {len(tol)}")
+        for v in list(tol) + [band_width]:
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 4096:
+                raise ValueError(f"BoundaryMatcher: tolerances and band_width are integers in 0..4096, got {v!r}")
+        self.tolerances = tuple(int(v) for v in tol)
+        self.band_width = int(band_width)
+        self._tol_sq = (C.c_int32 * len(tol))(*[v * v for v in self.tolerances])
+        self.images = 0
+        self.band_widths, self.image_sizes = [], []      # per image
+        self._records, self._hist = [], None
+
+    def update(self, pred_labels, truth):
+        """pred_labels / truth: integer device label maps of equal shape [N, H, W] (values outside 0..254 become 255)."""
+        what = "BoundaryMatcher.update"
+        if torch.is_tensor(pred_labels) and torch.is_tensor(truth) and pred_labels.shape != truth.shape:
+            raise ValueError(f"{what}: prediction / truth shapes differ")
+        p = _class_maps(pred_labels, what)
+        t = _class_maps(truth.to(p.device), what)
+        n, h, w = p.shape
+        c, dev = self.num_classes, p.device
+        if 2 * n >= 65536 or self.images + n >= 2 ** 31:
+            raise _boundary_error(what, 2 * n, h, w, c)
+        d2 = boundary_distance_sq(torch.cat([t, p]), c)       # one pass serves both
+        band = self.band_width or boundary_band_width(h, w)
+        if self._hist is None:
+            self._hist = torch.zeros((c - 1, 2, BOUNDARY_HIST_BINS), dtype=torch.int64, device=dev)
+        records = torch.zeros((n, c - 1, len(BOUNDARY_FIELDS)), dtype=torch.int64, device=dev)
+        L.check(L.lib().unet_boundary_stats(_ptr(t), _ptr(p), _ptr(d2[:n]), _ptr(d2[n:]), n, h, w, c, self._tol_sq,
+                                            len(self.tolerances), band * band, self.images, _ptr(records),
+                                            _ptr(self._hist), _stream()), "unet_boundary_stats")
+        self._records.append(records)
+        self.band_widths.extend([band] * n)
+        self.image_sizes.extend([(h, w)] * n)
+        self.images += n
+
+    def compute(self):
+        """{"records": int64 [images * (num_classes - 1), 20] numpy records of BOUNDARY_FIELDS sorted by (image, class), the
+        image index counted over all updates; "hist": int64 [num_classes - 1, 2, 1025], direction 0 = prediction to
+        truth, 1 = truth to prediction, bin min(floor(distance), 1024); "band_widths" and "image_sizes" per image;
+        "tolerances"; "images"}."""
+        import numpy as np
+        c, f = self.num_classes, len(BOUNDARY_FIELDS)
+        res = {"records": np.zeros((0, f), np.int64), "hist": np.zeros((c - 1, 2, BOUNDARY_HIST_BINS), np.int64),
+               "band_widths": list(self.band_widths), "image_sizes": list(self.image_sizes),
+               "tolerances": self.tolerances, "images": self.images}
+        if not self._records:
+            return res
+        flat = torch.cat([r.reshape(-1) for r in self._records] + [self._hist.reshape(-1)]).cpu().numpy()  # the one read-back
+        rec = flat[:-self._hist.numel()].reshape(-1, f)
+        res["records"] = np.ascontiguousarray(rec[np.lexsort((rec[:, 1], rec[:, 0]))])
+        res["hist"] = flat[-self._hist.numel():].reshape(c - 1, 2, BOUNDARY_HIST_BINS).copy()
+        return res
+
+
 def preprocess_u8(images_u8, flips=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """uint8 [N, H, W, 3] device batch -> normalised fp32 NCHW (ToTensor + Normalize, optional per-sample horizontal
     flip): /root/reference/src/dataset.py:134-146, src/kolektorsdd_dataset.py:133-150, on the GPU."""
