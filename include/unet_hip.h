@@ -666,6 +666,48 @@ int32_t unet_render_sheet(const unet_panel* panels, int32_t k, int32_t n, int32_
 int32_t unet_seg_confidence(const float* logits, int32_t n, int32_t c, int64_t hw, uint8_t* labels, float* conf,
                             void* stream);
 
+/* Calibration of that confidence (no reference counterpart; csrc/calibration.hip, restated in numpy by
+ * tests/_calibration_ref.py): the confidence at a temperature, a reliability histogram, and the negative log-likelihood
+ * at up to 32 temperatures from one read of the logits.  All three refuse on the host, before any HIP call and so also
+ * without a GPU, with UNET_ERR_UNSUPPORTED (-2, the status unet_seg_confidence gives for its class count): a NULL
+ * pointer, c outside 2..8, n < 1, hw < 1 (histogram and sweep: hw > 2^31 - 1; sweep: n >= 65536), bins outside 1..64, k
+ * outside 1..32, select not 0 or 1, an inv_t that is not a finite fp32 > 0.  They allocate nothing and do not synchronise.
+ *
+ * unet_seg_confidence_scaled: unet_seg_confidence of softmax(z / T), inv_t = 1 / T.  labels = the first maximum of the RAW
+ * logits (a rounding of z * inv_t can never change a label); conf = 1 / sum_j expf((z_j - max z) * inv_t), every
+ * operation one fp32 rounding, j in class order.  The same 16-byte / scalar access rule.  At inv_t == 1.0f the product is
+ * exact and the bytes are those of unet_seg_confidence.  labels or conf may be NULL (not both).
+ *
+ * unet_reliability_histogram: labels (uint8) and conf (fp32) as unet_seg_confidence_scaled or unet_tile_blend wrote them,
+ * target (int64), all [n][hw].  hist (uint64 [c][bins][3], device, ADDED to: zero it first): per PREDICTED class and
+ * confidence bin {pixels, pixels whose target equals the label, sum of q}, q(v) = (uint32) rint(v * 65536.0f) (ties to
+ * even) on v clamped to [0, 1], NaN -> 0 (the rule of unet_describe_class_regions), bin = min(bins - 1, (q * bins) >> 16).
+ * A pixel is skipped, and counted in skipped[0] (uint64, device, ADDED to), when its target is ignore_index or outside
+ * 0..c-1 or its label is >= c.  select 0 takes every other pixel, select 1 only those whose target or label is not class
+ * 0; a pixel that select leaves out is not counted anywhere.  Integers only (32-bit LDS cells per block of at most 4096
+ * pixels, 64-bit integer atomics to memory): the outputs are a function of the inputs alone, and no cell overflows before
+ * 2^47 pixels.
+ *
+ * unet_temperature_sweep: logits fp32 [n][c][hw], target int64 [n][hw], inv_t = HOST array of k values.  With d_j = z_j -
+ * max z and t the target: nll[i] (fp64 [k], device, ADDED to) += the sum over the pixels taken of
+ * logf(sum_j expf(d_j * inv_t[i])) - d_t * inv_t[i], the per-pixel term in fp32 with every product and sum rounded once
+ * (j in class order), the sum in fp64.  counted (uint64 [2], device, ADDED to): [0] the pixels taken, [1] the pixels with a
+ * non-finite logit, which are set aside first, whatever their target.  The skip and select rules are the histogram's,
+ * with the label = the first maximum, computed here.  The order of summation is a function of (n, hw, k) alone (fixed
+ * pixel ranges per lane and block, shuffle trees, block partials in the workspace, one ordered final sum; no
+ * floating-point atomics): two calls on the same input give the same bits, whichever of the 16-byte (hw % 4 == 0, aligned
+ * pointers) and scalar loads they use.  The workspace (8-byte aligned) holds the block partials; too small a one is
+ * UNET_ERR_WORKSPACE, and the query returns 0 for a shape the call refuses. */
+int32_t unet_seg_confidence_scaled(const float* logits, int32_t n, int32_t c, int64_t hw, float inv_t, uint8_t* labels,
+                                   float* conf, void* stream);
+int32_t unet_reliability_histogram(const uint8_t* labels, const float* conf, const int64_t* target, int32_t n, int64_t hw,
+                                   int32_t c, int32_t bins, int64_t ignore_index, int32_t select, uint64_t* hist,
+                                   uint64_t* skipped, void* stream);
+size_t unet_temperature_sweep_workspace(int32_t n, int64_t hw, int32_t k);
+int32_t unet_temperature_sweep(const float* logits, const int64_t* target, int32_t n, int32_t c, int64_t hw,
+                               int64_t ignore_index, int32_t select, const float* inv_t /* host [k] */, int32_t k,
+                               double* nll, uint64_t* counted, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The prediction sheets of the Gear / KolektorSDD visualisation CLIs (visualize.py:120-236 visualize_single_prediction /
  * visualize_prediction_grid, visualize_kolektorsdd.py:101-202, drawn there by matplotlib on the host) as one packed
  * uint8 RGB image written by one launch: R = ceil(n / per_row) rows of per_row samples, each sample k <= 8 panels of

@@ -167,6 +167,10 @@ SIGNATURES = {
     "unet_render_sheet": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "unet_seg_confidence": (_i, [_p, _i, _i, _l, _p, _p, _p]),
     "unet_seg_render_sheet": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "unet_seg_confidence_scaled": (_i, [_p, _i, _i, _l, _f, _p, _p, _p]),
+    "unet_reliability_histogram": (_i, [_p, _p, _p, _i, _l, _i, _i, _l, _i, _p, _p, _p]),
+    "unet_temperature_sweep_workspace": (_z, [_i, _l, _i]),
+    "unet_temperature_sweep": (_i, [_p, _p, _i, _i, _l, _l, _i, _p, _i, _p, _p, _p, _z, _p]),
     "unet_channel_scale": (_i, [_i, _p, _p, _i, _l, _i, _p, _p]),
     "unet_anomaly_score_workspace": (_z, [_i, _l]),
     "unet_anomaly_score": (_i, [_p, _p, _i, _i, _l, _i, _p, _p, _p, _z, _p]),

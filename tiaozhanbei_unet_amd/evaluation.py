@@ -742,6 +742,121 @@ class BoundaryMatcher:
         return res
 
 
+CALIBRATION_MAX_BINS = 64
+CALIBRATION_MAX_TEMPERATURES = 32
+CALIBRATION_SELECT = {"all": 0, "defects": 1}
+
+
+class CalibrationMeter:
+    """Calibration of the per-pixel confidence, accumulated over batches (csrc/calibration.hip): a reliability histogram of
+    the confidence at ``temperature`` and the summed negative log-likelihood of softmax(logits / T) for every T of
+    ``temperatures`` (up to 32), both over the same pixels.  A pixel whose target is ``ignore_index`` or outside
+    0..num_classes-1 is skipped; ``select`` "defects" also leaves out the pixels whose target and label are both class 0
+    (background is ~99 % of these data sets).  ``seg_calibration`` turns the result into ECE / MCE and a fitted temperature.
+
+    ``update`` makes three launches -- the confidence at ``temperature`` (``sheets.seg_confidence``), the histogram
+    (unet_reliability_histogram), the sweep (unet_temperature_sweep) -- into device accumulators and does not synchronise;
+    ``update_confidence`` takes labels and confidence that exist already (``tiling.blend_tiles`` makes them) and runs the
+    histogram alone.  ``compute`` reads everything back once."""
+
+    def __init__(self, num_classes, bins=15, temperatures=(1.0,), temperature=1.0, ignore_index=None, select="all"):
+        from .sheets import inverse_temperature
+        self.num_classes, self.bins = int(num_classes), int(bins)
+        if not 2 <= self.num_classes <= 8:
+            raise ValueError(f"CalibrationMeter: {num_classes} classes, 2..8 are supported")
+        if not 1 <= self.bins <= CALIBRATION_MAX_BINS:
+            raise ValueError(f"CalibrationMeter: {bins} bins, 1..{CALIBRATION_MAX_BINS} are supported")
+        self.temperatures = tuple(float(t) for t in temperatures)
+        if not 1 <= len(self.temperatures) <= CALIBRATION_MAX_TEMPERATURES:
+            raise ValueError(f"CalibrationMeter: {len(self.temperatures)} temperatures, 1..{CALIBRATION_MAX_TEMPERATURES} "
+                             "are supported")
+        self.inv_t = [inverse_temperature(t, "CalibrationMeter: temperature") for t in self.temperatures]
+        self.temperature = float(temperature)
+        inverse_temperature(self.temperature, "CalibrationMeter: temperature")
+        if select not in CALIBRATION_SELECT:
+            raise ValueError(f"CalibrationMeter: select is 'all' or 'defects', got {select!r}")
+        self.select = select
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
+        self._inv_t = (C.c_float * len(self.inv_t))(*self.inv_t)
+        self._counts = None            # int64 [C * bins * 3 + 3]: the histogram, skipped, taken, non-finite
+        self._nll = None               # float64 [K]
+
+    def _accumulators(self, dev):
+        if self._counts is None:
+            self._counts = torch.zeros(self.num_classes * self.bins * 3 + 3, dtype=torch.int64, device=dev)
+            self._nll = torch.zeros(len(self.temperatures), dtype=torch.float64, device=dev)
+        elif self._counts.device != dev:
+            raise ValueError("CalibrationMeter: every update must be on the same device")
+        return self._counts, self._nll
+
+    def _target(self, target, shape, dev, what):
+        if not torch.is_tensor(target) or target.is_floating_point() or target.dtype == torch.bool \
+                or tuple(target.shape) != shape:
+            raise ValueError(f"{what}: the target is an integer tensor {shape}")
+        return target.detach().to(device=dev, dtype=torch.int64).contiguous()
+
+    def update_confidence(self, labels, conf, target):
+        """labels uint8 / conf float32 / target integer DEVICE tensors (N, H, W): the histogram alone."""
+        what = "CalibrationMeter.update_confidence"
+        _require_cuda(labels, conf)
+        if labels.dtype != torch.uint8 or labels.dim() != 3 or labels.numel() == 0:
+            raise ValueError(f"{what}: labels are a uint8 (N, H, W) tensor, got {labels.dtype} {tuple(labels.shape)}")
+        if not conf.is_floating_point() or conf.shape != labels.shape or conf.device != labels.device:
+            raise ValueError(f"{what}: conf is a float tensor {tuple(labels.shape)} on the labels' device")
+        n, h, w = labels.shape
+        t = self._target(target, (n, h, w), labels.device, what)
+        lab, cf = labels.detach().contiguous(), conf.detach().float().contiguous()
+        counts, _ = self._accumulators(lab.device)
+        cells = self.num_classes * self.bins * 3
+        ign = -1 if self.ignore_index is None else self.ignore_index       # a negative target is skipped anyway
+        L.check(L.lib().unet_reliability_histogram(_ptr(lab), _ptr(cf), _ptr(t), n, h * w, self.num_classes, self.bins, ign,
+                                                   CALIBRATION_SELECT[self.select], _ptr(counts), _ptr(counts[cells:]),
+                                                   _stream()), "unet_reliability_histogram")
+
+    def update(self, logits, target):
+        """logits: float DEVICE tensor (N, num_classes, H, W); target: integer tensor (N, H, W)."""
+        from .sheets import seg_confidence
+        what = "CalibrationMeter.update"
+        _require_cuda(logits)
+        if logits.dim() != 4 or logits.shape[1] != self.num_classes or logits.numel() == 0:
+            raise ValueError(f"{what}: logits are (N, {self.num_classes}, H, W), got {tuple(logits.shape)}")
+        n, c, h, w = logits.shape
+        x = logits.detach().float().contiguous()
+        t = self._target(target, (n, h, w), x.device, what)
+        labels, conf = seg_confidence(x, temperature=self.temperature)
+        self.update_confidence(labels, conf, t)
+        counts, nll = self._accumulators(x.device)
+        lib = L.lib()
+        k = len(self.inv_t)
+        nbytes = lib.unet_temperature_sweep_workspace(n, h * w, k)
+        if nbytes == 0:
+            raise RuntimeError(f"{what}: {n} x {h} x {w} logits are not supported (n < 65536, at most 2^31 - 1 pixels an image)")
+        ws = _workspace(nbytes, x.device)
+        cells = c * self.bins * 3
+        ign = -1 if self.ignore_index is None else self.ignore_index
+        L.check(lib.unet_temperature_sweep(_ptr(x), _ptr(t), n, c, h * w, ign, CALIBRATION_SELECT[self.select], self._inv_t,
+                                           k, _ptr(nll), _ptr(counts[cells + 1:]), _ptr(ws), ws.numel(), _stream()),
+                "unet_temperature_sweep")
+
+    def compute(self):
+        """{"hist": int64 [num_classes, bins, 3] numpy {pixels, correct pixels, sum of q = rint(65536 conf)} by predicted
+        class and bin, "skipped", "nll": float64 [K] summed over "counted" pixels, "nonfinite": pixels with a non-finite
+        logit, set aside by the sweep, "temperatures", "temperature", "bins", "select"}."""
+        import numpy as np
+        c, b, k = self.num_classes, self.bins, len(self.temperatures)
+        res = {"hist": np.zeros((c, b, 3), np.int64), "skipped": 0, "nll": np.zeros(k, np.float64), "counted": 0,
+               "nonfinite": 0, "temperatures": self.temperatures, "temperature": self.temperature, "bins": b,
+               "select": self.select}
+        if self._counts is None:
+            return res
+        flat = torch.cat([self._counts, self._nll.view(torch.int64)]).cpu().numpy()      # the one read-back
+        cells = c * b * 3
+        res["hist"] = flat[:cells].reshape(c, b, 3).copy()
+        res["skipped"], res["counted"], res["nonfinite"] = (int(v) for v in flat[cells:cells + 3])
+        res["nll"] = flat[cells + 3:].view(np.float64).copy()
+        return res
+
+
 def preprocess_u8(images_u8, flips=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """uint8 [N, H, W, 3] device batch -> normalised fp32 NCHW (ToTensor + Normalize, optional per-sample horizontal
     flip): /root/reference/src/dataset.py:134-146, src/kolektorsdd_dataset.py:133-150, on the GPU."""

@@ -19,7 +19,8 @@ from . import _lib as L
 from ._hipcall import (BN_EPS, _DT, _as_nhwc, _is_nhwc, _nhwc_empty, _pad64, _ptr, _require_cuda, _stream, _views,
                        _workspace, prof_collect, prof_enable, prof_kernels)
 from .evaluation import (BOUNDARY_FIELDS, BOUNDARY_NONE, DEFECT_FIELDS, PAIR_FIELDS, RECORD_FIELDS, BinaryAUC,
-                         BoundaryMatcher, ClassRegionMatcher, DetectionMatcher, GaussianSmoother, RegionOverlapAUC,
+                         BoundaryMatcher, CalibrationMeter, ClassRegionMatcher, DetectionMatcher, GaussianSmoother,
+                         RegionOverlapAUC,
                          anomaly_score, boundary_distance_sq, describe_class_regions, label_class_regions, label_regions,
                          pair_class_regions, preprocess_u8, threshold_confusion)
 from .sheets import (IMAGENET_MEAN, IMAGENET_STD, MAX_PANELS, TAB10, class_palette, colormap_lut, panel_range,

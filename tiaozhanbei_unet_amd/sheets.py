@@ -157,21 +157,45 @@ TAB10 = ((31, 119, 180), (255, 127, 14), (44, 160, 44), (214, 39, 40), (148, 103
 _seg_tables = {}           # (device index, "palette" | "lut") -> the default table, uploaded once
 
 
-def seg_confidence(logits, labels=True, conf=True):
+def inverse_temperature(temperature, what="temperature"):
+    """float32(1 / T) as a Python float, the ``inv_t`` of unet_seg_confidence_scaled and unet_temperature_sweep: the
+    quotient in float64, rounded once.  ValueError unless both T and the rounded quotient are finite and > 0."""
+    import math
+    import struct
+    t = float(temperature)
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f"{what} {temperature!r} is not a finite value > 0")
+    try:
+        inv = struct.unpack("f", struct.pack("f", 1.0 / t))[0]
+    except OverflowError:
+        inv = math.inf
+    if not (math.isfinite(inv) and inv > 0.0):
+        raise ValueError(f"{what} {temperature!r}: 1 / T is not a finite float32 > 0")
+    return inv
+
+
+def seg_confidence(logits, labels=True, conf=True, temperature=1.0):
     """(labels, conf) of (N, C, H, W) logits, 2 <= C <= 8, as DEVICE tensors: labels uint8 (N, H, W) = the argmax (the
     first maximum wins ties, as torch.argmax), conf float32 (N, H, W) = softmax(logits, 1).max(1) computed in fp32 as
     1 / sum_j expf(z_j - max z) (reference visualize.py:134-135, visualize_kolektorsdd.py:131).  Either is None
-    when not asked for.  One launch (unet_seg_confidence); does not synchronise."""
+    when not asked for.  ``temperature`` T != 1: the confidence of softmax(logits / T), 1 / sum_j expf((z_j - max z) *
+    float32(1 / T)), with the labels still those of the raw logits (unet_seg_confidence_scaled).  One launch
+    (unet_seg_confidence at T == 1); does not synchronise."""
     _require_cuda(logits)
     if logits.dim() != 4:
         raise ValueError(f"seg_confidence: logits are (N, C, H, W), got {tuple(logits.shape)}")
     if not (labels or conf):
         raise ValueError("seg_confidence: neither labels nor conf asked for")
+    inv_t = 1.0 if float(temperature) == 1.0 else inverse_temperature(temperature, "seg_confidence: temperature")
     n, c, h, w = logits.shape
     x = logits.detach().float().contiguous()
     lab = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if labels else None
     cf = torch.empty((n, h, w), dtype=torch.float32, device=x.device) if conf else None
-    L.check(L.lib().unet_seg_confidence(_ptr(x), n, c, h * w, _ptr(lab), _ptr(cf), _stream()), "unet_seg_confidence")
+    if float(temperature) == 1.0:
+        L.check(L.lib().unet_seg_confidence(_ptr(x), n, c, h * w, _ptr(lab), _ptr(cf), _stream()), "unet_seg_confidence")
+    else:
+        L.check(L.lib().unet_seg_confidence_scaled(_ptr(x), n, c, h * w, inv_t, _ptr(lab), _ptr(cf), _stream()),
+                "unet_seg_confidence_scaled")
     return lab, cf
 
 

@@ -157,3 +157,18 @@ class TiledPredictor:
         tiles = gather_tiles(frame.float(), th, tw, oy, ox)
         labels, conf = blend_tiles(self.tile_logits(tiles), oy, ox, (h, w), ramp=ramp)
         return labels, conf, {"tile": [th, tw], "origins_y": oy, "origins_x": ox, "ramp": ramp}
+
+    def blended_logits(self, frame):
+        """(logits float32 (C, H, W), plan): the blended logits that ``__call__`` takes its labels and confidence from, by
+        the same plan (``blend_tiles(..., blended=True)``), for whoever needs more than the maximum.
+        ``sheets.seg_confidence`` of them gives ``__call__``'s labels and confidence bit for bit."""
+        if not torch.is_tensor(frame) or frame.dim() != 3:
+            raise ValueError("TiledPredictor: a frame is a (3, H, W) tensor")
+        h, w = int(frame.shape[1]), int(frame.shape[2])
+        th, tw = min(self.tile_hw[0], h), min(self.tile_hw[1], w)
+        oy = plan_axis(h, th, min(self.min_overlap, th - 1))
+        ox = plan_axis(w, tw, min(self.min_overlap, tw - 1))
+        ramp = [default_ramp(oy, th), default_ramp(ox, tw)]
+        tiles = gather_tiles(frame.float(), th, tw, oy, ox)
+        _labels, _conf, mixed = blend_tiles(self.tile_logits(tiles), oy, ox, (h, w), ramp=ramp, blended=True)
+        return mixed, {"tile": [th, tw], "origins_y": oy, "origins_x": ox, "ramp": ramp}
