@@ -904,6 +904,39 @@ int32_t unet_tile_blend(const float* tiles, int32_t c, int32_t th, int32_t tw, c
                         const int32_t* ox, int32_t nx, int32_t h, int32_t w, int32_t ramp_y, int32_t ramp_x,
                         uint8_t* labels, float* conf, float* blended, void* stream);
 
+/* View ensembling (predict_views, eval_views; no reference counterpart: the reference asks its model once per image): the
+ * logits of n_views views of one image -- the image resized by a factor, possibly mirrored -- are brought back onto one
+ * frame of h x w and reduced (csrc/views.hip, restated by tests/_views_ref.py).  views[n_views]: a HOST array; the
+ * descriptors travel in the kernel arguments, so nothing is allocated, copied or synchronised and the call can be
+ * captured.  View v: logits = DEVICE fp32 [c][h][w] of ITS h x w, flip_x / flip_y = 1 when the model saw the image
+ * mirrored along x / y (the logits are those of the mirrored image) else 0.
+ * Sampling, per axis, in integers: for output index i of an axis with N frame and M view samples
+ *   p = floor(((2 i + 1) M 2^15) / N) - 2^15 in 64-bit integers, clamped to [0, (M - 1) 2^16]: (i + 1/2) M / N - 1/2 in
+ *   16.16, the half-pixel-centre convention with edge clamp; i0 = p >> 16, f = p & 0xFFFF, i1 = min(i0 + 1, M - 1);
+ *   M == N gives the tap i with fraction 0.  A flipped axis reads M - 1 - i0 and M - 1 - i1.
+ * The value of a view at a pixel, with a00 .. a11 the samples at (y0 | y1, x0 | x1): top = ((float)(65536 - fx) a00 +
+ * (float)fx a01) 2^-16, bot likewise from a10 and a11, val = ((float)(65536 - fy) top + (float)fy bot) 2^-16, every product
+ * and every sum one fp32 rounding.  A view with the frame's size on BOTH axes is not interpolated: its logits are taken
+ * unchanged, bits included.
+ * Reduction, per pixel and class: acc_c starts as the first view's value and adds the others in ascending view order;
+ * merged[c][h][w] (fp32) = acc_c / (float)n_views, one correctly rounded division.  labels[h][w] (uint8) and conf[h][w]
+ * (fp32) follow from the merged logits by unet_seg_confidence's rule: the first maximum wins, conf = 1 / sum_j expf(z_j -
+ * max z) in class order.  agreement[h][w] (uint8) = the number of views whose own first maximum over the classes of val
+ * equals the merged label.  Logits are averaged, not probabilities: merged, labels and agreement are a function of the
+ * inputs alone, with no expf between.  Each output may be NULL, not all of them.  The contract covers finite logits.
+ * Refused on the host before any HIP call, all UNET_ERR_UNSUPPORTED: a NULL views array or a NULL logits pointer;
+ * n_views outside 1..16; c outside 2..8; h, w or a view's h, w outside 1..16384; every output NULL; a flip that is not 0
+ * or 1.  One launch, no atomics, no LDS, no workspace; a lane owns 4 consecutive x (16-byte stores, and 16-byte loads of
+ * the views of the frame's own size, reversed under flip_x) when w is a multiple of 4 and merged, conf and those views
+ * are 16-byte aligned (labels, agreement: 4), else one pixel.  Allocates nothing, does not synchronise. */
+typedef struct unet_merge_view {
+  const float* logits;
+  int32_t h, w;
+  int32_t flip_x, flip_y;
+} unet_merge_view;
+int32_t unet_view_merge(const unet_merge_view* views, int32_t n_views, int32_t c, int32_t h, int32_t w, float* merged,
+                        uint8_t* labels, float* conf, uint8_t* agreement, void* stream);
+
 /* Affine crops of a ragged batch (train_gear_crops; no reference counterpart: the reference trains on squeezed frames):
  * n_crops crops of out_h x out_w, cut with scale, rotation and flip out of n_images images of DIFFERENT sizes, in one
  * launch (csrc/crops.hip, restated in numpy int64 by tests/_crops_ref.py).  src: one packed byte buffer of src_bytes

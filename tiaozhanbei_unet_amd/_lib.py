@@ -63,6 +63,13 @@ class CropDesc(C.Structure):
 
 
 CROP_NEAREST, CROP_BILINEAR = 0, 1
+
+
+class MergeView(C.Structure):
+    """struct unet_merge_view"""
+    _fields_ = [("logits", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("flip_x", C.c_int32), ("flip_y", C.c_int32)]
+
+
 _i, _l, _f, _p, _z, _d = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes): every symbol include/unet_hip.h declares
@@ -189,7 +196,8 @@ SIGNATURES = {
     "unet_smooth_maps": (_i, [_p, _p, _l, _i, _i, _p, _i, _p, _p]),
     "unet_tile_gather": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p]),
     "unet_tile_blend": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
-    "unet_affine_crop_u8": (_i, [_p, _l, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "unet_view_merge": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "unet_affine_crop_u8":(_i, [_p, _l, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
     "unet_adam_chunk_elems": (_i, []),
     "unet_adam_multi": (_i, [_p, _p, _i, _f, _d, _d, _f, _f, _f, _i, _i, _p]),
     "unet_adam_step": (_i, [_p, _p, _p, _p, _l, _f, _d, _d, _f, _f, _f, _i, _p]),
