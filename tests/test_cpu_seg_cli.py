@@ -1,13 +1,15 @@
 """CPU checks of the KolektorSDD trainer and the Gear / KolektorSDD evaluation CLIs: their flags against the
 reference's (pinned as data), the refusal of a CPU device, the exports of the per-image statistics kernel, and the host
-helper that turns one image's counts into the reference's ``compute_prediction_stats`` dict."""
+helper that turns one image's counts into the reference's ``compute_prediction_stats`` dict; and the refusals that the
+tools over a checkpoint take from ``seg_cli``."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
-from tiaozhanbei_unet_amd import _lib, eval_gear, eval_kolektorsdd, train_kolektorsdd
+from tiaozhanbei_unet_amd import (_lib, eval_boundaries, eval_calibration, eval_detection, eval_gear, eval_kolektorsdd,
+                                 eval_views, predict, predict_tiled, predict_views, seg_cli, train_kolektorsdd)
 from tiaozhanbei_unet_amd.metrics import image_prediction_stats
 
 REFERENCE_KOLEKTOR_TRAIN_FLAGS = {  # reference train_kolektorsdd.py:26-101, pinned here as data
@@ -57,6 +59,56 @@ def test_seg_clis_refuse_cpu(main, argv):
     with pytest.raises(SystemExit) as e:
         main(["--device", "cpu"] + argv)
     assert "no CPU path" in str(e.value)
+
+
+TILED_TOOLS = [eval_detection, eval_boundaries, eval_calibration, eval_views]
+
+
+@pytest.mark.parametrize("tool", TILED_TOOLS, ids=[t.__name__.rsplit(".", 1)[1] for t in TILED_TOOLS])
+def test_shared_tiling_refusals(tool, capsys):
+    """the tiling flags are seg_cli's, object for object, and so are their rules; eval_views is always tiled"""
+    gear = ["--dataset", "gear", "--checkpoint", "c.pth"]
+    always_tiled = tool is eval_views
+    tiled = [] if always_tiled else ["--tiled"]
+    for dataset in (("gear",) if always_tiled else seg_cli.DATASETS):
+        flags = dict(tool.flags_of(dataset))
+        assert all(flags[name] is kw for name, kw in seg_cli.TILING_FLAGS)
+    assert [name for name, _ in seg_cli.TILING_FLAGS] == ["--tiled", "--tile", "--min_overlap"]
+    args = tool.parse_args(gear + tiled + ["--tile", "64", "64", "--min_overlap", "63"])
+    assert (args.tiled, args.tile, args.min_overlap) == (True, [64, 64], 63)
+    for bad, said in ((gear + ["--tile", "0", "64"], "--tile sides must be positive"),
+                      (gear + tiled + ["--tile", "0", "64"], "--tile sides must be positive"),
+                      (gear + tiled + ["--tile", "64", "64", "--min_overlap", "64"], "smaller than both tile sides"),
+                      (gear + tiled + ["--tile", "64", "32", "--min_overlap", "32"], "smaller than both tile sides"),
+                      (gear + tiled + ["--min_overlap", "-1"], "--min_overlap must be at least 0")):
+        with pytest.raises(SystemExit):
+            tool.parse_args(bad)
+        assert said in capsys.readouterr().err, bad
+    if always_tiled:
+        return
+    args = tool.parse_args(gear + ["--min_overlap", "512"])        # the overlap binds only where tiles are cut
+    assert (args.tiled, args.tile, args.min_overlap) == (False, [512, 512], 512)
+    with pytest.raises(SystemExit):
+        tool.parse_args(["--dataset", "kolektorsdd", "--checkpoint", "c.pth", "--tiled"])
+    assert "--tiled needs --dataset gear" in capsys.readouterr().err
+    assert tool.parse_args(["--dataset", "kolektorsdd", "--checkpoint", "c.pth"]).tile == [1024, 512]
+
+
+PREDICT_TOOLS = [predict, predict_tiled, predict_views]
+
+
+@pytest.mark.parametrize("tool", PREDICT_TOOLS, ids=[t.__name__.rsplit(".", 1)[1] for t in PREDICT_TOOLS])
+@pytest.mark.parametrize("extra, said", [(["--batch_size", "0"], "--batch_size must be at least 1"),
+                                         (["--min_region_pixels", "0"], "--min_region_pixels must be at least 1"),
+                                         (["--min_confidence", "1.5"], "--min_confidence must lie in 0..1"),
+                                         (["--min_confidence", "-0.1"], "--min_confidence must lie in 0..1")])
+def test_shared_predict_refusals(tool, extra, said, capsys):
+    base = ["--task", "gear", "--checkpoint", "c.pth", "--input", "photos"]
+    args = tool.parse_args(base + ["--batch_size", "1", "--min_region_pixels", "1", "--min_confidence", "1"])
+    assert (args.batch_size, args.min_region_pixels, args.min_confidence) == (1, 1, 1.0)
+    with pytest.raises(SystemExit):
+        tool.parse_args(base + extra)
+    assert said in capsys.readouterr().err
 
 
 def test_library_exports_per_image_stats():

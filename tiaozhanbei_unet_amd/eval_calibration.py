@@ -28,16 +28,13 @@ calibration improves the accept / reject decisions on real Gear data has not bee
 """
 from __future__ import annotations
 
-import argparse
 import json
 import os
-import sys
 
-from . import eval_detection, eval_regions, seg_calibration
+from . import seg_calibration, seg_cli
 
-DATASETS = eval_regions.DATASETS
-_TILE_FLAGS = ("--tiled", "--tile", "--min_overlap")
-EXTRA_FLAGS = [(n, kw) for n, kw in eval_detection.EXTRA_FLAGS if n in _TILE_FLAGS] + [
+DATASETS = seg_cli.DATASETS
+EXTRA_FLAGS = seg_cli.TILING_FLAGS + [
     ("--bins", dict(type=int, default=15, help="confidence bins of the reliability diagram, 1..64")),
     ("--temperature_range", dict(type=float, nargs=2, default=[0.25, 4.0], metavar=("LO", "HI"),
                                  help="the temperatures searched, 0 < LO < HI")),
@@ -52,29 +49,13 @@ EPILOG = ("Fit on --split val, never on the split you report.  The fold of --sav
 
 
 def flags_of(dataset):
-    cli = eval_regions._cli(dataset)
-    return [(n, kw) for n, kw in cli.FLAGS if n not in eval_regions._NOT_HERE] + EXTRA_FLAGS
+    return seg_cli.base_flags(dataset) + EXTRA_FLAGS
 
 
 def parse_args(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    first = argparse.ArgumentParser(add_help=False)
-    first.add_argument("--dataset", required=True, choices=DATASETS)
-    dataset = first.parse_known_args(argv)[0].dataset          # its flags depend on the data set
-    ap = argparse.ArgumentParser(description="Confidence calibration of a segmentation checkpoint: reliability, ECE, a "
-                                             "fitted temperature (MI355X HIP path)", epilog=EPILOG)
-    ap.add_argument("--dataset", required=True, choices=DATASETS)
-    for name, kw in flags_of(dataset):
-        ap.add_argument(name, **kw)
-    args = ap.parse_args(argv)
-    if args.tiled and dataset != "gear":
-        ap.error("--tiled needs --dataset gear: KolektorSDD's masks are bitmaps, there is no full-resolution loader")
-    if args.tile is None:
-        args.tile = eval_detection.frame_of(args)
-    if min(args.tile) < 1:
-        ap.error("--tile sides must be positive")
-    if args.min_overlap < 0 or (args.tiled and args.min_overlap >= min(args.tile)):
-        ap.error("--min_overlap must be at least 0 and, with --tiled, smaller than both tile sides")
+    ap, args = seg_cli.parse_dataset_args(argv, "Confidence calibration of a segmentation checkpoint: reliability, ECE, a "
+                                                "fitted temperature (MI355X HIP path)", flags_of, epilog=EPILOG)
+    seg_cli.check_tiling(ap, args)
     if not 1 <= args.bins <= 64:
         ap.error("--bins must lie in 1..64")
     lo, hi = args.temperature_range
@@ -96,17 +77,12 @@ def frame_logits(model, batches):
 
 def tiled_logits(predictor, loader, device):
     """(logits (1, C, H, W), mask (1, H, W)) of every image of a raw Gear loader at its own size, the way
-    ``eval_detection.match_tiled`` walks it"""
+    ``seg_cli.tiled_predictions`` walks it"""
     import torch
-    from .augment import color_jitter_normalize_u8
-    from .crops import full_resolution_masks
     with torch.no_grad():
-        for images, polys, sizes, _paths in loader:
-            masks = full_resolution_masks(polys, sizes, device=device)
-            for i in range(len(sizes)):
-                frame = color_jitter_normalize_u8(images[i].to(device, non_blocking=True).unsqueeze(0))[0]
-                logits, _plan = predictor.blended_logits(frame)
-                yield logits.unsqueeze(0), masks[i].unsqueeze(0)
+        for image, mask, _path in seg_cli.full_resolution_images(loader, device):
+            logits, _plan = predictor.blended_logits(seg_cli.normalized_frame(image))
+            yield logits[None], mask[None]
 
 
 def measure(pairs, num_classes, bins, temperatures, temperature, select):
@@ -121,28 +97,12 @@ def measure(pairs, num_classes, bins, temperatures, temperature, select):
 def main(argv=None):
     args = parse_args(argv)
     import torch
-    from .train_gear import build_seg_model, require_gpu
-    from .utils import load_checkpoint
 
-    device = require_gpu(args)
-    cli = eval_regions._cli(args.dataset)
-    mode = "tiled" if args.tiled else "frame"
-    print("=" * 60 + f"\n{args.dataset.upper()} DATASET CALIBRATION ({mode})\n" + "=" * 60)
-    print(f"Device: {device}\nCheckpoint: {os.path.basename(args.checkpoint)}\nDataset: {args.split} split")
-    os.makedirs(args.save_dir, exist_ok=True)
-    loader, num_classes = cli._split_loader(args)
-    class_names = list(cli._class_names(loader.dataset, num_classes))
-    print(f"Number of classes: {num_classes}\nClass names: {class_names}\nSamples: {len(loader.dataset)}")
-    model = build_seg_model(args, num_classes, device)
-    epoch, loss = load_checkpoint(model, None, args.checkpoint, device)
-    print(f"Loaded checkpoint from epoch {epoch} with loss {loss:.4f}")
-
+    mode = seg_cli.mode_of(args)
+    device, cli, loader, num_classes, class_names, model = seg_cli.open_checkpoint_session(args, "CALIBRATION", mode)
+    class_names = list(class_names)
     if args.tiled:
-        from .tiling import TiledPredictor
-        from .train_gear_crops import check_image_sizes
-        check_image_sizes([loader.dataset])
-        print(f"Tile: {args.tile}  min overlap: {args.min_overlap}")
-        predictor = TiledPredictor(model, args.tile, args.min_overlap, args.batch_size)
+        predictor = seg_cli.tiled_predictor(args, loader, model)
 
         def pairs():
             return tiled_logits(predictor, loader, device)

@@ -25,120 +25,48 @@ region).  The numbers describe the checkpoint given, on the split given.
 """
 from __future__ import annotations
 
-import argparse
 import json
 import os
-import sys
 
-from . import eval_regions, seg_detection
+from . import eval_regions, seg_cli, seg_detection
 
-DATASETS = eval_regions.DATASETS
+DATASETS = seg_cli.DATASETS
 EXTRA_FLAGS = [("--max_false_alarms", dict(type=float, default=0.1,
                                            help="false alarms per image the recommended --min_confidence may cost")),
-               ("--tiled", dict(action="store_true", help="Gear: predict every image at its own size, in tiles")),
-               ("--tile", dict(type=int, nargs=2, default=None, metavar=("H", "W"), help="default: the frame flags")),
-               ("--min_overlap", dict(type=int, default=64, help="pixels neighbouring tiles share at least"))]
+               *seg_cli.TILING_FLAGS]
 
 
 def flags_of(dataset):
     return eval_regions.flags_of(dataset) + EXTRA_FLAGS
 
 
-def frame_of(args):
-    if args.dataset == "gear":
-        return [args.image_size, args.image_size]
-    return [args.image_height, args.image_width]
+def check_flags(ap, args):
+    """the refusals of this tool's own flags (``eval_views`` takes them too)"""
+    seg_cli.check_region_flags(ap, args)
+    if not args.max_false_alarms >= 0.0:
+        ap.error("--max_false_alarms must be at least 0")
+    seg_cli.check_tiling(ap, args)
 
 
 def parse_args(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    first = argparse.ArgumentParser(add_help=False)
-    first.add_argument("--dataset", required=True, choices=DATASETS)
-    dataset = first.parse_known_args(argv)[0].dataset          # its flags depend on the data set
-    ap = argparse.ArgumentParser(description="Defect detection curves over confidence of a segmentation checkpoint "
-                                             "(MI355X HIP path)")
-    ap.add_argument("--dataset", required=True, choices=DATASETS)
-    for name, kw in flags_of(dataset):
-        ap.add_argument(name, **kw)
-    args = ap.parse_args(argv)
-    if args.min_region_pixels < 1:
-        ap.error("--min_region_pixels must be at least 1")
-    if any(not 0.0 <= t <= 1.0 for t in args.coverage_thresholds):
-        ap.error("--coverage_thresholds must lie in 0..1")
-    if not args.max_false_alarms >= 0.0:
-        ap.error("--max_false_alarms must be at least 0")
-    if args.tiled and dataset != "gear":
-        ap.error("--tiled needs --dataset gear: KolektorSDD's masks are bitmaps, there is no full-resolution loader")
-    if args.tile is None:
-        args.tile = frame_of(args)
-    if min(args.tile) < 1:
-        ap.error("--tile sides must be positive")
-    if args.min_overlap < 0 or (args.tiled and args.min_overlap >= min(args.tile)):
-        ap.error("--min_overlap must be at least 0 and, with --tiled, smaller than both tile sides")
+    ap, args = seg_cli.parse_dataset_args(argv, "Defect detection curves over confidence of a segmentation checkpoint "
+                                                "(MI355X HIP path)", flags_of)
+    check_flags(ap, args)
     return args
-
-
-def match_frames(model, batches, num_classes, min_pixels):
-    """Eval-mode pass over (images, masks, paths) device batches: the matcher's result and the paths."""
-    import torch
-    from .evaluation import DetectionMatcher
-    from .sheets import seg_confidence
-    model.eval()
-    matcher, paths = DetectionMatcher(num_classes, min_pixels), []
-    with torch.no_grad():
-        for images, masks, batch_paths in batches:
-            labels, conf = seg_confidence(model(images))
-            matcher.update(labels, conf, masks)
-            paths.extend(batch_paths)
-    return matcher.compute(), paths
-
-
-def match_tiled(predictor, loader, num_classes, min_pixels, device):
-    """Every image of a raw Gear loader at its own size, the way ``predict_tiled`` predicts and
-    ``train_gear_crops.validate_tiled`` validates: the matcher's result and the paths."""
-    import torch
-    from .augment import color_jitter_normalize_u8
-    from .crops import full_resolution_masks
-    from .evaluation import DetectionMatcher
-    matcher, all_paths = DetectionMatcher(num_classes, min_pixels), []
-    with torch.no_grad():
-        for images, polys, sizes, paths in loader:
-            masks = full_resolution_masks(polys, sizes, device=device)
-            for i in range(len(sizes)):
-                frame = color_jitter_normalize_u8(images[i].to(device, non_blocking=True).unsqueeze(0))[0]
-                labels, conf, _plan = predictor(frame)
-                matcher.update(labels.unsqueeze(0), conf.unsqueeze(0), masks[i].unsqueeze(0))
-            all_paths.extend(paths)
-    return matcher.compute(), all_paths
 
 
 def main(argv=None):
     args = parse_args(argv)
-    from .train_gear import build_seg_model, require_gpu
-    from .utils import load_checkpoint
+    from .evaluation import DetectionMatcher
 
-    device = require_gpu(args)
-    cli = eval_regions._cli(args.dataset)
-    mode = "tiled" if args.tiled else "frame"
-    print("=" * 60 + f"\n{args.dataset.upper()} DATASET DETECTION EVALUATION ({mode})\n" + "=" * 60)
-    print(f"Device: {device}\nCheckpoint: {os.path.basename(args.checkpoint)}\nDataset: {args.split} split")
-    os.makedirs(args.save_dir, exist_ok=True)
-    loader, num_classes = cli._split_loader(args)
-    class_names = cli._class_names(loader.dataset, num_classes)
-    print(f"Number of classes: {num_classes}\nClass names: {class_names}\nSamples: {len(loader.dataset)}")
-    model = build_seg_model(args, num_classes, device)
-    epoch, loss = load_checkpoint(model, None, args.checkpoint, device)
-    print(f"Loaded checkpoint from epoch {epoch} with loss {loss:.4f}")
-
-    if args.tiled:
-        from .tiling import TiledPredictor
-        from .train_gear_crops import check_image_sizes
-        check_image_sizes([loader.dataset])
-        print(f"Tile: {args.tile}  min overlap: {args.min_overlap}")
-        predictor = TiledPredictor(model, args.tile, args.min_overlap, args.batch_size)
-        got, paths = match_tiled(predictor, loader, num_classes, args.min_region_pixels, device)
-    else:
-        got, paths = match_frames(model, cli._batches(args, loader, device), num_classes, args.min_region_pixels)
+    mode = seg_cli.mode_of(args)
+    device, cli, loader, num_classes, class_names, model = seg_cli.open_checkpoint_session(args, "DETECTION EVALUATION",
+                                                                                           mode)
+    matcher, paths = DetectionMatcher(num_classes, args.min_region_pixels), []
+    for labels, conf, masks, batch_paths in seg_cli.labelled_predictions(args, cli, loader, model, device):
+        matcher.update(labels, conf, masks)
+        paths.extend(batch_paths)
+    got = matcher.compute()
 
     results = seg_detection.detection_results(got["truth"], got["pred"], got["pairs"], got["images"], num_classes,
                                               args.coverage_thresholds, class_names, args.max_false_alarms)

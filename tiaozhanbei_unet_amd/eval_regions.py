@@ -17,42 +17,24 @@ min_region_pixels, image_level, thresholds {t: {overall, per_class}}, mean_cover
 """
 from __future__ import annotations
 
-import argparse
 import json
 import os
-import sys
 
-from . import seg_eval, seg_regions
+from . import seg_cli, seg_regions
 
-DATASETS = ("gear", "kolektorsdd")
-_NOT_HERE = ("--save_predictions", "--save_confusion_matrix", "--debug", "--debug_samples")
+DATASETS = seg_cli.DATASETS
 EXTRA_FLAGS = [("--min_region_pixels", dict(type=int, default=1)),
                ("--coverage_thresholds", dict(type=float, nargs="+", default=list(seg_regions.DEFAULT_THRESHOLDS)))]
 
 
-def _cli(dataset):
-    from . import eval_gear, eval_kolektorsdd
-    return {"gear": eval_gear, "kolektorsdd": eval_kolektorsdd}[dataset]
-
-
 def flags_of(dataset):
-    return [(n, kw) for n, kw in _cli(dataset).FLAGS if n not in _NOT_HERE] + EXTRA_FLAGS
+    return seg_cli.base_flags(dataset) + EXTRA_FLAGS
 
 
 def parse_args(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    first = argparse.ArgumentParser(add_help=False)
-    first.add_argument("--dataset", required=True, choices=DATASETS)
-    dataset = first.parse_known_args(argv)[0].dataset          # its flags depend on the data set
-    ap = argparse.ArgumentParser(description="Defect-level region metrics of a segmentation checkpoint (MI355X HIP path)")
-    ap.add_argument("--dataset", required=True, choices=DATASETS)
-    for name, kw in flags_of(dataset):
-        ap.add_argument(name, **kw)
-    args = ap.parse_args(argv)
-    if args.min_region_pixels < 1:
-        ap.error("--min_region_pixels must be at least 1")
-    if any(not 0.0 <= t <= 1.0 for t in args.coverage_thresholds):
-        ap.error("--coverage_thresholds must lie in 0..1")
+    ap, args = seg_cli.parse_dataset_args(argv, "Defect-level region metrics of a segmentation checkpoint (MI355X HIP path)",
+                                          flags_of)
+    seg_cli.check_region_flags(ap, args)
     return args
 
 
@@ -74,20 +56,7 @@ def match(model, batches, num_classes, min_pixels):
 
 def main(argv=None):
     args = parse_args(argv)
-    from .train_gear import build_seg_model, require_gpu
-    from .utils import load_checkpoint
-
-    device = require_gpu(args)
-    cli = _cli(args.dataset)
-    print("=" * 60 + f"\n{args.dataset.upper()} DATASET REGION EVALUATION\n" + "=" * 60)
-    print(f"Device: {device}\nCheckpoint: {os.path.basename(args.checkpoint)}\nDataset: {args.split} split")
-    os.makedirs(args.save_dir, exist_ok=True)
-    loader, num_classes = cli._split_loader(args)
-    class_names = cli._class_names(loader.dataset, num_classes)
-    print(f"Number of classes: {num_classes}\nClass names: {class_names}\nSamples: {len(loader.dataset)}")
-    model = build_seg_model(args, num_classes, device)
-    epoch, loss = load_checkpoint(model, None, args.checkpoint, device)
-    print(f"Loaded checkpoint from epoch {epoch} with loss {loss:.4f}")
+    device, cli, loader, num_classes, class_names, model = seg_cli.open_checkpoint_session(args, "REGION EVALUATION")
 
     got, paths, width = match(model, cli._batches(args, loader, device), num_classes, args.min_region_pixels)
     results = seg_regions.region_metrics(got["truth"], got["pred"], got["images"], num_classes,

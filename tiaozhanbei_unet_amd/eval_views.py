@@ -21,48 +21,32 @@ alarms.  Prints the comparison as a two-column table.  The numbers describe the 
 """
 from __future__ import annotations
 
-import argparse
 import json
 import os
-import sys
 
-from . import eval_detection, seg_detection
+from . import eval_detection, seg_cli, seg_detection
 from . import views as V
 from .predict_views import VIEW_FLAGS, check_views
 
-DATASETS = eval_detection.DATASETS
+DATASETS = seg_cli.DATASETS
 
 
 def flags_of(dataset):
     return eval_detection.flags_of(dataset) + VIEW_FLAGS
 
 
-def parse_args(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    ap = argparse.ArgumentParser(description="A view ensemble against the single view: detection figures of both "
-                                             "(MI355X HIP path)")
-    ap.add_argument("--dataset", required=True, choices=DATASETS)
-    first = argparse.ArgumentParser(add_help=False)
-    first.add_argument("--dataset", required=True, choices=DATASETS)
-    dataset = first.parse_known_args(argv)[0].dataset
+def _gear_flags(dataset):
     if dataset != "gear":
-        ap.error("eval_views needs --dataset gear: KolektorSDD's masks are bitmaps, there is no full-resolution loader")
-    for name, kw in flags_of(dataset):
-        ap.add_argument(name, **kw)
-    args = ap.parse_args(argv)
+        raise ValueError("eval_views needs --dataset gear: KolektorSDD's masks are bitmaps, there is no full-resolution "
+                         "loader")
+    return flags_of(dataset)
+
+
+def parse_args(argv=None):
+    ap, args = seg_cli.parse_dataset_args(argv, "A view ensemble against the single view: detection figures of both "
+                                                "(MI355X HIP path)", _gear_flags)
     args.tiled = True
-    if args.min_region_pixels < 1:
-        ap.error("--min_region_pixels must be at least 1")
-    if any(not 0.0 <= t <= 1.0 for t in args.coverage_thresholds):
-        ap.error("--coverage_thresholds must lie in 0..1")
-    if not args.max_false_alarms >= 0.0:
-        ap.error("--max_false_alarms must be at least 0")
-    if args.tile is None:
-        args.tile = eval_detection.frame_of(args)
-    if min(args.tile) < 1:
-        ap.error("--tile sides must be positive")
-    if not 0 <= args.min_overlap < min(args.tile):
-        ap.error("--min_overlap must be at least 0 and smaller than both tile sides")
+    eval_detection.check_flags(ap, args)
     check_views(ap, args)
     plain = (1.0, 0, 0)
     if plain not in args.views:
@@ -76,27 +60,23 @@ def match_views(ensemble, loader, num_classes, min_pixels, device):
     the matcher's result from the ensemble, per predicted region of the latter its mean view agreement, the paths)."""
     import numpy as np
     import torch
-    from .crops import full_resolution_masks
     from .evaluation import DetectionMatcher, describe_class_regions
     from .sheets import seg_confidence
     single, merged = DetectionMatcher(num_classes, min_pixels), DetectionMatcher(num_classes, min_pixels)
     agree, all_paths, n_views = [], [], len(ensemble.views)
     flips = [(fx, fy) for _s, fx, fy in ensemble.views]
     with torch.no_grad():
-        for images, polys, sizes, paths in loader:
-            masks = full_resolution_masks(polys, sizes, device=device)
-            for i in range(len(sizes)):
-                image = images[i].to(device, non_blocking=True)
-                frame_hw = (int(image.shape[0]), int(image.shape[1]))
-                logits, _plan = ensemble.view_logits(image, frame_hw)
-                labels, conf = seg_confidence(logits[0][None])
-                single.update(labels, conf, masks[i].unsqueeze(0))
-                labels, conf, agreement = V.merge_views(logits, flips, frame_hw)
-                base = merged.images
-                merged.update(labels[None], conf[None], masks[i].unsqueeze(0))
-                agree.append(describe_class_regions(labels[None], num_classes, agreement[None].float() / float(n_views),
-                                                    min_pixels, image_base=base))
-            all_paths.extend(paths)
+        for image, mask, path in seg_cli.full_resolution_images(loader, device):
+            frame_hw = (int(image.shape[0]), int(image.shape[1]))
+            logits, _plan = ensemble.view_logits(image, frame_hw)
+            labels, conf = seg_confidence(logits[0][None])
+            single.update(labels, conf, mask[None])
+            labels, conf, agreement = V.merge_views(logits, flips, frame_hw)
+            base = merged.images
+            merged.update(labels[None], conf[None], mask[None])
+            agree.append(describe_class_regions(labels[None], num_classes, agreement[None].float() / float(n_views),
+                                                min_pixels, image_base=base))
+            all_paths.append(path)
     got = merged.compute()
     rec = np.concatenate(agree) if agree else np.zeros((0, 12), np.int64)
     if rec.shape != got["pred"].shape or (rec[:, :4] != got["pred"][:, :4]).any():
@@ -147,29 +127,13 @@ def format_comparison(comparison, agreement, n_views):
 
 def main(argv=None):
     args = parse_args(argv)
-    from .train_gear import build_seg_model, require_gpu
-    from .utils import load_checkpoint
 
-    device = require_gpu(args)
-    from . import eval_regions
-    from .tiling import TiledPredictor
-    from .train_gear_crops import check_image_sizes
-    cli = eval_regions._cli(args.dataset)
-    print("=" * 60 + f"\n{args.dataset.upper()} DATASET VIEW-ENSEMBLE EVALUATION\n" + "=" * 60)
-    print(f"Device: {device}\nCheckpoint: {os.path.basename(args.checkpoint)}\nDataset: {args.split} split")
-    os.makedirs(args.save_dir, exist_ok=True)
-    loader, num_classes = cli._split_loader(args)
+    device, _cli, loader, num_classes, class_names, model = seg_cli.open_checkpoint_session(args, "VIEW-ENSEMBLE EVALUATION")
     if not 2 <= num_classes <= 8:
         raise SystemExit(f"{num_classes} classes: the merge kernel takes 2 to 8")
-    class_names = cli._class_names(loader.dataset, num_classes)
-    print(f"Number of classes: {num_classes}\nClass names: {class_names}\nSamples: {len(loader.dataset)}")
-    model = build_seg_model(args, num_classes, device)
-    epoch, loss = load_checkpoint(model, None, args.checkpoint, device)
-    print(f"Loaded checkpoint from epoch {epoch} with loss {loss:.4f}")
-    check_image_sizes([loader.dataset])
-    print(f"Tile: {args.tile}  min overlap: {args.min_overlap}")
+    predictor = seg_cli.tiled_predictor(args, loader, model)
     print(f"Views: {len(args.views)} (scales {args.view_scales}, flips {args.view_flips})")
-    ensemble = V.ViewEnsemble(TiledPredictor(model, args.tile, args.min_overlap, args.batch_size), args.views)
+    ensemble = V.ViewEnsemble(predictor, args.views)
     got_single, got_merged, agreement, _paths = match_views(ensemble, loader, num_classes, args.min_region_pixels, device)
 
     sides = {}

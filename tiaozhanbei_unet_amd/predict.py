@@ -26,16 +26,15 @@ the numbers are what the given checkpoint predicts.
 from __future__ import annotations
 
 import argparse
-import json
 import os
 
-from . import defects
+from . import defects, seg_cli
+from .seg_cli import HEAD_WEIGHT  # noqa: F401  (its home; importable from here as before)
 
 TASKS = {"gear": {"image_size": (512, 512), "class_names": ["background", "pitting", "spalling", "scrape"],
                   "palette": "index"},
          "kolektorsdd": {"image_size": (1024, 512), "class_names": ["background", "defect_type_1", "defect_type_2"],
                          "palette": "scaled"}}
-HEAD_WEIGHT = "outc.conv.weight"                         # [num_classes, 64, 1, 1] of UNet and SegmentationUNet
 
 FLAGS = [("--task", dict(type=str, required=True, choices=sorted(TASKS))),
          ("--checkpoint", dict(type=str, required=True)),
@@ -68,12 +67,7 @@ def parse_args(argv=None):
         args.image_size = list(TASKS[args.task]["image_size"])
     if min(args.image_size) < 1:
         ap.error("--image_size must be positive")
-    if args.min_region_pixels < 1:
-        ap.error("--min_region_pixels must be at least 1")
-    if not 0.0 <= args.min_confidence <= 1.0:
-        ap.error("--min_confidence must lie in 0..1")
-    if args.batch_size < 1:
-        ap.error("--batch_size must be at least 1")
+    seg_cli.check_predict_flags(ap, args)
     return args
 
 
@@ -126,55 +120,22 @@ def predict_batches(model, loader, size, num_classes, min_pixels, device):
             yield idx, sizes, x, labels, means.tolist(), records
 
 
-def _save_mask(labels_u8, palette_bytes, path):
-    from PIL import Image
-    im = Image.fromarray(labels_u8)                    # mode L; the palette makes it P
-    im.putpalette(palette_bytes)
-    im.save(path)
+def image_loader(paths, batch_size, num_workers):
+    """``collate_images`` batches of ``ImageFiles(paths)``, in order"""
+    from torch.utils.data import DataLoader
+    return DataLoader(ImageFiles(paths), batch_size=batch_size, shuffle=False, num_workers=num_workers, pin_memory=True,
+                      collate_fn=collate_images)
 
 
 def main(argv=None):
     args = parse_args(argv)
-    from .train_gear import build_seg_model, require_gpu
-    device = require_gpu(args)
-    import torch
-    from torch.utils.data import DataLoader
-    from . import augment, sheets
-    from .seg_visualize import GUTTER, OVERLAY_ALPHA, save_png
-
     task = TASKS[args.task]
-    paths = defects.list_images(args.input)
-    if not paths:
-        raise SystemExit(f"no image files below {args.input}")
-    names = defects.output_names(paths, args.input)
-    ckpt = torch.load(args.checkpoint, map_location=device, weights_only=True)
-    state = ckpt["model_state_dict"]
-    if args.num_classes is None:
-        if HEAD_WEIGHT not in state:
-            raise SystemExit(f"{args.checkpoint} has no {HEAD_WEIGHT}: pass --num_classes")
-        args.num_classes = int(state[HEAD_WEIGHT].shape[0])
-    num_classes = args.num_classes
-    if not 2 <= num_classes <= 8:
-        raise SystemExit(f"{num_classes} classes: the confidence kernel takes 2 to 8")
-    class_names = defects.class_names_for(task["class_names"], num_classes, args.class_names)
-    unknown = sorted(set(args.reject_classes or ()) - set(class_names))
-    if unknown:
-        raise SystemExit(f"--reject_classes {unknown}: the classes are {class_names}")
-    print("=" * 60 + f"\n{args.task.upper()} PREDICTION\n" + "=" * 60)
-    print(f"Device: {device}\nCheckpoint: {os.path.basename(args.checkpoint)}\nImages: {len(paths)}")
-    print(f"Number of classes: {num_classes}\nClass names: {class_names}")
-    model = build_seg_model(args, num_classes, device)
-    model.load_state_dict(state)
+    device, paths, names, num_classes, class_names, model = seg_cli.open_prediction(args, task, "PREDICTION", "confidence")
+    import numpy as np
+    from . import augment
 
-    mask_dir = os.path.join(args.output_dir, "masks")
-    os.makedirs(mask_dir, exist_ok=True)
-    overlay_dir = os.path.join(args.output_dir, "overlays")
-    if args.save_overlays:
-        os.makedirs(overlay_dir, exist_ok=True)
-    host_palette = sheets.class_palette(num_classes, task["palette"])
-    palette, palette_bytes = host_palette.to(device), host_palette.numpy().tobytes()
-    loader = DataLoader(ImageFiles(paths), batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers,
-                        pin_memory=True, collate_fn=collate_images)
+    mask_dir, overlay_dir, palette, palette_bytes = seg_cli.prediction_outputs(args, task, num_classes, device)
+    loader = image_loader(paths, args.batch_size, args.num_workers)
     originals, frame_means, records = [None] * len(paths), [None] * len(paths), []
     for idx, sizes, x, labels, means, rec in predict_batches(model, loader, args.image_size, num_classes,
                                                              args.min_region_pixels, device):
@@ -187,13 +148,11 @@ def main(argv=None):
                 mask = host[k]
             else:
                 mask = augment.resize_nearest_u8(labels[k:k + 1].unsqueeze(-1), *sizes[k])[0, :, :, 0].cpu().numpy()
-            _save_mask(mask, palette_bytes, os.path.join(mask_dir, names[i] + ".png"))
+            seg_cli.save_mask(mask, palette_bytes, os.path.join(mask_dir, names[i] + ".png"))
             if args.save_overlays:
-                sheet = sheets.render_seg_sheet(x[k:k + 1].float(), [("image",), ("overlay", labels[k:k + 1], OVERLAY_ALPHA)],
-                                                gutter=GUTTER, palette=palette)
-                save_png(sheet, os.path.join(overlay_dir, names[i] + ".png"))
+                seg_cli.save_overlay(x[k:k + 1].float(), labels[k:k + 1], palette,
+                                     os.path.join(overlay_dir, names[i] + ".png"))
 
-    import numpy as np
     entries = defects.defect_entries(np.concatenate(records), class_names, args.image_size, originals,
                                      args.min_confidence, args.reject_classes)
     images = []
@@ -203,18 +162,7 @@ def main(argv=None):
             pixels[d["class_name"]] += d["pixels"]
         images.append({"image_path": paths[i], "name": names[i], "original_size": list(originals[i]),
                        "mean_confidence": frame_means[i], "defect_pixels": pixels, **e})
-    summary = defects.summarize(entries, class_names)
-    out_path = os.path.join(args.output_dir, "predictions.json")
-    with open(out_path, "w") as f:
-        json.dump({"args": vars(args), "class_names": class_names, "frame_size": list(args.image_size), "images": images,
-                   "summary": summary}, f, indent=2)
-    for im in images:
-        found = ", ".join(f"{d['class_name']} {d['pixels']} px @ {d['mean_confidence']:.2f}" for d in im["defects"][:4])
-        more = f" (+{len(im['defects']) - 4} more)" if len(im["defects"]) > 4 else ""
-        print(f"{im['decision']:>6}  {im['name']}: {found or 'no defects'}{more}")
-    print(f"Images: {summary['images']}  rejected: {summary['rejected']}  defects: {summary['defects']}")
-    print(f"Predictions saved to: {out_path}")
-    return out_path
+    return seg_cli.write_predictions(args, class_names, images, frame_size=args.image_size)
 
 
 if __name__ == "__main__":

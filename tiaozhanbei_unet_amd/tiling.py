@@ -145,7 +145,8 @@ class TiledPredictor:
                 out[k:k + z.shape[0]] = z
         return out
 
-    def __call__(self, frame):
+    def _planned_logits(self, frame):
+        """(tile logits (T, C, th, tw), (H, W), plan) of a frame: the tiles placed, gathered and run through the model"""
         if not torch.is_tensor(frame) or frame.dim() != 3:
             raise ValueError("TiledPredictor: a frame is a (3, H, W) tensor")
         h, w = int(frame.shape[1]), int(frame.shape[2])
@@ -153,22 +154,24 @@ class TiledPredictor:
         th, tw = min(self.tile_hw[0], h), min(self.tile_hw[1], w)
         oy = plan_axis(h, th, min(self.min_overlap, th - 1))
         ox = plan_axis(w, tw, min(self.min_overlap, tw - 1))
-        ramp = [default_ramp(oy, th), default_ramp(ox, tw)]
-        tiles = gather_tiles(frame.float(), th, tw, oy, ox)
-        labels, conf = blend_tiles(self.tile_logits(tiles), oy, ox, (h, w), ramp=ramp)
-        return labels, conf, {"tile": [th, tw], "origins_y": oy, "origins_x": ox, "ramp": ramp}
+        plan = {"tile": [th, tw], "origins_y": oy, "origins_x": ox, "ramp": [default_ramp(oy, th), default_ramp(ox, tw)]}
+        return self.tile_logits(gather_tiles(frame.float(), th, tw, oy, ox)), (h, w), plan
+
+    def __call__(self, frame):
+        logits, frame_hw, plan = self._planned_logits(frame)
+        labels, conf = blend_tiles(logits, plan["origins_y"], plan["origins_x"], frame_hw, ramp=plan["ramp"])
+        return labels, conf, plan
+
+    def blended(self, frame):
+        """(labels, conf, logits float32 (C, H, W), plan): ``__call__``'s results and the blended logits they are taken
+        from, by the same plan and in the same single launch (``blend_tiles(..., blended=True)``), for whoever needs more
+        than the maximum.  ``sheets.seg_confidence`` of the logits gives the labels and the confidence bit for bit."""
+        logits, frame_hw, plan = self._planned_logits(frame)
+        labels, conf, mixed = blend_tiles(logits, plan["origins_y"], plan["origins_x"], frame_hw, ramp=plan["ramp"],
+                                          blended=True)
+        return labels, conf, mixed, plan
 
     def blended_logits(self, frame):
-        """(logits float32 (C, H, W), plan): the blended logits that ``__call__`` takes its labels and confidence from, by
-        the same plan (``blend_tiles(..., blended=True)``), for whoever needs more than the maximum.
-        ``sheets.seg_confidence`` of them gives ``__call__``'s labels and confidence bit for bit."""
-        if not torch.is_tensor(frame) or frame.dim() != 3:
-            raise ValueError("TiledPredictor: a frame is a (3, H, W) tensor")
-        h, w = int(frame.shape[1]), int(frame.shape[2])
-        th, tw = min(self.tile_hw[0], h), min(self.tile_hw[1], w)
-        oy = plan_axis(h, th, min(self.min_overlap, th - 1))
-        ox = plan_axis(w, tw, min(self.min_overlap, tw - 1))
-        ramp = [default_ramp(oy, th), default_ramp(ox, tw)]
-        tiles = gather_tiles(frame.float(), th, tw, oy, ox)
-        _labels, _conf, mixed = blend_tiles(self.tile_logits(tiles), oy, ox, (h, w), ramp=ramp, blended=True)
-        return mixed, {"tile": [th, tw], "origins_y": oy, "origins_x": ox, "ramp": ramp}
+        """(logits float32 (C, H, W), plan) of ``blended``"""
+        _labels, _conf, mixed, plan = self.blended(frame)
+        return mixed, plan

@@ -75,40 +75,22 @@ def check_image_sizes(datasets):
                                  f"and {MAX_IMAGE_SIDE} high (the full-resolution mask kernel's limits)")
 
 
-def tiled_logits(predictor, frame):
-    """(labels uint8 (H, W), blended logits float32 (C, H, W)) of a normalised DEVICE frame (3, H, W): the plan, the
-    gather and the blend of ``TiledPredictor.__call__``, keeping the blended logits."""
-    from .tiling import blend_tiles, default_ramp, gather_tiles, plan_axis
-    h, w = int(frame.shape[1]), int(frame.shape[2])
-    th, tw = min(predictor.tile_hw[0], h), min(predictor.tile_hw[1], w)
-    oy = plan_axis(h, th, min(predictor.min_overlap, th - 1))
-    ox = plan_axis(w, tw, min(predictor.min_overlap, tw - 1))
-    ramp = [default_ramp(oy, th), default_ramp(ox, tw)]
-    logits = predictor.tile_logits(gather_tiles(frame.float(), th, tw, oy, ox))
-    labels, _conf, mixed = blend_tiles(logits, oy, ox, (h, w), ramp=ramp, blended=True)
-    return labels, mixed
-
-
 def validate_tiled(model, criterion, loader, predictor, num_classes, device):
     """Validation the way ``predict_tiled`` predicts: image by image at its own size.  The loss is the unweighted mean of
     the per-image losses on the blended logits, the metrics those of the blended label maps."""
     import torch
-    from .augment import color_jitter_normalize_u8
-    from .crops import full_resolution_masks
     from .metrics import SegmentationMetrics
+    from .seg_cli import full_resolution_images, normalized_frame
     metrics = SegmentationMetrics(num_classes)
     total = torch.zeros((), dtype=torch.float64, device=device)
     count = 0
     with torch.no_grad():
-        for images, polys, sizes, _paths in loader:
-            masks = full_resolution_masks(polys, sizes, device=device)
-            for i in range(len(sizes)):
-                frame = color_jitter_normalize_u8(images[i].to(device, non_blocking=True).unsqueeze(0))[0]
-                labels, mixed = tiled_logits(predictor, frame)
-                target = masks[i].unsqueeze(0).long()
-                total += criterion(mixed.unsqueeze(0), target).detach().double()
-                metrics.update(labels.unsqueeze(0), target)
-                count += 1
+        for image, mask, _path in full_resolution_images(loader, device):
+            labels, _conf, mixed, _plan = predictor.blended(normalized_frame(image))
+            target = mask[None].long()
+            total += criterion(mixed[None], target).detach().double()
+            metrics.update(labels[None], target)
+            count += 1
     return {"loss": float(total) / max(count, 1), "metrics": metrics.compute_all_metrics()}
 
 
