@@ -560,6 +560,33 @@ int32_t unet_describe_class_regions(const uint8_t* classes, const int32_t* regio
                                     int64_t capacity, int64_t* record_count, void* workspace, size_t workspace_bytes,
                                     void* stream);
 
+/* Shape records of class regions (no reference counterpart; csrc/shapes.hip, restated in numpy by tests/_shapes_ref.py):
+ * what a defect's length, width, orientation, perimeter and holes are computed from.  region and sizes are what
+ * unet_label_class_regions makes (region[g] - 1 = the root of pixel g, 0 = background).  direction_table: HOST int32
+ * [directions][2], the vectors (c_k, s_k), read during the call and passed to the kernels by value; every component in
+ * -16384..16384 (else UNET_ERR_BAD_ARG).  Every region with size >= min_pixels (>= 1) yields one record of
+ * 11 + 2 directions int64 {image_base + image, root index y * w + x, size, sum_xx, sum_yy, sum_xy, q1, q2, qd, q3, q4,
+ * pmin_0 .. pmin_{D-1}, pmax_0 .. pmax_{D-1}}: the sums of x x, y y and x y over the region's pixels in frame
+ * coordinates; the bit-quad counts (Gray 1971) over all (h + 1)(w + 1) 2 x 2 windows of the region's own mask padded
+ * with non-members -- windows with one member, two edge-adjacent, two diagonal, three and four; a pixel of another
+ * region or class or outside the frame is a non-member --; and the minimum and maximum of x c_k + y s_k over the
+ * region's pixels.  Slots, record_count (ADDED to: zero it first), capacity and the record order are those of
+ * unet_describe_class_regions: with equal min_pixels and image_base the two calls keep the same regions, and sorted by
+ * (image, root index) their records align.  Two launches: the root pixels take their slots and write their own pixel's
+ * values, leaving the slot in the workspace (all of it is written); every other class pixel adds its moments and the
+ * windows it is the first member of (summed per thread, wave and block first) with int64 atomicAdd, and, if one of its 8
+ * neighbours is a non-member, its projections with atomicMin / atomicMax (reduced across the wave first, and only
+ * issued where they improve on the record).  Integers only: apart from the record order the output is a function of the
+ * inputs alone.  n < 65536, n h w <= 2^31 - 1, h and w <= 16384 (sum_xx <= 2^56, |p| < 2^30), directions even in
+ * 2..32, image_base + n and capacity <= 2^31 - 1, else UNET_ERR_UNSUPPORTED before any launch (and the workspace query
+ * returns 0); a NULL pointer or min_pixels < 1 is UNET_ERR_BAD_ARG.  Allocates nothing, does not synchronise. */
+size_t unet_measure_class_regions_workspace(int64_t n, int64_t h, int64_t w, int32_t directions);
+int32_t unet_measure_class_regions(const int32_t* region, const int32_t* sizes, int64_t n, int64_t h, int64_t w,
+                                   int32_t min_pixels, int32_t image_base,
+                                   const int32_t* direction_table /* host [directions][2] */, int32_t directions,
+                                   int64_t* records, int64_t capacity, int64_t* record_count, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
 /* Outline accuracy of label maps (no reference counterpart): an exact squared Euclidean distance transform of the class
  * boundaries, and one record per (image, class) of how far the outlines of two maps lie apart (csrc/distance.hip).
  * classes / truth / pred: uint8 [n][h][w] as unet_label_class_regions takes them; a pixel has class c iff its value is c,

@@ -164,6 +164,8 @@ SIGNATURES = {
     "unet_region_pairs": (_i, [_p, _p, _l, _l, _l, _l, _i, _p, _l, _p, _p, _p, _z, _p]),
     "unet_describe_class_regions_workspace": (_z, [_l, _l, _l, _i]),
     "unet_describe_class_regions": (_i, [_p, _p, _p, _p, _l, _l, _l, _i, _i, _i, _p, _l, _p, _p, _z, _p]),
+    "unet_measure_class_regions_workspace": (_z, [_l, _l, _l, _i]),
+    "unet_measure_class_regions": (_i, [_p, _p, _l, _l, _l, _i, _i, _p, _i, _p, _l, _p, _p, _z, _p]),
     "unet_boundary_distance_sq_workspace": (_z, [_l, _l, _l, _i]),
     "unet_boundary_distance_sq": (_i, [_p, _l, _l, _l, _i, _p, _p, _z, _p]),
     "unet_boundary_stats": (_i, [_p, _p, _p, _p, _l, _l, _l, _i, _p, _i, _i, _i, _p, _p, _p]),

@@ -424,6 +424,19 @@ def describe_class_regions(labels, num_classes, conf=None, min_pixels=1, image_b
     throughout, so the array is a function of the inputs alone).  Two host reads: the region counts, which bound the
     records from above and size the buffer, and the records with their count."""
     import numpy as np
+    t, cf, c, min_pixels, image_base = _describe_args("describe_class_regions", labels, num_classes, conf, min_pixels,
+                                                      image_base)
+    region, sizes, counts = label_class_regions(t, c)
+    cap = int(counts.sum())                            # every record is a region: there cannot be more
+    if cap == 0:
+        return np.zeros((0, len(DEFECT_FIELDS)), np.int64)
+    out = _describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap)
+    return _defect_records(out.cpu().numpy(), cap, "describe_class_regions")
+
+
+def _describe_args(what, labels, num_classes, conf, min_pixels, image_base):
+    """(uint8 maps, fp32 conf or None, num_classes, min_pixels, image_base) of ``describe_class_regions``' arguments,
+    refused as it refuses them; nothing is launched"""
     _require_cuda(labels)
     c, min_pixels, image_base = int(num_classes), int(min_pixels), int(image_base)
     lib = L.lib()
@@ -431,27 +444,22 @@ def describe_class_regions(labels, num_classes, conf=None, min_pixels=1, image_b
         n, h, w = labels.shape
         nbytes = lib.unet_describe_class_regions_workspace(n, h, w, c) if 0 <= c < 2 ** 31 else 0
         if nbytes == 0 or image_base + n >= 2 ** 31:
-            raise _class_regions_error("describe_class_regions", n, h, w, num_classes)
-    t = _class_maps(labels, "describe_class_regions")
+            raise _class_regions_error(what, n, h, w, num_classes)
+    t = _class_maps(labels, what)
     n, h, w = t.shape
     if min_pixels < 1:
-        raise ValueError(f"describe_class_regions: min_pixels {min_pixels} is below 1")
+        raise ValueError(f"{what}: min_pixels {min_pixels} is below 1")
     if image_base < 0:
-        raise ValueError(f"describe_class_regions: image_base {image_base} is negative")
+        raise ValueError(f"{what}: image_base {image_base} is negative")
     cf = None
     if conf is not None:
         if not torch.is_tensor(conf) or not conf.is_floating_point() or tuple(conf.shape) != (n, h, w):
-            raise ValueError(f"describe_class_regions: conf is a float tensor {(n, h, w)}, like the labels")
+            raise ValueError(f"{what}: conf is a float tensor {(n, h, w)}, like the labels")
         _require_cuda(conf)
         if conf.device != t.device:
-            raise ValueError("describe_class_regions: labels and conf share one device")
+            raise ValueError(f"{what}: labels and conf share one device")
         cf = conf.detach().float().contiguous()
-    region, sizes, counts = label_class_regions(t, c)
-    cap = int(counts.sum())                            # every record is a region: there cannot be more
-    if cap == 0:
-        return np.zeros((0, len(DEFECT_FIELDS)), np.int64)
-    out = _describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap)
-    return _defect_records(out.cpu().numpy(), cap, "describe_class_regions")
+    return t, cf, c, min_pixels, image_base
 
 
 def _describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap):
@@ -477,6 +485,113 @@ def _defect_records(host, cap, what):
         raise RuntimeError(f"{what}: more records than regions")      # cannot happen
     rec = host[:-1].reshape(cap, len(DEFECT_FIELDS))[:k]
     return np.ascontiguousarray(rec[np.lexsort((rec[:, 2], rec[:, 0]))])
+
+
+from .defects import SHAPE_HEAD, direction_table  # noqa: E402  (numpy only: the host side of these records)
+
+
+def shape_fields(directions=32):
+    """the field names of a shape record with ``directions`` directions: SHAPE_HEAD, pmin_k, pmax_k"""
+    d = int(directions)
+    return SHAPE_HEAD + tuple(f"pmin_{k}" for k in range(d)) + tuple(f"pmax_{k}" for k in range(d))
+
+
+SHAPE_FIELDS = shape_fields(32)
+
+
+def _measure_args(what, labels, min_pixels, image_base, directions):
+    """(direction table int32 [D, 2], D) once the shape, ``directions``, ``min_pixels`` and ``image_base`` are known to be
+    ones unet_measure_class_regions takes; nothing is launched"""
+    d, min_pixels, image_base = int(directions), int(min_pixels), int(image_base)
+    if labels.dim() == 3 and labels.numel():
+        n, h, w = labels.shape
+        nbytes = L.lib().unet_measure_class_regions_workspace(n, h, w, d) if -2 ** 31 <= d < 2 ** 31 else 0
+        if nbytes == 0 or image_base + n >= 2 ** 31:
+            raise RuntimeError(f"{what}: {n} x {h} x {w} maps with {directions} directions are not supported (n < 65536, "
+                               "at most 2^31 - 1 pixels, sides up to 16384, an even number of 2..32 directions)")
+    if min_pixels < 1:
+        raise ValueError(f"{what}: min_pixels {min_pixels} is below 1")
+    if image_base < 0:
+        raise ValueError(f"{what}: image_base {image_base} is negative")
+    return direction_table(d), d
+
+
+def measure_class_regions(labels, num_classes, min_pixels=1, image_base=0, directions=32):
+    """One shape record per class region of integer label maps [N, H, W] that has at least ``min_pixels`` pixels: an
+    int64 [K, 11 + 2 directions] numpy array of ``shape_fields(directions)`` (SHAPE_FIELDS at the default 32), sorted by
+    (image, root).  The regions, ``image``, ``root`` and ``size`` are ``describe_class_regions``': with equal arguments the
+    rows of the two align one to one.  ``sum_xx`` / ``sum_yy`` / ``sum_xy``: sums of x x, y y, x y over the region's
+    pixels in frame coordinates; ``q1, q2, qd, q3, q4``: its bit-quad counts (2 x 2 windows of the region's own mask with
+    one member, two edge-adjacent, two diagonal, three, four); ``pmin_k`` / ``pmax_k``: the extremes of x c_k + y s_k for
+    ``defects.direction_table(directions)``.  ``defects.shape_measures`` turns a record into lengths
+    (unet_measure_class_regions; integers throughout, so the array is a function of the inputs alone).  Sides up to
+    16384, an even number of 2..32 directions.  Two host reads: the region counts and the records with their count."""
+    import numpy as np
+    _require_cuda(labels)
+    c = int(num_classes)
+    if labels.dim() == 3 and labels.numel():
+        n, h, w = labels.shape
+        if (L.lib().unet_label_class_regions_workspace(n, h, w, c) if 0 <= c < 2 ** 31 else 0) == 0:
+            raise _class_regions_error("measure_class_regions", n, h, w, num_classes)
+    table, d = _measure_args("measure_class_regions", labels, min_pixels, image_base, directions)
+    t = _class_maps(labels, "measure_class_regions")
+    region, sizes, counts = label_class_regions(t, c)
+    cap = int(counts.sum())
+    if cap == 0:
+        return np.zeros((0, len(SHAPE_HEAD) + 2 * d), np.int64)
+    out = _measure_labelled(region, sizes, int(min_pixels), int(image_base), cap, table)
+    return _sorted_records(out.cpu().numpy(), cap, len(SHAPE_HEAD) + 2 * d, 1, "measure_class_regions")
+
+
+def _measure_labelled(region, sizes, min_pixels, image_base, cap, table):
+    """unet_measure_class_regions on labelled maps: the DEVICE int64 buffer of ``cap`` records of
+    ``shape_fields(len(table))`` followed by their count."""
+    import numpy as np
+    n, h, w = region.shape
+    lib = L.lib()
+    table = np.ascontiguousarray(table, np.int32)
+    d = table.shape[0]
+    out = torch.empty(cap * (len(SHAPE_HEAD) + 2 * d) + 1, dtype=torch.int64, device=region.device)
+    records, count = out[:-1], out[-1:]
+    count.zero_()
+    ws = _workspace(lib.unet_measure_class_regions_workspace(n, h, w, d), region.device)
+    L.check(lib.unet_measure_class_regions(_ptr(region), _ptr(sizes), n, h, w, min_pixels, image_base,
+                                           table.ctypes.data, d, _ptr(records), cap, _ptr(count), _ptr(ws), ws.numel(),
+                                           _stream()), "unet_measure_class_regions")
+    return out
+
+
+def _sorted_records(host, cap, fields, root_field, what):
+    """the records of a ``cap * fields + 1`` buffer (the count last), sorted by (image, root)"""
+    import numpy as np
+    k = int(host[-1])
+    if k > cap:
+        raise RuntimeError(f"{what}: more records than regions")      # cannot happen
+    rec = host[:-1].reshape(cap, fields)[:k]
+    return np.ascontiguousarray(rec[np.lexsort((rec[:, root_field], rec[:, 0]))])
+
+
+def describe_and_measure_class_regions(labels, num_classes, conf=None, min_pixels=1, image_base=0, directions=32):
+    """(``describe_class_regions``' records, ``measure_class_regions``' records) of one labelling: the maps are labelled
+    once, both kernels run on that labelling, and the two record sets come to the host in one buffer, so the host reads
+    stay two (the region counts, then the records).  The rows of the two arrays align."""
+    import numpy as np
+    t, cf, c, min_pixels, image_base = _describe_args("describe_and_measure_class_regions", labels, num_classes, conf,
+                                                      min_pixels, image_base)
+    table, d = _measure_args("describe_and_measure_class_regions", t, min_pixels, image_base, directions)
+    fd, fs = len(DEFECT_FIELDS), len(SHAPE_HEAD) + 2 * d
+    region, sizes, counts = label_class_regions(t, c)
+    cap = int(counts.sum())
+    if cap == 0:
+        return np.zeros((0, fd), np.int64), np.zeros((0, fs), np.int64)
+    both = torch.cat([_describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap),
+                      _measure_labelled(region, sizes, min_pixels, image_base, cap, table)]).cpu().numpy()
+    what = "describe_and_measure_class_regions"
+    rec = _defect_records(both[:cap * fd + 1], cap, what)
+    shapes = _sorted_records(both[cap * fd + 1:], cap, fs, 1, what)
+    if len(rec) != len(shapes) or (rec[:, [0, 2, 3]] != shapes[:, :3]).any():
+        raise RuntimeError(f"{what}: the two record sets differ")      # cannot happen
+    return rec, shapes
 
 
 PAIR_FIELDS = ("image", "truth_root", "pred_root", "overlap")

@@ -22,6 +22,14 @@ per predicted 8-connected class region of at least ``--min_region_pixels`` pixel
 it has a defect of one of ``--reject_classes`` (default: every class but the background) whose mean confidence is at
 least ``--min_confidence``; defects below it stay listed with ``"counted": false``.  Nothing here claims any accuracy:
 the numbers are what the given checkpoint predicts.
+
+Build-only, off by default (``seg_cli.SHAPE_FLAGS``, shared with ``predict_tiled`` and ``predict_views``):
+``--measure_shapes`` adds a ``shape`` dict to every defect (``defects.shape_measures`` of the integer records of
+``evaluation.measure_class_regions``, csrc/shapes.hip: Feret length / width / angle, equivalent ellipse, perimeter,
+circularity, holes; lengths in the image's own pixels, and with ``--pixel_size MM`` in millimetres too);
+``--min_defect_length X`` / ``--min_defect_area X`` (mm and mm2 with ``--pixel_size``, image pixels otherwise; either implies
+``--measure_shapes``) make ``counted`` also require that length and that area, and a ``size_rules`` block records them.
+With none of the four nothing new is launched and every output byte is as before.
 """
 from __future__ import annotations
 
@@ -60,7 +68,7 @@ FLAGS = [("--task", dict(type=str, required=True, choices=sorted(TASKS))),
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Defects with boxes and confidence from unlabelled images (MI355X HIP path)")
-    for name, kw in FLAGS:
+    for name, kw in FLAGS + seg_cli.SHAPE_FLAGS:
         ap.add_argument(name, **kw)
     args = ap.parse_args(argv)
     if args.image_size is None:
@@ -68,6 +76,7 @@ def parse_args(argv=None):
     if min(args.image_size) < 1:
         ap.error("--image_size must be positive")
     seg_cli.check_predict_flags(ap, args)
+    seg_cli.check_shape_flags(ap, args)
     return args
 
 
@@ -96,15 +105,16 @@ def collate_images(samples):
     return (torch.stack(imgs) if same else list(imgs)), list(idx)
 
 
-def predict_batches(model, loader, size, num_classes, min_pixels, device):
+def predict_batches(model, loader, size, num_classes, min_pixels, device, directions=None):
     """Eval-mode pass over ``collate_images`` batches.  Yields per batch (indices, original sizes [(H0, W0)], normalised
     images, labels uint8 [N, H, W], frame mean confidence list, records with ``image`` = the dataset index).  The records
-    and the means are the batch's host reads."""
+    and the means are the batch's host reads.  With ``directions`` (a number of Feret directions) the records are the
+    pair (records, shape records) of ``evaluation.describe_and_measure_class_regions``: one labelling, the same reads."""
     import numpy as np
     import torch
     from . import sheets
     from .augment import DeviceTransform
-    from .evaluation import describe_class_regions
+    from .evaluation import describe_and_measure_class_regions, describe_class_regions
     from .metrics import per_image_stats
     tf = DeviceTransform(tuple(size), train=False)
     model.eval()
@@ -115,8 +125,13 @@ def predict_batches(model, loader, size, num_classes, min_pixels, device):
             logits = model(x)
             labels, conf = sheets.seg_confidence(logits)
             means = per_image_stats(logits)["conf_mean"]
-            records = describe_class_regions(labels, num_classes, conf, min_pixels)
-            records[:, 0] = np.asarray(idx, np.int64)[records[:, 0]]
+            if directions is None:
+                records = describe_class_regions(labels, num_classes, conf, min_pixels)
+                records[:, 0] = np.asarray(idx, np.int64)[records[:, 0]]
+            else:
+                records = describe_and_measure_class_regions(labels, num_classes, conf, min_pixels, 0, directions)
+                for rec in records:
+                    rec[:, 0] = np.asarray(idx, np.int64)[rec[:, 0]]
             yield idx, sizes, x, labels, means.tolist(), records
 
 
@@ -136,9 +151,14 @@ def main(argv=None):
 
     mask_dir, overlay_dir, palette, palette_bytes = seg_cli.prediction_outputs(args, task, num_classes, device)
     loader = image_loader(paths, args.batch_size, args.num_workers)
-    originals, frame_means, records = [None] * len(paths), [None] * len(paths), []
+    originals, frame_means, records, shapes = [None] * len(paths), [None] * len(paths), [], []
+    rules = seg_cli.size_rules_of(args)
     for idx, sizes, x, labels, means, rec in predict_batches(model, loader, args.image_size, num_classes,
-                                                             args.min_region_pixels, device):
+                                                             args.min_region_pixels, device,
+                                                             None if rules is None else seg_cli.DIRECTIONS):
+        if rules is not None:
+            rec, shp = rec
+            shapes.append(shp)
         records.append(rec)
         if args.mask_size == "frame":
             host = labels.cpu().numpy()
@@ -154,7 +174,8 @@ def main(argv=None):
                                      os.path.join(overlay_dir, names[i] + ".png"))
 
     entries = defects.defect_entries(np.concatenate(records), class_names, args.image_size, originals,
-                                     args.min_confidence, args.reject_classes)
+                                     args.min_confidence, args.reject_classes,
+                                     np.concatenate(shapes) if shapes else None, rules)
     images = []
     for i, e in enumerate(entries):
         pixels = {name: 0 for name in class_names[1:]}

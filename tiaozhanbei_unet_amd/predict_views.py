@@ -49,11 +49,12 @@ def check_views(ap, args, scale=1.0):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="predict at full resolution from several views merged on the GPU")
-    for name, kw in FLAGS:
+    for name, kw in FLAGS + seg_cli.SHAPE_FLAGS:
         ap.add_argument(name, **kw)
     args = ap.parse_args(argv)
     seg_cli.check_tile_scale(ap, args, TASKS[args.task]["image_size"])
     seg_cli.check_predict_flags(ap, args)
+    seg_cli.check_shape_flags(ap, args)
     check_views(ap, args, args.scale)
     return args
 
@@ -74,7 +75,6 @@ def main(argv=None):
     task, views = TASKS[args.task], args.views
     device, paths, names, num_classes, class_names, model = seg_cli.open_prediction(args, task, "VIEW-ENSEMBLE PREDICTION",
                                                                                     "merge")
-    from .evaluation import describe_class_regions
     from .predict import image_loader
     from .tiling import TiledPredictor
 
@@ -88,12 +88,12 @@ def main(argv=None):
         original = (int(image.shape[0]), int(image.shape[1]))
         frame_hw = working_frame(original, args.scale)
         labels, conf, agreement, plan = ensemble(image, frame_hw)
-        records = describe_class_regions(labels[None], num_classes, conf[None], args.min_region_pixels)
+        records, shapes = seg_cli.describe_regions(args, labels[None], num_classes, conf[None])
         agree = agreement_means(labels[None], agreement[None], len(views), num_classes, args.min_region_pixels, records)
         frame = load_frame(image, frame_hw, device) if args.save_overlays else None
         images[i] = seg_cli.save_frame_prediction(args, outputs, paths[i], names[i], original, labels, conf, records,
                                                   class_names, {"tiling": plan[0]["tiling"], "views": plan}, frame=frame,
-                                                  defect_extras={"mean_view_agreement": agree})
+                                                  defect_extras={"mean_view_agreement": agree}, shapes=shapes)
     return seg_cli.write_predictions(args, class_names, images, middle=lambda im: f"in {len(im['views'])} views")
 
 

@@ -8,7 +8,8 @@ the ``eval_*`` side   ``parse_dataset_args`` (``--dataset`` first, then that dat
                       checkpoint), ``tiled_predictor``, the full-resolution walk ``full_resolution_images`` /
                       ``normalized_frame``, and the labelled-prediction sources ``frame_predictions`` /
                       ``tiled_predictions`` (``labelled_predictions`` picks one by ``--tiled``)
-the ``predict*`` side the refusals ``check_predict_flags`` and ``check_tile_scale``, ``open_prediction`` (images, state
+the ``predict*`` side the refusals ``check_predict_flags`` and ``check_tile_scale``, the shape flags (``SHAPE_FLAGS``,
+                      ``check_shape_flags``, ``size_rules_of``, ``describe_regions``), ``open_prediction`` (images, state
                       dict, classes, banner, model), ``prediction_outputs`` (``masks/``, ``overlays/``, palettes),
                       ``save_mask`` / ``save_overlay``, ``save_frame_prediction`` (one image's entry, mask and overlay)
                       and ``write_predictions`` (``predictions.json`` and the printed lines)
@@ -180,6 +181,56 @@ def check_predict_flags(ap, args):
         ap.error("--batch_size must be at least 1")
 
 
+# build-only: length, width, orientation, perimeter and holes of every defect (csrc/shapes.hip, defects.shape_measures).
+# Their default is "absent": a run that gives none of them has the ``args`` of before and launches nothing new.
+DIRECTIONS = 32                                          # Feret directions over half a turn: the length is low by < 0.12 %
+SHAPE_FLAGS = [("--measure_shapes", dict(action="store_true", default=argparse.SUPPRESS,
+                                         help="add a shape block (Feret length / width, axes, perimeter, holes) per defect")),
+               ("--pixel_size", dict(type=float, default=argparse.SUPPRESS, metavar="MM",
+                                     help="millimetres per pixel of the original image: adds *_mm fields")),
+               ("--min_defect_length", dict(type=float, default=argparse.SUPPRESS, metavar="X",
+                                            help="count only defects at least this long (mm with --pixel_size, else "
+                                                 "image pixels); implies --measure_shapes")),
+               ("--min_defect_area", dict(type=float, default=argparse.SUPPRESS, metavar="X",
+                                          help="count only defects of at least this area (mm2 with --pixel_size, else "
+                                               "image pixels); implies --measure_shapes"))]
+
+
+def check_shape_flags(ap, args):
+    """The rules of ``SHAPE_FLAGS``.  With none of them given ``args`` stays as it is; otherwise all four are set
+    (``measure_shapes`` True, ``pixel_size`` None or > 0, the thresholds 0 or what was given)."""
+    given = {name[2:] for name, _ in SHAPE_FLAGS if hasattr(args, name[2:])}
+    if not given:
+        return
+    if given == {"pixel_size"}:
+        ap.error("--pixel_size needs --measure_shapes, --min_defect_length or --min_defect_area")
+    args.measure_shapes = True
+    args.pixel_size = getattr(args, "pixel_size", None)
+    if args.pixel_size is not None and not 0.0 < args.pixel_size < float("inf"):
+        ap.error("--pixel_size must be positive")
+    for name in ("min_defect_length", "min_defect_area"):
+        setattr(args, name, getattr(args, name, 0.0))
+        if not 0.0 <= getattr(args, name) < float("inf"):
+            ap.error(f"--{name} must be at least 0")
+
+
+def size_rules_of(args):
+    """``defects.size_rules`` of the shape flags, or None when shapes are not measured"""
+    if not getattr(args, "measure_shapes", False):
+        return None
+    from . import defects
+    return defects.size_rules(args.pixel_size, args.min_defect_length, args.min_defect_area)
+
+
+def describe_regions(args, labels, num_classes, conf):
+    """(records, shape records or None) of label maps (N, H, W) for a predict tool: ``describe_class_regions``, and with
+    the shape flags ``measure_class_regions`` on the same labelling (one labelling, the same two host reads)"""
+    from . import evaluation
+    if size_rules_of(args) is None:
+        return evaluation.describe_class_regions(labels, num_classes, conf, args.min_region_pixels), None
+    return evaluation.describe_and_measure_class_regions(labels, num_classes, conf, args.min_region_pixels, 0, DIRECTIONS)
+
+
 def check_tile_scale(ap, args, default_tile):
     """The ``--tile``, ``--min_overlap`` and ``--scale`` rules of ``predict_tiled`` and ``predict_views``."""
     if args.tile is None:
@@ -257,16 +308,18 @@ def save_overlay(frame, labels, palette, path):
 
 
 def save_frame_prediction(args, outputs, path, name, original, labels, conf, records, class_names, plans, frame=None,
-                          defect_extras=None):
+                          defect_extras=None, shapes=None):
     """One image of ``predict_tiled`` / ``predict_views``: its ``predictions.json`` entry from the ``records`` of its
     label map (H, W) and confidence, ``masks/<name>.png`` at the image's ``original`` size (NEAREST when the frame
     differs), and with ``--save_overlays`` the overlay on ``frame``, the normalised (3, H, W) frame.  ``plans``: the keys
     that follow ``frame_size`` in the entry; ``defect_extras``: {key: one value per listed defect, in the records' order}.
-    ``outputs``: what ``prediction_outputs`` returned.  Returns the entry."""
+    ``outputs``: what ``prediction_outputs`` returned; ``shapes``: the records' shape records from ``describe_regions``
+    (None unless the shape flags are given).  Returns the entry."""
     from . import augment, defects
     mask_dir, overlay_dir, palette, palette_bytes = outputs
     frame_hw = (int(labels.shape[0]), int(labels.shape[1]))
-    (entry,) = defects.defect_entries(records, class_names, frame_hw, [original], args.min_confidence, args.reject_classes)
+    (entry,) = defects.defect_entries(records, class_names, frame_hw, [original], args.min_confidence, args.reject_classes,
+                                      shapes, size_rules_of(args))
     pixels = {cls: 0 for cls in class_names[1:]}
     for k, d in enumerate(entry["defects"]):                # defect_entries keeps the records' order: by root
         for key, values in (defect_extras or {}).items():
@@ -281,18 +334,25 @@ def save_frame_prediction(args, outputs, path, name, original, labels, conf, rec
 
 
 def write_predictions(args, class_names, images, middle=None, frame_size=None):
-    """``{output_dir}/predictions.json`` (args, class_names, [frame_size,] images, summary) and the printed lines: one
-    per image -- decision, name, then the frame size and ``middle(entry)`` (such as "in 4 tiles") when ``middle`` is
-    given, then its first four defects -- and the totals.  Returns the file's path."""
+    """``{output_dir}/predictions.json`` (args, class_names, [frame_size,] [size_rules,] images, summary) and the printed
+    lines: one per image -- decision, name, then the frame size and ``middle(entry)`` (such as "in 4 tiles") when
+    ``middle`` is given, then its first four defects, with their Feret length when shapes were measured -- and the
+    totals.  ``size_rules`` (``size_rules_of``) is there only with the shape flags.  Returns the file's path."""
     from . import defects
     summary = defects.summarize(images, class_names)
     shared = {} if frame_size is None else {"frame_size": list(frame_size)}
+    rules = size_rules_of(args)
+    if rules is not None:
+        shared["size_rules"] = rules
+    unit = "mm" if rules and rules["pixel_size"] is not None else "px"
+    length = "feret_length_mm" if unit == "mm" else "feret_length"
     out_path = os.path.join(args.output_dir, "predictions.json")
     with open(out_path, "w") as f:
         json.dump({"args": vars(args), "class_names": class_names, **shared, "images": images, "summary": summary}, f,
                   indent=2)
     for im in images:
         found = ", ".join(f"{d['class_name']} {d['pixels']} px @ {d['mean_confidence']:.2f}"
+                          + (f" length {d['shape'][length]:.1f} {unit}" if "shape" in d else "")
                           + (f" (views {d['mean_view_agreement']:.2f})" if "mean_view_agreement" in d else "")
                           for d in im["defects"][:4])
         more = f" (+{len(im['defects']) - 4} more)" if len(im["defects"]) > 4 else ""
