@@ -1,13 +1,9 @@
 // Calibration of the per-pixel confidence of a segmentation model (no reference counterpart): how well the softmax
 // maximum that predict / eval_detection threshold agrees with the accuracy it promises, and the one temperature T that
-// minimises the negative log-likelihood of softmax(z / T) on a held-out split.  Three entry points, restated in numpy by
-// tests/_calibration_ref.py:
-//   seg_confidence_scaled  segvis.hip's seg_confidence at a temperature: labels = the first maximum of the RAW logits (a
-//                          rounding of z * inv_t can never move a label), conf = 1 / sum_j expf((z_j - z_max) * inv_t) in
-//                          class order, all fp32.  (z_j - z_max) * 1.0f is z_j - z_max, so inv_t == 1 gives segvis.hip's
-//                          bytes.  The same access rule: 4 pixels per lane (16-byte loads and stores) when hw % 4 == 0 and
-//                          the pointers allow it, else 1.
-//   reliability_histogram  integers only.  Per pixel q = rint(clamp(conf, 0, 1) * 65536) (defects.hip's conf_q; NaN -> 0),
+// minimises the negative log-likelihood of softmax(z / T) on a held-out split.  Two entry points, restated in numpy by
+// tests/_calibration_ref.py (the third of that file, the confidence at a temperature, is segvis.hip's seg_confidence
+// with SCALED):
+//   reliability_histogram  integers only.  Per pixel q = rint(clamp(conf, 0, 1) * 65536) (segpixel.h's conf_q; NaN -> 0),
 //                          bin = min(bins - 1, (q * bins) >> 16), and hist[label][bin] += {1, truth == label, q}.  A block
 //                          owns ONE tile of RH_THREADS * RH_ITEMS = 4096 consecutive pixels, thread t the pixels t, t +
 //                          256, ...: it folds them in registers while the (label, bin) key stays the same (background at a
@@ -36,86 +32,19 @@
 // A pixel is left out of histogram and sweep alike when its target is ignore_index or outside 0..C-1 (the histogram:
 // also when its label byte is >= C; it counts these in `skipped`), and with select == 1 when truth and label are both
 // class 0.  The sweep first sets aside every pixel with a non-finite logit (counted[1]), whatever its target.
-#include "common.h"
+#include "segpixel.h"
 
 namespace {
 
-constexpr int MAXC = 8;                                // = segvis.hip, segeval.hip, segloss.hip
+using namespace segpx;                                 // MAXC, aligned, conf_q (segpixel.h)
 constexpr int MAX_BINS = 64;
 constexpr int MAXK = 32;                               // temperatures per sweep
-constexpr int CF_THREADS = 256;
-constexpr int CF_MAX_BLOCKS = 4096;
 constexpr int RH_THREADS = 256;
 constexpr int RH_ITEMS = 16;                           // pixels per thread
 constexpr int RH_TILE = RH_THREADS * RH_ITEMS;         // pixels per block: 4096
 constexpr int TS_THREADS = 256;
 constexpr int TS_WAVES = TS_THREADS / WAVE;
 constexpr int TS_MAX_PARTS = 2048;                     // blocks of one sweep, all images together
-
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-// ---- confidence at a temperature ---------------------------------------------------------------------------------------
-struct ScaledParams {
-  const float* logits; unsigned char* labels; float* conf;
-  int C; float inv_t; long long hw;
-  long long units;                                     // n * hw / V
-};
-
-__device__ __forceinline__ int argmax_conf_scaled(const float (&z)[MAXC], int C, float inv_t, float& conf) {
-  float best = z[0];
-  int arg = 0;
-#pragma unroll
-  for (int c = 1; c < MAXC; ++c)
-    if (c < C && z[c] > best) { best = z[c]; arg = c; }
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) s += expf((z[c] - best) * inv_t);
-  conf = 1.0f / s;
-  return arg;
-}
-
-// grid-stride over units of V pixels; V divides hw, so a unit lies in one image (segvis.hip's seg_confidence)
-template <int V>
-__global__ __launch_bounds__(CF_THREADS) void seg_confidence_scaled(const ScaledParams P) {
-  const long long per_img = P.hw / V;
-  for (long long u = (long long)blockIdx.x * CF_THREADS + threadIdx.x; u < P.units; u += (long long)gridDim.x * CF_THREADS) {
-    const long long n = u / per_img, at = (u % per_img) * V;
-    const float* x = P.logits + n * P.C * P.hw + at;
-    float z[V][MAXC];
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      if (c < P.C) {
-        if constexpr (V == 4) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(x + c * P.hw);
-          z[0][c] = v[0]; z[1][c] = v[1]; z[2][c] = v[2]; z[3][c] = v[3];
-        } else {
-          z[0][c] = x[c * P.hw];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < V; ++j) z[j][c] = 0.f;
-      }
-    }
-    int arg[V];
-    float cf[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) arg[j] = argmax_conf_scaled(z[j], P.C, P.inv_t, cf[j]);
-    const long long o = n * P.hw + at;
-    if constexpr (V == 4) {
-      if (P.labels)
-        *reinterpret_cast<unsigned int*>(P.labels + o) =
-            (unsigned)arg[0] | ((unsigned)arg[1] << 8) | ((unsigned)arg[2] << 16) | ((unsigned)arg[3] << 24);
-      if (P.conf) {
-        const f32x4 v = {cf[0], cf[1], cf[2], cf[3]};
-        *reinterpret_cast<f32x4*>(P.conf + o) = v;
-      }
-    } else {
-      if (P.labels) P.labels[o] = (unsigned char)arg[0];
-      if (P.conf) P.conf[o] = cf[0];
-    }
-  }
-}
 
 // ---- reliability histogram ---------------------------------------------------------------------------------------------
 struct HistParams {
@@ -126,11 +55,6 @@ struct HistParams {
   unsigned long long* hist;                            // [C][bins][3]
   unsigned long long* skipped;
 };
-
-// defects.hip's rule: the product is a scaling by a power of two, so it is exact; fmaxf(NaN, 0) is 0
-__device__ __forceinline__ unsigned conf_q(float v) {
-  return (unsigned)rintf(fminf(fmaxf(v, 0.0f), 1.0f) * 65536.0f);
-}
 
 // grid = tiles of RH_TILE pixels
 __global__ __launch_bounds__(RH_THREADS) void reliability_histogram(const HistParams P) {
@@ -392,26 +316,6 @@ inline bool sweep_shape_ok(int64_t n, int64_t hw, int64_t K) {
 }
 
 }  // namespace
-
-extern "C" int32_t unet_seg_confidence_scaled(const float* logits, int32_t n, int32_t c, int64_t hw, float inv_t,
-                                              uint8_t* labels, float* conf, void* stream) {
-  const char* who = "unet_seg_confidence_scaled";
-  UNET_REQUIRE(logits && (labels || conf), UNET_ERR_UNSUPPORTED, "%s: null pointer", who);
-  UNET_REQUIRE(n > 0 && hw > 0 && c >= 2 && c <= MAXC, UNET_ERR_UNSUPPORTED, "%s: n=%d c=%d hw=%lld (2..8 classes)", who, n,
-               c, (long long)hw);
-  UNET_REQUIRE(inv_t > 0.0f && inv_t <= 3.402823466e38f, UNET_ERR_UNSUPPORTED, "%s: inv_t=%g is not a finite value > 0", who,
-               (double)inv_t);
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec = hw % 4 == 0 && aligned(logits, 16) && (!labels || aligned(labels, 4)) && (!conf || aligned(conf, 16));
-  ScaledParams P{logits, labels, conf, c, inv_t, (long long)hw, (long long)n * (hw / (vec ? 4 : 1))};
-  long long blocks = cdiv64(P.units, CF_THREADS);
-  if (blocks > CF_MAX_BLOCKS) blocks = CF_MAX_BLOCKS;
-  const double bytes = (double)n * hw * (4.0 * c + (labels ? 1.0 : 0.0) + (conf ? 4.0 : 0.0));
-  ProfScope prof(UNET_K_OTHER, 0.0, s, "seg_confidence_scaled", bytes);
-  if (vec) hipLaunchKernelGGL(seg_confidence_scaled<4>, dim3((unsigned)blocks), dim3(CF_THREADS), 0, s, P);
-  else hipLaunchKernelGGL(seg_confidence_scaled<1>, dim3((unsigned)blocks), dim3(CF_THREADS), 0, s, P);
-  return unet_check_launch("seg_confidence_scaled");
-}
 
 extern "C" int32_t unet_reliability_histogram(const uint8_t* labels, const float* conf, const int64_t* target, int32_t n,
                                               int64_t hw, int32_t c, int32_t bins, int64_t ignore_index, int32_t select,

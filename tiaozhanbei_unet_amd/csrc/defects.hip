@@ -15,25 +15,23 @@
 //   accumulate_defects    every class pixel but the root finds its region's slot at the region root and folds (x, y,
 //                         q(conf)) into the record with atomicMin / atomicMax / atomicAdd on int64.  Not one atomic per
 //                         pixel and field: a thread folds its ACC_ITEMS pixels in registers while the slot stays the
-//                         same (its pixels lie 256 apart: inside a large region they share it); at the end the
-//                         wave reduces the lanes that share a slot with shuffles (up to LEADERS different slots per wave,
-//                         the remaining lanes commit on their own); the first such sum of each of the block's waves goes
-//                         through LDS, where one thread folds the waves that share a slot.  A region that fills the
-//                         frame costs one commit of 8 atomics per block of 2048 pixels; a wave of many small regions
-//                         falls back to per-lane commits.
-// The confidence is summed as q(v) = (uint32) rint(clamp(v, 0, 1) * 65536) (ties to even; the product is a scaling by a
-// power of two, so it is exact and the TU's contraction mode cannot matter): integer sums are exact in any order, a float
-// sum would depend on the order the atomics arrive in.  Apart from the record order every output is a function of the
-// inputs alone.
-#include "unionfind.h"
+//                         same (its pixels lie 256 apart: inside a large region they share it); slots.h's flush_by_slot
+//                         then sums across the wave and the block.  A region that fills the frame costs one commit of 8
+//                         atomics per block of 2048 pixels.
+// The confidence is summed as segpixel.h's conf_q(v) = (uint32) rint(clamp(v, 0, 1) * 65536) (ties to even; the product
+// is a scaling by a power of two, so it is exact and the TU's contraction mode cannot matter): integer sums are exact in
+// any order, a float sum would depend on the order the atomics arrive in.  Apart from the record order every output is a
+// function of the inputs alone.
+#include "segpixel.h"
+#include "slots.h"
 
 namespace {
 
 using namespace uf;
+using namespace segpx;                                 // class_of, conf_q (segpixel.h)
 constexpr int ACC_ITEMS = 8;                           // pixels per lane of both passes
 constexpr int DREC = 12;                               // int64 fields of a record
-constexpr int LEADERS = 4;                             // slots per wave that are reduced with shuffles
-constexpr int PX_WAVES = PX_THREADS / WAVE;
+using slots::PX_WAVES;
 
 struct DescribeParams {
   const uint8_t* cls; const int* region; const int* sizes; const float* conf;
@@ -43,12 +41,6 @@ struct DescribeParams {
   unsigned long long* rec_count;
   int* slot;                                           // [n][h][w] workspace
 };
-
-__device__ __forceinline__ int class_of(uint8_t v, int C) { return v < C ? v : 0; }
-
-__device__ __forceinline__ unsigned conf_q(float v) {
-  return (unsigned)rintf(fminf(fmaxf(v, 0.0f), 1.0f) * 65536.0f);
-}
 
 // grid (pixels of one image / (PX_THREADS * ACC_ITEMS), images); every lane runs every round (the ballots want that)
 __global__ __launch_bounds__(PX_THREADS) void assign_defect_slots(const DescribeParams A) {
@@ -138,9 +130,7 @@ __device__ __forceinline__ Acc wave_fold(Acc a, bool on) {
 
 // same grid as assign_defect_slots, after it
 __global__ __launch_bounds__(PX_THREADS) void accumulate_defects(const DescribeParams A) {
-  __shared__ Acc part[PX_WAVES];
   const long long base = (long long)blockIdx.y * A.per;
-  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
   int slot[ACC_ITEMS];
   unsigned q[ACC_ITEMS];
 #pragma unroll
@@ -173,36 +163,7 @@ __global__ __launch_bounds__(PX_THREADS) void accumulate_defects(const DescribeP
       }
     }
   }
-  // the wave: the lanes that share the slot of the first pending lane are summed with shuffles, LEADERS times over
-  Acc mine;
-  mine.slot = -1;
-  unsigned long long m = __ballot(a.slot >= 0);
-  for (int it = 0; it < LEADERS && m; ++it) {          // wave-uniform
-    const int first = __ffsll((long long)m) - 1;
-    const int lead = __shfl(a.slot, first);
-    const bool on = a.slot == lead;
-    const unsigned long long same = __ballot(on);
-    Acc s = wave_fold(a, on);
-    s.slot = lead;
-    if (it == 0) mine = s;
-    else if (lane == first) commit(A.rec, s);
-    if (on) a.slot = -1;
-    m &= ~same;
-  }
-  if (a.slot >= 0) commit(A.rec, a);                   // a wave of more than LEADERS regions: each lane for itself
-  // the block: the waves' first sums, folded where they share a slot
-  if (lane == 0) part[wave] = mine;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-#pragma unroll
-  for (int i = 0; i < PX_WAVES; ++i) {
-    Acc s = part[i];
-    if (s.slot < 0) continue;
-#pragma unroll
-    for (int j = i + 1; j < PX_WAVES; ++j)
-      if (part[j].slot == s.slot) { fold(s, part[j]); part[j].slot = -1; }
-    commit(A.rec, s);
-  }
+  slots::flush_by_slot(a, [&](const Acc& s) { commit(A.rec, s); });
 }
 
 inline bool supported(int64_t n, int64_t h, int64_t w, int64_t C) {

@@ -19,10 +19,11 @@
 // templated on the element type, pro_curve / pro_finalize integrate the curve up to the fpr limit (see there).
 // No float atomics: the sorted arrays are a function of the pixel multiset and every partition below a function of
 // (P, N), so results are bitwise identical whatever the batch split, image order or run.
-#include "common.h"
+#include "segpixel.h"
 
 namespace {
 
+using segpx::aligned;
 constexpr int AP_THREADS = 256;
 constexpr int AP_WAVES = AP_THREADS / WAVE;
 constexpr int RS_THREADS = 256;
@@ -571,7 +572,6 @@ inline RegionLayout region_layout(long long n_pos, long long n_neg) {
 inline bool supported(long long n_pos, long long n_neg) {
   return n_pos >= 0 && n_neg >= 0 && n_pos + n_neg < (1LL << 31);
 }
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 

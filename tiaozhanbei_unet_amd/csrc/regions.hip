@@ -1,20 +1,17 @@
 // 8-connected regions of the ground-truth masks (truth > 0.5) with their sizes: what the per-region-overlap (PRO) curve
-// of the MVTec evaluation weights its pixels by.  Tiled union-find on parent links (index of a pixel of the same region
-// with a smaller or equal linear index y*w + x; a root links to itself), four launches, no workgroup waits on another:
-//   label_tile     a 32x32 tile in LDS: every defective pixel is united with its W neighbour and with N, or (N clear)
-//                  NW and NE, by atomicMin on the links; each pixel then finds its tile root.  Writes the root's image
-//                  index as the pixel's global link and, at the root, the pixel count of the tile component.
+// of the MVTec evaluation weights its pixels by.  The labelling is labeller.h's tiled union-find (tile pass, border merge,
+// root sizes) with the one-class policy below: a pixel is defective or not, so "the neighbour is my own" is the sign of
+// its link.  label_tile is a wrapper around its tile body; the other passes are this file's own:
 //   merge_borders  a thread per pixel of a tile's first column / first row: united with its (up to 3) neighbours in
 //                  the tile to the left / above by atomicMin on the global links.
-//   root_sizes     every tile root finds its region root, adds its count there (integer atomicAdd) and links to it.
-//   finish         every pixel: label = 1 + region root, size = the root's count; the totals {regions, defective, ok}.
-// A link only ever decreases and always stays inside its region, so a stale read costs a retry, never a wrong union;
-// the minimum index of a region is its only possible root, so labels and sizes are a function of the mask alone.
-#include "unionfind.h"
+//   root_sizes     every tile root finds its region root, adds its count there and links to it (unionfind.h).
+//   finish_labels  every pixel: label = 1 + region root, size = the root's count; the totals {regions, defective, ok}.
+// Labels and sizes are a function of the mask alone (labeller.h says why).
+#include "labeller.h"
 
 namespace {
 
-using namespace uf;                                   // tiles, links, find_root, unite (unionfind.h)
+using namespace uf;                                   // tiles, links, find_root (unionfind.h); the bodies (labeller.h)
 constexpr int FIN_ITEMS = 8;                           // pixels per lane of finish_labels: 3 count atomics per 2048 pixels
 
 struct LabelParams {
@@ -25,56 +22,22 @@ struct LabelParams {
   unsigned long long* counts;                          // {regions, defective, ok}
 };
 
+// labeller.h's pixel policy for image n: one class (defective); the images of `select` (NULL: all)
+struct MaskPixels {
+  const float* truth; const uint8_t* select;           // the image's plane; its entry of `select`, or NULL
+  static constexpr bool BY_CLASS = false;
+  __device__ __forceinline__ int cls(long long g) const { return truth[g] > 0.5f; }
+  __device__ __forceinline__ bool selected() const { return !select || *select; }
+};
+__device__ __forceinline__ MaskPixels pixels_of(const LabelParams& A, int n) {
+  return MaskPixels{A.truth + (long long)n * A.per, A.select ? A.select + n : nullptr};
+}
+__device__ __forceinline__ Frame frame_of(const LabelParams& A, int n) {
+  return Frame{A.h, A.w, A.tiles_x, A.per, A.parent + (long long)n * A.per, A.sizes + (long long)n * A.per};
+}
+
 __global__ __launch_bounds__(LT_THREADS) void label_tile(const LabelParams A) {
-  __shared__ int par[LT_PIX];
-  __shared__ int cnt[LT_PIX];
-  const int n = blockIdx.y;
-  if (A.select && !A.select[n]) return;                // block-uniform
-  const int y0 = (int)(blockIdx.x / A.tiles_x) * LT, x0 = (int)(blockIdx.x % A.tiles_x) * LT;
-  const float* t = A.truth + (long long)n * A.per;
-  constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP;
-  bool def[LT_ITEMS];
-#pragma unroll
-  for (int j = 0; j < LT_ITEMS; ++j) {
-    const int i = threadIdx.x + j * LT_THREADS, y = y0 + i / LT, x = x0 + i % LT;
-    def[j] = y < A.h && x < A.w && t[(long long)y * A.w + x] > 0.5f;
-    par[i] = def[j] ? i : -1;
-    cnt[i] = 0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < LT_ITEMS; ++j) {
-    if (!def[j]) continue;
-    const int i = threadIdx.x + j * LT_THREADS, ly = i / LT, lx = i % LT;
-    if (lx > 0 && link_of<WG>(par, i - 1) >= 0) unite<WG>(par, i, i - 1);
-    if (ly > 0) {
-      if (link_of<WG>(par, i - LT) >= 0) {             // N joins NW and NE by their own W links
-        unite<WG>(par, i, i - LT);
-      } else {
-        if (lx > 0 && link_of<WG>(par, i - LT - 1) >= 0) unite<WG>(par, i, i - LT - 1);
-        if (lx < LT - 1 && link_of<WG>(par, i - LT + 1) >= 0) unite<WG>(par, i, i - LT + 1);
-      }
-    }
-  }
-  __syncthreads();
-  int root[LT_ITEMS];
-#pragma unroll
-  for (int j = 0; j < LT_ITEMS; ++j) {
-    root[j] = def[j] ? find_root<WG>(par, threadIdx.x + j * LT_THREADS) : -1;
-    if (def[j]) atomicAdd(&cnt[root[j]], 1);
-  }
-  __syncthreads();
-  int* parent = A.parent + (long long)n * A.per;
-  int* sizes = A.sizes + (long long)n * A.per;
-#pragma unroll
-  for (int j = 0; j < LT_ITEMS; ++j) {
-    const int i = threadIdx.x + j * LT_THREADS, y = y0 + i / LT, x = x0 + i % LT;
-    if (y >= A.h || x >= A.w) continue;
-    const long long g = (long long)y * A.w + x;
-    // the tile's row-major order follows the image's: the tile root is the component's smallest image index too
-    parent[g] = def[j] ? (y0 + root[j] / LT) * A.w + x0 + root[j] % LT : -1;
-    sizes[g] = root[j] == i ? cnt[i] : 0;
-  }
+  label_tile_body(pixels_of(A, blockIdx.y), frame_of(A, blockIdx.y));
 }
 
 // grid (border pixels of one image / PX_THREADS, images): first the (tiles_x - 1) * h pixels of the tiles' first
@@ -184,22 +147,6 @@ extern "C" int32_t unet_label_regions(const float* truth, const uint8_t* select,
   LabelParams A{truth, select, (int)h, (int)w, tx, ty, (long long)(h * w), (int*)workspace, labels, sizes,
                 (unsigned long long*)counts};
   ProfScope prof(UNET_K_OTHER, 0.0, s, "label_tile", (double)n * h * w * 12.0);
-  hipLaunchKernelGGL(label_tile, dim3((unsigned)((long long)tx * ty), (unsigned)n), dim3(LT_THREADS), 0, s, A);
-  int32_t rc = unet_check_launch("label_tile");
-  if (rc) return rc;
-  const long long border = (long long)(tx - 1) * h + (long long)(ty - 1) * w;
-  if (border > 0) {
-    hipLaunchKernelGGL(merge_borders, dim3((unsigned)cdiv64(border, PX_THREADS), (unsigned)n), dim3(PX_THREADS), 0, s, A);
-    rc = unet_check_launch("merge_borders");
-    if (rc) return rc;
-  }
-  const dim3 grid((unsigned)cdiv64(h * w, PX_THREADS), (unsigned)n);
-  if (border > 0) {                                    // one tile: every tile root is a region root already
-    hipLaunchKernelGGL(root_sizes, grid, dim3(PX_THREADS), 0, s, A);
-    rc = unet_check_launch("root_sizes");
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(finish_labels, dim3((unsigned)cdiv64(h * w, PX_THREADS * FIN_ITEMS), (unsigned)n), dim3(PX_THREADS),
-                     0, s, A);
-  return unet_check_launch("finish_labels");
+  return launch_labeller<LabelParams>({label_tile, "label_tile"}, {merge_borders, "merge_borders"}, {root_sizes, "root_sizes"},
+                                      {finish_labels, "finish_labels"}, A, n, h, w, FIN_ITEMS, s);
 }

@@ -8,6 +8,7 @@
 //   render_sheet   a thread produces RUN = 4 consecutive pixels of one sheet row = 12 bytes = 3 dwords, stored as dwords
 //                  where the run is whole and its address dword-aligned, else byte by byte.  With W and the gutter both
 //                  multiples of 4 a run never crosses a panel border and its inputs come in as 16-byte loads (VEC).
+//                  The run geometry, the table staging and the byte / blend rules are sheet.h's, shared with segvis.hip.
 // Per-pixel arithmetic (every product and sum rounds once: this file is built with -ffp-contract=off):
 //   image    v = x * std[c], then + mean[c] (fp32), clamp to [0, 1], byte = (uint8)(v * 255.0f) truncating; NaN -> 0
 //   unit     clamp to [0, 1], the same byte rule (the reconstruction panel)
@@ -17,18 +18,19 @@
 //            matplotlib's cmap(Normalize()(x.astype(float64))) takes, exactly; from fp32 it would differ at bin borders.
 //   overlay  (a8 * hot(map) + (255 - a8) * image + 127) / 255 in integers per channel; a non-finite map pixel shows image
 // The two 256-entry LUTs come from the caller (device memory, [2][256][3] bytes: gray, hot) and are staged in LDS.
-#include "common.h"
+#include "segpixel.h"
+#include "sheet.h"
 
 namespace {
 
+using segpx::aligned;
+using namespace sheet;                                 // RUN, WHITE, the pixel rules, stage_table, run_at (sheet.h)
 constexpr int RG_THREADS = 256;
 constexpr int RG_WAVES = RG_THREADS / WAVE;
 constexpr int RG_MAX_BLOCKS = 2048;
 constexpr int SH_THREADS = 256;                        // = LUT entries: thread t stages entry t of both tables
 constexpr int SH_MAX_BLOCKS = 2048;
-constexpr int RUN = 4;                                 // pixels per thread
 constexpr int MAX_PANELS = 8;
-constexpr uint32_t WHITE = 0x00ffffffu;
 
 // ---- range -------------------------------------------------------------------------------------------------------------
 struct RangeParams {
@@ -99,18 +101,8 @@ struct SheetParams {
   uint32_t rw, runs;                                   // runs per sheet row, runs of the sheet
 };
 
-// clamp to [0, 1] (NaN -> 0), then the truncating byte of matplotlib's (x * 255).astype(uint8) on float32
-__device__ __forceinline__ uint32_t unit_byte(float v) {
-  if (!(v > 0.f)) v = 0.f;
-  if (v > 1.f) v = 1.f;
-  return (uint32_t)(v * 255.0f);
-}
 __device__ __forceinline__ uint32_t rgb_pixel(const SheetParams& A, bool denorm, float r, float g, float b) {
-  if (denorm) {
-    r = r * A.std[0]; r = r + A.mean[0];
-    g = g * A.std[1]; g = g + A.mean[1];
-    b = b * A.std[2]; b = b + A.mean[2];
-  }
+  if (denorm) denormalise(A.mean, A.std, r, g, b);
   return unit_byte(r) | (unit_byte(g) << 8) | (unit_byte(b) << 16);
 }
 
@@ -130,13 +122,6 @@ __device__ __forceinline__ int map_index(float x, const Range& R) {
   if (!(R.span > 0.0)) return 0;
   const double s = floor((((double)x - R.lo) / R.span) * 256.0);
   return s >= 255.0 ? 255 : (s <= 0.0 ? 0 : (int)s);
-}
-__device__ __forceinline__ uint32_t blend(uint32_t heat, uint32_t img, uint32_t a8) {
-  uint32_t out = 0;
-#pragma unroll
-  for (int s = 0; s < 24; s += 8)
-    out |= ((a8 * ((heat >> s) & 255u) + (255u - a8) * ((img >> s) & 255u) + 127u) / 255u) << s;
-  return out;
 }
 // one pixel of panel c from its loaded values: v[0..2] the rgb input, m the map input
 __device__ __forceinline__ uint32_t shade(const SheetParams& A, const uint32_t (*lut)[256], int kind, uint32_t a8,
@@ -158,18 +143,13 @@ template <bool VEC>
 __global__ __launch_bounds__(SH_THREADS) void render_sheet(const SheetParams A) {
   __shared__ uint32_t lut[2][256];
 #pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const uint8_t* e = A.luts + (m * 256 + threadIdx.x) * 3;
-    lut[m][threadIdx.x] = (uint32_t)e[0] | ((uint32_t)e[1] << 8) | ((uint32_t)e[2] << 16);
-  }
+  for (int m = 0; m < 2; ++m) stage_table(lut[m], A.luts, m * 256);     // gray, hot
   __syncthreads();
   const int SW = A.K * A.W + (A.K - 1) * A.g, ph = A.H + A.g, pw = A.W + A.g;
   const long long plane = (long long)A.H * A.W;
-  // a run is at least 3 bytes of a sheet of fewer than 2^31: 32-bit run indices
   for (uint32_t t = blockIdx.x * SH_THREADS + threadIdx.x; t < A.runs; t += gridDim.x * SH_THREADS) {
-    const int row = (int)(t / A.rw), col0 = (int)(t % A.rw) * RUN;
-    const int r = row / ph, y = row % ph;              // r < N: row < N ph - g
-    const int cnt = min(RUN, SW - col0);               // >= 1
+    const Run u = run_at(t, A.rw, SW);
+    const int col0 = u.col0, r = u.row / ph, y = u.row % ph;     // r < N: row < N ph - g
     uint32_t px[RUN];
 #pragma unroll
     for (int j = 0; j < RUN; ++j) px[j] = WHITE;
@@ -218,19 +198,17 @@ __global__ __launch_bounds__(SH_THREADS) void render_sheet(const SheetParams A) 
     }
     // 4 pixels x 3 bytes, the first pixel's red in the lowest byte
     const uint32_t w[3] = {px[0] | (px[1] << 24), (px[1] >> 8) | (px[2] << 16), (px[2] >> 16) | (px[3] << 8)};
-    uint8_t* a = A.out + (long long)row * (3LL * SW) + 3LL * col0;
-    if (cnt == RUN && ((uintptr_t)a & 3u) == 0) {
+    uint8_t* a = A.out + (long long)u.row * (3LL * SW) + 3LL * col0;
+    if (u.cnt == RUN && ((uintptr_t)a & 3u) == 0) {
       uint32_t* q = reinterpret_cast<uint32_t*>(a);
       q[0] = w[0]; q[1] = w[1]; q[2] = w[2];
     } else {
 #pragma unroll
       for (int j = 0; j < 3 * RUN; ++j)
-        if (j < 3 * cnt) a[j] = (uint8_t)(w[j / 4] >> (8 * (j % 4)));
+        if (j < 3 * u.cnt) a[j] = (uint8_t)(w[j / 4] >> (8 * (j % 4)));
     }
   }
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // shared checks of the two entry points: 0, or the status (error text set)
 int32_t check_panels(const char* who, const unet_panel* panels, int32_t k, int32_t n, int32_t h, int32_t w) {
@@ -269,7 +247,7 @@ extern "C" int32_t unet_render_range(const unet_panel* panels, int32_t k, int32_
   for (int c = 0; c < k; ++c) {
     if (!has_map(panels[c])) continue;
     A.map[c] = panels[c].map;
-    vec = vec && aligned16(A.map[c]);
+    vec = vec && aligned(A.map[c], 16);
     ++maps;
   }
   const size_t half = (size_t)k * n * sizeof(uint32_t);
@@ -305,8 +283,8 @@ extern "C" int32_t unet_render_sheet(const unet_panel* panels, int32_t k, int32_
   for (int c = 0; c < k; ++c) {
     A.kind[c] = panels[c].kind;
     A.a8[c] = panels[c].alpha8;
-    if (has_rgb(panels[c])) { A.rgb[c] = panels[c].rgb; vec = vec && aligned16(A.rgb[c]); in_bytes += 12.0; }
-    if (has_map(panels[c])) { A.map[c] = panels[c].map; vec = vec && aligned16(A.map[c]); in_bytes += 4.0; }
+    if (has_rgb(panels[c])) { A.rgb[c] = panels[c].rgb; vec = vec && aligned(A.rgb[c], 16); in_bytes += 12.0; }
+    if (has_map(panels[c])) { A.map[c] = panels[c].map; vec = vec && aligned(A.map[c], 16); in_bytes += 4.0; }
   }
   A.K = k; A.N = n; A.H = h; A.W = w; A.g = gutter;
   for (int c = 0; c < 3; ++c) { A.mean[c] = mean3[c]; A.std[c] = std3[c]; }

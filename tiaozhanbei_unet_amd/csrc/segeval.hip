@@ -13,11 +13,12 @@
 //   seg_stats_finalize   grid N: ordered sums of the block partials -> uint64 confusion, mean and unbiased std.
 // No float atomics, no global atomics at all: the pixel -> lane -> block mapping is a function of (n, c, hw) only,
 // so results are bitwise identical from run to run.
-#include "common.h"
+#include "segpixel.h"
 
 namespace {
 
-constexpr int MAXC = 8;                  // = segloss.hip
+using segpx::MAXC;
+using segpx::aligned;
 constexpr int ST_THREADS = 256;
 constexpr int ST_WAVES = ST_THREADS / WAVE;
 constexpr int FIN_THREADS = 256;
@@ -226,8 +227,6 @@ inline int stats_bpi(int n, long long units) {
   if (b < 1) b = 1;
   return (int)b;
 }
-
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 

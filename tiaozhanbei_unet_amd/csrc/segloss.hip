@@ -28,11 +28,11 @@
 //   * input_is_prob: Dice of the given map, gradient with respect to the map; loss[1] and loss[3] are not defined
 #include <stdlib.h>
 
-#include "common.h"
+#include "segpixel.h"
 
 namespace {
 
-constexpr int MAXC = 8;
+using segpx::MAXC;
 constexpr int SEG_THREADS = 256;
 constexpr int NSUM = 3 * MAXC + 3;       // per block: I[c], P[c], T[c], ce_num, ce_den, focal_sum
 

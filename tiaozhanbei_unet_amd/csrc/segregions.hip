@@ -2,14 +2,11 @@
 // pixel statistics of segeval.hip.  A pixel has class c iff its value is c with 1 <= c < C (0 and every value >= C are
 // background); a class region is an 8-connected component of pixels of one and the same class in one image.
 //
-// Labelling is the tiled union-find of regions.hip (unionfind.h) with one change, the predicate of the union step:
-// "the neighbour is defective" becomes "the neighbour has my class".  Four launches, no workgroup waits on another:
-//   label_class_tile      a 32x32 tile in LDS: every class pixel is united with its W neighbour and with N, or (N of
-//                         another class) NW and NE, where they have its class; the tile root's image index becomes the
-//                         pixel's global link and the root holds the pixel count of the tile component.
+// Labelling is labeller.h's tiled union-find (label_class_tile is a wrapper around its tile body) with
+// the by-class policy below: "the neighbour is my own" means "the neighbour has my class".  This file's own passes:
 //   merge_class_borders   a thread per pixel of a tile's first column / first row: united with those of its (up to 3)
 //                         neighbours in the tile to the left / above that have its class.
-//   class_root_sizes      every tile root adds its count at its region root and links to it.
+//   class_root_sizes      every tile root adds its count at its region root and links to it (unionfind.h).
 //   finish_class_regions  every pixel: region = 1 + region root, size = the root's count; regions per image and class.
 // Matching is two more launches over the pixels, integers only:
 //   count_class_hits      a pixel whose truth and predicted class agree (not background) and whose predicted region is
@@ -23,11 +20,13 @@
 // one class: every link stays inside its class region, every chain descends to a root, and the retries of unite are
 // bounded by the finitely many times the links can be lowered.  The smallest index of a region is its only possible
 // root, so every output but the record order is a function of the two label maps alone.
-#include "unionfind.h"
+#include "labeller.h"
+#include "segpixel.h"
 
 namespace {
 
-using namespace uf;
+using namespace uf;                                   // tiles, links, find_root (unionfind.h); the bodies (labeller.h)
+using segpx::class_of;
 constexpr int FIN_ITEMS = 8;                           // pixels per lane of the per-pixel passes
 constexpr int REC = 5;                                 // int32 fields of a record
 static_assert(PX_THREADS == 256, "finish_class_regions keeps one counter per thread and class");
@@ -40,59 +39,22 @@ struct ClassParams {
   unsigned long long* counts;                          // [n][C] regions per image and class
 };
 
-__device__ __forceinline__ int class_of(uint8_t v, int C) { return v < C ? v : 0; }
+// labeller.h's pixel policy for image n: the classes 1 .. C - 1 of a label map, every image
+struct ClassPixels {
+  const uint8_t* map; int C;                           // the image's plane
+  static constexpr bool BY_CLASS = true;
+  __device__ __forceinline__ int cls(long long g) const { return class_of(map[g], C); }
+  __device__ __forceinline__ bool selected() const { return true; }
+};
+__device__ __forceinline__ ClassPixels pixels_of(const ClassParams& A, int n) {
+  return ClassPixels{A.cls + (long long)n * A.per, A.C};
+}
+__device__ __forceinline__ Frame frame_of(const ClassParams& A, int n) {
+  return Frame{A.h, A.w, A.tiles_x, A.per, A.parent + (long long)n * A.per, A.sizes + (long long)n * A.per};
+}
 
 __global__ __launch_bounds__(LT_THREADS) void label_class_tile(const ClassParams A) {
-  __shared__ int par[LT_PIX];
-  __shared__ int cnt[LT_PIX];
-  __shared__ uint8_t kls[LT_PIX];                      // written once before the barrier, then only read
-  const int n = blockIdx.y;
-  const int y0 = (int)(blockIdx.x / A.tiles_x) * LT, x0 = (int)(blockIdx.x % A.tiles_x) * LT;
-  const uint8_t* t = A.cls + (long long)n * A.per;
-  constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP;
-  int c[LT_ITEMS];
-#pragma unroll
-  for (int j = 0; j < LT_ITEMS; ++j) {
-    const int i = threadIdx.x + j * LT_THREADS, y = y0 + i / LT, x = x0 + i % LT;
-    c[j] = (y < A.h && x < A.w) ? class_of(t[(long long)y * A.w + x], A.C) : 0;
-    par[i] = c[j] ? i : -1;
-    cnt[i] = 0;
-    kls[i] = (uint8_t)c[j];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < LT_ITEMS; ++j) {
-    if (!c[j]) continue;
-    const int i = threadIdx.x + j * LT_THREADS, ly = i / LT, lx = i % LT;
-    if (lx > 0 && kls[i - 1] == c[j]) unite<WG>(par, i, i - 1);
-    if (ly > 0) {
-      if (kls[i - LT] == c[j]) {                       // N of my class joins NW and NE of my class by their own W links
-        unite<WG>(par, i, i - LT);
-      } else {
-        if (lx > 0 && kls[i - LT - 1] == c[j]) unite<WG>(par, i, i - LT - 1);
-        if (lx < LT - 1 && kls[i - LT + 1] == c[j]) unite<WG>(par, i, i - LT + 1);
-      }
-    }
-  }
-  __syncthreads();
-  int root[LT_ITEMS];
-#pragma unroll
-  for (int j = 0; j < LT_ITEMS; ++j) {
-    root[j] = c[j] ? find_root<WG>(par, threadIdx.x + j * LT_THREADS) : -1;
-    if (c[j]) atomicAdd(&cnt[root[j]], 1);
-  }
-  __syncthreads();
-  int* parent = A.parent + (long long)n * A.per;
-  int* sizes = A.sizes + (long long)n * A.per;
-#pragma unroll
-  for (int j = 0; j < LT_ITEMS; ++j) {
-    const int i = threadIdx.x + j * LT_THREADS, y = y0 + i / LT, x = x0 + i % LT;
-    if (y >= A.h || x >= A.w) continue;
-    const long long g = (long long)y * A.w + x;
-    // the tile's row-major order follows the image's: the tile root is the component's smallest image index too
-    parent[g] = c[j] ? (y0 + root[j] / LT) * A.w + x0 + root[j] % LT : -1;
-    sizes[g] = root[j] == i ? cnt[i] : 0;
-  }
+  label_tile_body(pixels_of(A, blockIdx.y), frame_of(A, blockIdx.y));
 }
 
 // grid (border pixels of one image / PX_THREADS, images): first the (tiles_x - 1) * h pixels of the tiles' first
@@ -274,23 +236,9 @@ extern "C" int32_t unet_label_class_regions(const uint8_t* classes, int64_t n, i
   ClassParams A{classes, (int)num_classes, (int)h, (int)w, tx, ty, (long long)(h * w), (int*)workspace, region, sizes,
                 (unsigned long long*)counts};
   ProfScope prof(UNET_K_OTHER, 0.0, s, "label_class_tile", (double)n * h * w * 13.0);
-  hipLaunchKernelGGL(label_class_tile, dim3((unsigned)((long long)tx * ty), (unsigned)n), dim3(LT_THREADS), 0, s, A);
-  int32_t rc = unet_check_launch("label_class_tile");
-  if (rc) return rc;
-  const long long border = (long long)(tx - 1) * h + (long long)(ty - 1) * w;
-  if (border > 0) {
-    hipLaunchKernelGGL(merge_class_borders, dim3((unsigned)cdiv64(border, PX_THREADS), (unsigned)n), dim3(PX_THREADS), 0,
-                       s, A);
-    rc = unet_check_launch("merge_class_borders");
-    if (rc) return rc;
-    hipLaunchKernelGGL(class_root_sizes, dim3((unsigned)cdiv64(h * w, PX_THREADS), (unsigned)n), dim3(PX_THREADS), 0, s,
-                       A);                             // one tile: every tile root is a region root already
-    rc = unet_check_launch("class_root_sizes");
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(finish_class_regions, dim3((unsigned)cdiv64(h * w, PX_THREADS * FIN_ITEMS), (unsigned)n),
-                     dim3(PX_THREADS), 0, s, A);
-  return unet_check_launch("finish_class_regions");
+  return launch_labeller<ClassParams>({label_class_tile, "label_class_tile"}, {merge_class_borders, "merge_class_borders"},
+                                      {class_root_sizes, "class_root_sizes"},
+                                      {finish_class_regions, "finish_class_regions"}, A, n, h, w, FIN_ITEMS, s);
 }
 
 extern "C" size_t unet_match_class_regions_workspace(int64_t n, int64_t h, int64_t w, int32_t num_classes) {

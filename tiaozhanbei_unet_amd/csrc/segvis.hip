@@ -4,58 +4,47 @@
 //                      conf = softmax(logits).max(0) = 1 / sum_j expf(z_j - z_max) per pixel, all in fp32, j in class
 //                      order (visualize.py:134-135, visualize_kolektorsdd.py:131).  A lane owns 4 consecutive pixels (one
 //                      16-byte read per class plane, one 4-byte label store, one 16-byte confidence store) when hw % 4 == 0
-//                      and the pointers allow it, else 1 pixel.  HBM-bound, no reductions, no atomics.
+//                      and the pointers allow it, else 1 pixel.  HBM-bound, no reductions, no atomics.  The rule itself
+//                      is segpixel.h's argmax_conf, which tiles.hip and views.hip apply to their merged logits.
+//   seg_confidence_scaled  the same kernel with SCALED (eval_calibration): conf = 1 / sum_j expf((z_j - z_max) * inv_t), the
+//                      labels still those of the raw logits; inv_t == 1 gives seg_confidence's bytes.
 //   seg_render_sheet   one launch writes the whole uint8 RGB sheet of ceil(n / per_row) rows of per_row samples of k panels
 //                      of h x w pixels, `gutter` pixels of 255 between panels in both directions and in the cells past n.
-//                      As render.hip: a thread produces RUN = 4 consecutive pixels of one sheet row = 12 bytes = 3 dwords,
-//                      stored as dwords where the run is whole and its address dword-aligned, else byte by byte.  With w
-//                      and the gutter both multiples of 4 a run never crosses a panel border and its inputs come in as
+//                      The run geometry, the table staging and the pixel rules are sheet.h's, shared with render.hip.  With
+//                      w and the gutter both multiples of 4 a run never crosses a panel border and its inputs come in as
 //                      16-byte (image, map) and 4-byte (labels) loads (VEC).
 // Per-pixel arithmetic (every product and sum rounds once: this file is built with -ffp-contract=off):
-//   image    render.hip's UNET_PANEL_IMAGE: v = x * std[c], then + mean[c] (fp32), clamp to [0, 1], NaN -> 0,
-//            byte = (uint8)(v * 255.0f) truncating
+//   image    sheet.h's denormalise and unit_byte, render.hip's UNET_PANEL_IMAGE: v = x * std[c], then + mean[c] (fp32), clamp to
+//            [0, 1], NaN -> 0, byte = (uint8)(v * 255.0f) truncating
 //   classes  palette[label]
 //   overlay  label 0: the image byte (visualize.py:112-113 draws nothing on the background); else
-//            (a8 * palette[label] + (255 - a8) * image + 127) / 255 in integers per channel (render.hip's blend)
+//            (a8 * palette[label] + (255 - a8) * image + 127) / 255 in integers per channel (sheet.h's blend)
 //   lut      the fixed range [0, 1] of imshow(vmin=0, vmax=1): i = floor(v * 256) (exact in fp32) clipped to [0, 255],
 //            v < 0 gives 0; a non-finite pixel is (255, 255, 255)
 // The two 256-entry tables (class palette, colour map) come from the caller in device memory and are staged in LDS.
-#include "common.h"
+#include "segpixel.h"
+#include "sheet.h"
 
 namespace {
 
-constexpr int MAXC = 8;                                // = segeval.hip, segloss.hip
+using namespace segpx;                                 // MAXC, aligned, argmax_conf (segpixel.h)
+using namespace sheet;                                 // RUN, WHITE, the pixel rules, stage_table, run_at (sheet.h)
 constexpr int CF_THREADS = 256;
 constexpr int CF_MAX_BLOCKS = 4096;
 constexpr int SH_THREADS = 256;                        // = table entries: thread t stages entry t of both tables
 constexpr int SH_MAX_BLOCKS = 2048;
-constexpr int RUN = 4;                                 // pixels per thread
 constexpr int MAX_PANELS = 8;
-constexpr uint32_t WHITE = 0x00ffffffu;
 
 // ---- confidence --------------------------------------------------------------------------------------------------------
 struct ConfParams {
   const float* logits; unsigned char* labels; float* conf;
-  int C; long long hw;
+  int C; float inv_t; long long hw;                    // inv_t: read by the SCALED kernels only
   long long units;                                     // n * hw / V
 };
 
-__device__ __forceinline__ int argmax_conf(const float (&z)[MAXC], int C, float& conf) {
-  float best = z[0];
-  int arg = 0;
-#pragma unroll
-  for (int c = 1; c < MAXC; ++c)
-    if (c < C && z[c] > best) { best = z[c]; arg = c; }
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) s += expf(z[c] - best);
-  conf = 1.0f / s;
-  return arg;
-}
-
-// grid-stride over units of V pixels; V divides hw, so a unit lies in one image
-template <int V>
+// grid-stride over units of V pixels; V divides hw, so a unit lies in one image.  SCALED: the confidence at the
+// temperature 1 / inv_t (unet_seg_confidence_scaled)
+template <int V, bool SCALED>
 __global__ __launch_bounds__(CF_THREADS) void seg_confidence(const ConfParams P) {
   const long long per_img = P.hw / V;
   for (long long u = (long long)blockIdx.x * CF_THREADS + threadIdx.x; u < P.units; u += (long long)gridDim.x * CF_THREADS) {
@@ -79,7 +68,7 @@ __global__ __launch_bounds__(CF_THREADS) void seg_confidence(const ConfParams P)
     int arg[V];
     float cf[V];
 #pragma unroll
-    for (int j = 0; j < V; ++j) arg[j] = argmax_conf(z[j], P.C, cf[j]);
+    for (int j = 0; j < V; ++j) arg[j] = argmax_conf<SCALED>(z[j], P.C, cf[j], P.inv_t);
     const long long o = n * P.hw + at;
     if constexpr (V == 4) {
       if (P.labels)
@@ -96,6 +85,21 @@ __global__ __launch_bounds__(CF_THREADS) void seg_confidence(const ConfParams P)
   }
 }
 
+// both entry points after their checks: 4 pixels per lane when hw % 4 == 0 and the pointers allow it, else 1
+template <bool SCALED>
+int32_t launch_confidence(const char* name, const float* logits, int n, int c, long long hw, float inv_t, uint8_t* labels,
+                          float* conf, hipStream_t s) {
+  const bool vec = hw % 4 == 0 && aligned(logits, 16) && (!labels || aligned(labels, 4)) && (!conf || aligned(conf, 16));
+  ConfParams P{logits, labels, conf, c, inv_t, hw, (long long)n * (hw / (vec ? 4 : 1))};
+  long long blocks = cdiv64(P.units, CF_THREADS);
+  if (blocks > CF_MAX_BLOCKS) blocks = CF_MAX_BLOCKS;
+  const double bytes = (double)n * hw * (4.0 * c + (labels ? 1.0 : 0.0) + (conf ? 4.0 : 0.0));
+  ProfScope prof(UNET_K_OTHER, 0.0, s, name, bytes);
+  if (vec) hipLaunchKernelGGL((seg_confidence<4, SCALED>), dim3((unsigned)blocks), dim3(CF_THREADS), 0, s, P);
+  else hipLaunchKernelGGL((seg_confidence<1, SCALED>), dim3((unsigned)blocks), dim3(CF_THREADS), 0, s, P);
+  return unet_check_launch(name);
+}
+
 // ---- sheet -------------------------------------------------------------------------------------------------------------
 struct SheetParams {
   const float* image;                                  // [n][3][h][w]
@@ -110,24 +114,9 @@ struct SheetParams {
   uint32_t rw, runs;                                   // runs per sheet row, runs of the sheet
 };
 
-// clamp to [0, 1] (NaN -> 0), then the truncating byte of matplotlib's (x * 255).astype(uint8) on float32 (render.hip)
-__device__ __forceinline__ uint32_t unit_byte(float v) {
-  if (!(v > 0.f)) v = 0.f;
-  if (v > 1.f) v = 1.f;
-  return (uint32_t)(v * 255.0f);
-}
 __device__ __forceinline__ uint32_t image_pixel(const SheetParams& A, float r, float g, float b) {
-  r = r * A.std[0]; r = r + A.mean[0];
-  g = g * A.std[1]; g = g + A.mean[1];
-  b = b * A.std[2]; b = b + A.mean[2];
+  denormalise(A.mean, A.std, r, g, b);
   return unit_byte(r) | (unit_byte(g) << 8) | (unit_byte(b) << 16);
-}
-__device__ __forceinline__ uint32_t blend(uint32_t top, uint32_t img, uint32_t a8) {
-  uint32_t out = 0;
-#pragma unroll
-  for (int s = 0; s < 24; s += 8)
-    out |= ((a8 * ((top >> s) & 255u) + (255u - a8) * ((img >> s) & 255u) + 127u) / 255u) << s;
-  return out;
 }
 // one pixel of a panel from its loaded values: v0..v2 the image input, l the label, m the map input
 __device__ __forceinline__ uint32_t shade(const SheetParams& A, const uint32_t* pal, const uint32_t* lut, int kind,
@@ -151,19 +140,14 @@ __device__ __forceinline__ bool needs_image(int kind) { return kind == UNET_SEG_
 template <bool VEC>
 __global__ __launch_bounds__(SH_THREADS) void seg_render_sheet(const SheetParams A) {
   __shared__ uint32_t tab[2][256];                     // palette, colour map
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const uint8_t* e = (m ? A.lut : A.palette) + threadIdx.x * 3;
-    tab[m][threadIdx.x] = (uint32_t)e[0] | ((uint32_t)e[1] << 8) | ((uint32_t)e[2] << 16);
-  }
+  stage_table(tab[0], A.palette);
+  stage_table(tab[1], A.lut);
   __syncthreads();
   const int SW = A.SW, ph = A.H + A.g, pw = A.W + A.g;
   const long long plane = (long long)A.H * A.W;
-  // a run is at least 3 bytes of a sheet of fewer than 2^31: 32-bit run indices
   for (uint32_t t = blockIdx.x * SH_THREADS + threadIdx.x; t < A.runs; t += gridDim.x * SH_THREADS) {
-    const int row = (int)(t / A.rw), col0 = (int)(t % A.rw) * RUN;
-    const int r = row / ph, y = row % ph;              // r < R: row < R ph - g
-    const int cnt = min(RUN, SW - col0);               // >= 1
+    const Run u = run_at(t, A.rw, SW);
+    const int col0 = u.col0, r = u.row / ph, y = u.row % ph;     // r < R: row < R ph - g
     uint32_t px[RUN];
 #pragma unroll
     for (int j = 0; j < RUN; ++j) px[j] = WHITE;
@@ -212,19 +196,17 @@ __global__ __launch_bounds__(SH_THREADS) void seg_render_sheet(const SheetParams
     }
     // 4 pixels x 3 bytes, the first pixel's red in the lowest byte
     const uint32_t w[3] = {px[0] | (px[1] << 24), (px[1] >> 8) | (px[2] << 16), (px[2] >> 16) | (px[3] << 8)};
-    uint8_t* a = A.out + (long long)row * (3LL * SW) + 3LL * col0;
-    if (cnt == RUN && ((uintptr_t)a & 3u) == 0) {
+    uint8_t* a = A.out + (long long)u.row * (3LL * SW) + 3LL * col0;
+    if (u.cnt == RUN && ((uintptr_t)a & 3u) == 0) {
       uint32_t* q = reinterpret_cast<uint32_t*>(a);
       q[0] = w[0]; q[1] = w[1]; q[2] = w[2];
     } else {
 #pragma unroll
       for (int j = 0; j < 3 * RUN; ++j)
-        if (j < 3 * cnt) a[j] = (uint8_t)(w[j / 4] >> (8 * (j % 4)));
+        if (j < 3 * u.cnt) a[j] = (uint8_t)(w[j / 4] >> (8 * (j % 4)));
     }
   }
 }
-
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 
@@ -233,16 +215,20 @@ extern "C" int32_t unet_seg_confidence(const float* logits, int32_t n, int32_t c
   UNET_REQUIRE(logits && (labels || conf), UNET_ERR_BAD_ARG, "unet_seg_confidence: null pointer");
   UNET_REQUIRE(n > 0 && hw > 0 && c >= 2 && c <= MAXC, UNET_ERR_UNSUPPORTED,
                "unet_seg_confidence: n=%d c=%d hw=%lld (2..8 classes)", n, c, (long long)hw);
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec = hw % 4 == 0 && aligned(logits, 16) && (!labels || aligned(labels, 4)) && (!conf || aligned(conf, 16));
-  ConfParams P{logits, labels, conf, c, (long long)hw, (long long)n * (hw / (vec ? 4 : 1))};
-  long long blocks = cdiv64(P.units, CF_THREADS);
-  if (blocks > CF_MAX_BLOCKS) blocks = CF_MAX_BLOCKS;
-  const double bytes = (double)n * hw * (4.0 * c + (labels ? 1.0 : 0.0) + (conf ? 4.0 : 0.0));
-  ProfScope prof(UNET_K_OTHER, 0.0, s, "seg_confidence", bytes);
-  if (vec) hipLaunchKernelGGL(seg_confidence<4>, dim3((unsigned)blocks), dim3(CF_THREADS), 0, s, P);
-  else hipLaunchKernelGGL(seg_confidence<1>, dim3((unsigned)blocks), dim3(CF_THREADS), 0, s, P);
-  return unet_check_launch("seg_confidence");
+  return launch_confidence<false>("seg_confidence", logits, n, c, hw, 1.0f, labels, conf, (hipStream_t)stream);
+}
+
+// seg_confidence at a temperature (eval_calibration): conf = 1 / sum_j expf((z_j - z_max) * inv_t), the labels those of
+// the raw logits; inv_t == 1 gives unet_seg_confidence's bytes
+extern "C" int32_t unet_seg_confidence_scaled(const float* logits, int32_t n, int32_t c, int64_t hw, float inv_t,
+                                              uint8_t* labels, float* conf, void* stream) {
+  const char* who = "unet_seg_confidence_scaled";
+  UNET_REQUIRE(logits && (labels || conf), UNET_ERR_UNSUPPORTED, "%s: null pointer", who);
+  UNET_REQUIRE(n > 0 && hw > 0 && c >= 2 && c <= MAXC, UNET_ERR_UNSUPPORTED, "%s: n=%d c=%d hw=%lld (2..8 classes)", who, n,
+               c, (long long)hw);
+  UNET_REQUIRE(inv_t > 0.0f && inv_t <= 3.402823466e38f, UNET_ERR_UNSUPPORTED, "%s: inv_t=%g is not a finite value > 0", who,
+               (double)inv_t);
+  return launch_confidence<true>("seg_confidence_scaled", logits, n, c, hw, inv_t, labels, conf, (hipStream_t)stream);
 }
 
 extern "C" int32_t unet_seg_render_sheet(const float* image, const unet_seg_panel* panels, int32_t k, int32_t n,

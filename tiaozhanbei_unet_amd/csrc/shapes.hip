@@ -21,8 +21,9 @@
 //                        one pixel; every pixel leaves its slot or -1 in the 4-byte-per-pixel workspace, all of which is
 //                        written.
 //   accumulate_shapes    every other class pixel finds its slot at the root.  Moments and quads take defects.hip's way
-//                        into the record: summed in the thread while the slot stays the same, across the wave for up to
-//                        LEADERS slots, across the block through LDS, then int64 atomicAdd at agent scope.  Projections:
+//                        into the record: summed in the thread while the slot stays the same, then slots.h's
+//                        flush_by_slot (across the wave for up to LEADERS slots, across the block through LDS), then int64
+//                        atomicAdd at agent scope.  Projections:
 //                        a lane takes the extremes of its own boundary pixels, the lanes of a wave that share the
 //                        leading slot are reduced with shuffles, LEADERS times over, one direction after the other (no
 //                        D values per lane in registers), and a lane on its own broadcasts its pixels; the commit has
@@ -31,18 +32,18 @@
 //                        only ever falls, so a value read earlier can only be too high and the skip is always right.
 //                        That read is what a block-level fold would save, without D LDS cells per slot.
 // No floating point: apart from the record order every output is a function of the inputs alone.
-#include "unionfind.h"
+#include "slots.h"
 
 namespace {
 
 using namespace uf;
+using slots::LEADERS;                                  // slots per wave that project() reduces with shuffles, as flush_by_slot
+using slots::PX_WAVES;
 constexpr int ACC_ITEMS = 8;                           // pixels per lane of both passes
 constexpr int HEAD = 11;                               // int64 fields before the projections
 constexpr int MAX_DIRS = 32;
 constexpr int MAX_SIDE = 16384;                        // sum_xx <= 2^56, |p| < 2^30
 constexpr int MAX_COMPONENT = 1 << 14;                 // |c_k|, |s_k|
-constexpr int LEADERS = 4;                             // slots per wave that are reduced with shuffles
-constexpr int PX_WAVES = PX_THREADS / WAVE;
 constexpr int DEV = __HIP_MEMORY_SCOPE_AGENT;
 
 struct ShapeParams {
@@ -251,10 +252,9 @@ __device__ __forceinline__ void project(const ShapeParams& A, int F, int lane, i
 // the assign pass, a row that crosses a few regions of a hundred pixels makes every lane change its region several times,
 // and each change is a commit.)
 __global__ __launch_bounds__(PX_THREADS) void accumulate_shapes(const ShapeParams A) {
-  __shared__ Acc part[PX_WAVES];
   const long long base = (long long)blockIdx.y * A.per;
   const int* img = A.region + base;
-  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
   const int F = HEAD + 2 * A.D;
   const long long g0 = ((long long)blockIdx.x * PX_THREADS + threadIdx.x) * ACC_ITEMS;
   int x = (int)(g0 % A.w), y = (int)(g0 / A.w);        // past the image for g0 >= per: not used there
@@ -303,36 +303,7 @@ __global__ __launch_bounds__(PX_THREADS) void accumulate_shapes(const ShapeParam
     if (++x == A.w) { x = 0; ++y; }
   }
   project(A, F, lane, edge_slot, edge_px, xs, ys);
-  // the wave: the lanes that share the slot of the first pending lane are summed with shuffles, LEADERS times over
-  Acc mine;
-  mine.slot = -1;
-  unsigned long long m = __ballot(a.slot >= 0);
-  for (int it = 0; it < LEADERS && m; ++it) {          // wave-uniform
-    const int first = __ffsll((long long)m) - 1;
-    const int lead = __shfl(a.slot, first);
-    const bool on = a.slot == lead;
-    const unsigned long long same = __ballot(on);
-    Acc s = wave_fold(a, on);
-    s.slot = lead;
-    if (it == 0) mine = s;
-    else if (lane == first) commit(A.rec, F, s);
-    if (on) a.slot = -1;
-    m &= ~same;
-  }
-  if (a.slot >= 0) commit(A.rec, F, a);                // a wave of more than LEADERS regions: each lane for itself
-  // the block: the waves' first sums, folded where they share a slot
-  if (lane == 0) part[wave] = mine;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-#pragma unroll
-  for (int i = 0; i < PX_WAVES; ++i) {
-    Acc s = part[i];
-    if (s.slot < 0) continue;
-#pragma unroll
-    for (int j = i + 1; j < PX_WAVES; ++j)
-      if (part[j].slot == s.slot) { fold(s, part[j]); part[j].slot = -1; }
-    commit(A.rec, F, s);
-  }
+  slots::flush_by_slot(a, [&](const Acc& s) { commit(A.rec, F, s); });
 }
 
 inline bool supported(int64_t n, int64_t h, int64_t w, int64_t D) {

@@ -7,19 +7,19 @@
 //                   wsum += q_y * q_x (int32),  acc_c = acc_c + (float)(q_y * q_x) * z_c  (product and sum rounded apart:
 //                   this file is built with -ffp-contract=off),  blended_c = acc_c / (float)wsum;
 //                 a pixel under exactly one tile takes that tile's logits unchanged.  labels / conf follow from the
-//                 blended logits by segvis.hip's rule (first maximum; 1 / sum_j expf(z_j - max z), j in class order),
-//                 restated here: segvis.hip keeps it in its own unnamed namespace, and its device code stays as it is.
+//                 blended logits by segpixel.h's argmax_conf (first maximum; 1 / sum_j expf(z_j - max z), j in class
+//                 order): the one rule seg_confidence applies to raw logits, so the two agree bit for bit.
 // The gather form: a lane owns output pixels and walks the tiles over them; no atomics, no LDS, the outputs are a
 // function of the inputs alone.  The origin tables (at most 64 per axis) travel in the kernel arguments.  A block works
 // on a segment of ONE row, so everything along y -- the covering tiles, q_y -- is wave-uniform, and the tables are only
 // ever indexed by uniform loop counters (scalar loads from the argument segment); along x every lane tests the nx tiles.
 // A lane owns 4 consecutive x (16-byte loads and stores) when w, tw and every ox[j] are multiples of 4 and the pointers
 // are aligned: the four pixels then lie under the same tiles.  Else one pixel.  HBM-bound: every tile logit is read once.
-#include "common.h"
+#include "segpixel.h"
 
 namespace {
 
-constexpr int MAXC = 8;                                // = segvis.hip
+using namespace segpx;                                 // MAXC, aligned, argmax_conf (segpixel.h)
 constexpr int MAX_TILES_AXIS = 64;
 constexpr int MAX_RAMP = 256;
 constexpr int TL_THREADS = 256;
@@ -37,22 +37,6 @@ struct BlendParams {
   const float* tiles; unsigned char* labels; float* conf; float* blended;
   int ramp_y, ramp_x;
 };
-
-// segvis.hip's argmax_conf, operation for operation (CM: the class slots the kernel keeps, C <= CM)
-template <int CM>
-__device__ __forceinline__ int argmax_conf(const float (&z)[CM], int C, float& conf) {
-  float best = z[0];
-  int arg = 0;
-#pragma unroll
-  for (int c = 1; c < CM; ++c)
-    if (c < C && z[c] > best) { best = z[c]; arg = c; }
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < CM; ++c)
-    if (c < C) s += expf(z[c] - best);
-  conf = 1.0f / s;
-  return arg;
-}
 
 __device__ __forceinline__ int ramp_weight(int k, int L, int B) { return min(min(k + 1, L - k), B); }
 
@@ -170,8 +154,6 @@ __global__ __launch_bounds__(TL_THREADS) void tile_blend(const TileGrid G, const
     }
   }
 }
-
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // the origins of one axis are a cover of [0, F) by tiles of length L: first 0, last F - L, strictly increasing, no gap
 bool valid_cover(const int32_t* o, int n, int F, int L) {

@@ -11,9 +11,9 @@
 //                   every product and every sum rounded once (this file is built with -ffp-contract=off); a view of the
 //                   frame's own size on both axes is not interpolated: its logits are taken unchanged.
 //                   acc_c starts as the first view's value and adds the others; merged_c = acc_c / (float)V.
-//                 labels / conf follow from the merged logits by segvis.hip's rule (first maximum; 1 / sum_j expf(z_j -
-//                 max z), j in class order), restated here as tiles.hip restates it; agreement counts the views whose own
-//                 first maximum is the merged label.
+//                 labels / conf follow from the merged logits by segpixel.h's argmax_conf (first maximum; 1 / sum_j
+//                 expf(z_j - max z), j in class order), as in segvis.hip and tiles.hip; agreement counts the views whose
+//                 own first maximum is the merged label.
 // The gather form: a lane owns output pixels and walks the views; no atomics, no LDS, the outputs are a function of the
 // inputs alone.  The view descriptors (at most 16) travel in the kernel arguments and are only indexed by the uniform view
 // counter.  A block works on a segment of ONE row, so the y taps and y weights are wave-uniform.  The floor above is two
@@ -25,11 +25,11 @@
 // measured to wait for is the number of gathered load instructions, so the two x taps of a row, which are neighbours
 // (or one sample at the clamped edge), come in ONE 8-byte load of samples xl, xl + 1 with xl = min(x0, x1, wv - 2), and
 // the row bases are scalars with 32-bit lane offsets: 107 -> 78 us on the six-view Gear frame (profiles/view_merge.txt).
-#include "common.h"
+#include "segpixel.h"
 
 namespace {
 
-constexpr int MAXC = 8;                                // = segvis.hip
+using namespace segpx;                                 // MAXC, aligned, argmax_conf (segpixel.h)
 constexpr int MAX_VIEWS = 16;
 constexpr int MAX_SIDE = 16384;
 constexpr int VM_THREADS = 256;
@@ -49,22 +49,6 @@ struct MergeArgs {
   long long items;                                     // row segments of the launch
   float* merged; unsigned char* labels; float* conf; unsigned char* agreement;
 };
-
-// segvis.hip's argmax_conf, operation for operation (CM: the class slots the kernel keeps, C <= CM)
-template <int CM>
-__device__ __forceinline__ int argmax_conf(const float (&z)[CM], int C, float& conf) {
-  float best = z[0];
-  int arg = 0;
-#pragma unroll
-  for (int c = 1; c < CM; ++c)
-    if (c < C && z[c] > best) { best = z[c]; arg = c; }
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < CM; ++c)
-    if (c < C) s += expf(z[c] - best);
-  conf = 1.0f / s;
-  return arg;
-}
 
 // Q = floor(((2 i + 1) M 2^15) / N), R its remainder; 0 <= i < N, 1 <= M, N <= 16384: t < 2^29, Q < 2^30 + 2^15
 __device__ __forceinline__ void tap_divide(int i, int M, int N, unsigned& Q, unsigned& R) {
@@ -246,7 +230,6 @@ __global__ __launch_bounds__(VM_THREADS) void view_merge(const MergeArgs A) {
   }
 }
 
-inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 inline bool side_ok(int v) { return v >= 1 && v <= MAX_SIDE; }
 
 }  // namespace
