@@ -587,6 +587,39 @@ int32_t unet_measure_class_regions(const int32_t* region, const int32_t* sizes, 
                                    int64_t* records, int64_t capacity, int64_t* record_count, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* Outlines of class regions (no reference counterpart; csrc/contours.hip, restated one edge at a time by
+ * tests/_contours_ref.py): the inverse of unet_polygon_mask_u8, each kept region's boundary as pixel-centre polygons.
+ * region and sizes are what unet_label_class_regions makes; a region is kept iff its size >= min_pixels (>= 1), the rule
+ * of unet_describe_class_regions.  A directed crack edge is (pixel p, direction d), d = 0 E (+x), 1 S (+y), 2 W, 3 N: it
+ * exists when p is a pixel of a kept region and its neighbour in direction r = (d + 1) % 4 is not a pixel of that region
+ * (outside the frame counts), and its id is 4 (y w + x) + d.  Its successor is (p + d + r, r) if that pixel is a member,
+ * else (p + d, d) if that one is, else (p, (d + 3) % 4); the edges fall into loops.  A loop's leader is its smallest id;
+ * area2 = the sum over its edges of x1 y0 - x0 y1 between their pixel-corner end points: +2 for one pixel, > 0 for a
+ * region's one outer loop, < 0 for each hole loop.  Its points: the edges' pixels in walk order from the leader, cyclic
+ * repeats merged, every point dropped whose step in equals its step out (a loop around one pixel keeps that pixel).
+ * unet_count_class_region_edges: counts[3] (int64, device, WRITTEN) = {edges, loops, points} of the maps, one pass over
+ * the pixels and no tracing (loops = twice the kept regions minus the Euler numbers of their masks).
+ * unet_trace_class_regions: counts as above, and for edges <= edge_cap: loops[L][6] (int64) = {image_base + image, region
+ * root index y w + x, leader edge id, n_points, first point, area2} in ascending (image, leader edge id), and
+ * points[P][2] (int32) = (x, y), each loop's points contiguous from its first point.  A row at or past loop_cap and a
+ * point at or past point_cap are not written; with edges > edge_cap nothing is; the counts are the true ones either way.
+ * Every position is a prefix sum and area2 an integer atomic add: the outputs are a function of the inputs alone, byte
+ * for byte.  The edges are compacted, a loop's leader and every edge's point ordinal are found by pointer doubling, one
+ * launch per round over ping-pong buffers, ceil(log2(edge_cap)) rounds each.
+ * Both: any h, w >= 1; n < 65536 and n h w <= 2^29 (an edge id fits int32); image_base + n, edge_cap, loop_cap and
+ * point_cap <= 2^31 - 1; else UNET_ERR_UNSUPPORTED before any launch (and the workspace queries return 0).  A NULL
+ * pointer (loops / points may be NULL with a capacity of 0) or min_pixels < 1 is UNET_ERR_BAD_ARG.  Allocate nothing, do
+ * not synchronise. */
+size_t unet_count_class_region_edges_workspace(int64_t n, int64_t h, int64_t w);
+int32_t unet_count_class_region_edges(const int32_t* region, const int32_t* sizes, int64_t n, int64_t h, int64_t w,
+                                      int32_t min_pixels, int64_t* counts /* [3] */, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+size_t unet_trace_class_regions_workspace(int64_t n, int64_t h, int64_t w, int64_t edge_cap);
+int32_t unet_trace_class_regions(const int32_t* region, const int32_t* sizes, int64_t n, int64_t h, int64_t w,
+                                 int32_t min_pixels, int32_t image_base, int64_t edge_cap, int64_t* loops,
+                                 int64_t loop_cap, int32_t* points, int64_t point_cap, int64_t* counts /* [3] */,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* Outline accuracy of label maps (no reference counterpart): an exact squared Euclidean distance transform of the class
  * boundaries, and one record per (image, class) of how far the outlines of two maps lie apart (csrc/distance.hip).
  * classes / truth / pred: uint8 [n][h][w] as unet_label_class_regions takes them; a pixel has class c iff its value is c,

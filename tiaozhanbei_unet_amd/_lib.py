@@ -166,6 +166,10 @@ SIGNATURES = {
     "unet_describe_class_regions": (_i, [_p, _p, _p, _p, _l, _l, _l, _i, _i, _i, _p, _l, _p, _p, _z, _p]),
     "unet_measure_class_regions_workspace": (_z, [_l, _l, _l, _i]),
     "unet_measure_class_regions": (_i, [_p, _p, _l, _l, _l, _i, _i, _p, _i, _p, _l, _p, _p, _z, _p]),
+    "unet_count_class_region_edges_workspace": (_z, [_l, _l, _l]),
+    "unet_count_class_region_edges": (_i, [_p, _p, _l, _l, _l, _i, _p, _p, _z, _p]),
+    "unet_trace_class_regions_workspace": (_z, [_l, _l, _l, _l]),
+    "unet_trace_class_regions": (_i, [_p, _p, _l, _l, _l, _i, _i, _l, _p, _l, _p, _l, _p, _p, _z, _p]),
     "unet_boundary_distance_sq_workspace": (_z, [_l, _l, _l, _i]),
     "unet_boundary_distance_sq": (_i, [_p, _l, _l, _l, _i, _p, _p, _z, _p]),
     "unet_boundary_stats": (_i, [_p, _p, _p, _p, _l, _l, _l, _i, _p, _i, _i, _i, _p, _p, _p]),

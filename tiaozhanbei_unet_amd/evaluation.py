@@ -571,27 +571,122 @@ def _sorted_records(host, cap, fields, root_field, what):
     return np.ascontiguousarray(rec[np.lexsort((rec[:, root_field], rec[:, 0]))])
 
 
-def describe_and_measure_class_regions(labels, num_classes, conf=None, min_pixels=1, image_base=0, directions=32):
+def describe_and_measure_class_regions(labels, num_classes, conf=None, min_pixels=1, image_base=0, directions=32,
+                                       contours=False):
     """(``describe_class_regions``' records, ``measure_class_regions``' records) of one labelling: the maps are labelled
     once, both kernels run on that labelling, and the two record sets come to the host in one buffer, so the host reads
-    stay two (the region counts, then the records).  The rows of the two arrays align."""
+    stay two (the region counts, then the records).  The rows of the two arrays align.
+
+    ``contours=True`` traces the same labelling too and returns (records, shape records, loops, points), the last two as
+    ``trace_class_regions`` gives them: the edge counts come with the records, and the outlines are a third read.  With
+    it ``directions=None`` leaves the shapes out (None in their place)."""
     import numpy as np
-    t, cf, c, min_pixels, image_base = _describe_args("describe_and_measure_class_regions", labels, num_classes, conf,
-                                                      min_pixels, image_base)
-    table, d = _measure_args("describe_and_measure_class_regions", t, min_pixels, image_base, directions)
+    what = "describe_and_measure_class_regions"
+    t, cf, c, min_pixels, image_base = _describe_args(what, labels, num_classes, conf, min_pixels, image_base)
+    shaped = not (contours and directions is None)
+    table, d = _measure_args(what, t, min_pixels, image_base, directions) if shaped else (None, 0)
+    if contours:
+        _trace_args(what, t)
     fd, fs = len(DEFECT_FIELDS), len(SHAPE_HEAD) + 2 * d
     region, sizes, counts = label_class_regions(t, c)
     cap = int(counts.sum())
     if cap == 0:
-        return np.zeros((0, fd), np.int64), np.zeros((0, fs), np.int64)
-    both = torch.cat([_describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap),
-                      _measure_labelled(region, sizes, min_pixels, image_base, cap, table)]).cpu().numpy()
-    what = "describe_and_measure_class_regions"
+        empty = (np.zeros((0, fd), np.int64), np.zeros((0, fs), np.int64) if shaped else None)
+        return empty + _no_outlines() if contours else empty
+    parts = [_describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap)]
+    if shaped:
+        parts.append(_measure_labelled(region, sizes, min_pixels, image_base, cap, table))
+    if contours:
+        parts.append(_count_edges(region, sizes, min_pixels))
+    both = torch.cat(parts).cpu().numpy()
     rec = _defect_records(both[:cap * fd + 1], cap, what)
-    shapes = _sorted_records(both[cap * fd + 1:], cap, fs, 1, what)
-    if len(rec) != len(shapes) or (rec[:, [0, 2, 3]] != shapes[:, :3]).any():
-        raise RuntimeError(f"{what}: the two record sets differ")      # cannot happen
-    return rec, shapes
+    shapes = None
+    if shaped:
+        shapes = _sorted_records(both[cap * fd + 1:cap * (fd + fs) + 2], cap, fs, 1, what)
+        if len(rec) != len(shapes) or (rec[:, [0, 2, 3]] != shapes[:, :3]).any():
+            raise RuntimeError(f"{what}: the two record sets differ")      # cannot happen
+    if not contours:
+        return rec, shapes
+    return (rec, shapes) + _trace_counted(region, sizes, min_pixels, image_base, both[-3:].tolist(), what)
+
+
+LOOP_FIELDS = ("image", "root", "leader", "n_points", "first_point", "area2")
+
+
+def _no_outlines():
+    import numpy as np
+    return np.zeros((0, len(LOOP_FIELDS)), np.int64), np.zeros((0, 2), np.int32)
+
+
+def _trace_args(what, region):
+    """refuse, before anything is launched, maps that unet_trace_class_regions does not take"""
+    if region.dim() != 3 or region.numel() == 0:
+        raise ValueError(f"{what}: [N, H, W] maps, got {tuple(region.shape)}")
+    n, h, w = region.shape
+    if L.lib().unet_count_class_region_edges_workspace(n, h, w) == 0:
+        raise RuntimeError(f"{what}: {n} x {h} x {w} maps cannot be traced (n < 65536, at most 2^29 pixels)")
+
+
+def _count_edges(region, sizes, min_pixels):
+    """unet_count_class_region_edges: the DEVICE int64 [3] counts {edges, loops, points}"""
+    n, h, w = region.shape
+    lib = L.lib()
+    counts = torch.empty(3, dtype=torch.int64, device=region.device)
+    ws = _workspace(lib.unet_count_class_region_edges_workspace(n, h, w), region.device)
+    L.check(lib.unet_count_class_region_edges(_ptr(region), _ptr(sizes), n, h, w, min_pixels, _ptr(counts), _ptr(ws),
+                                              ws.numel(), _stream()), "unet_count_class_region_edges")
+    return counts
+
+
+def _trace_counted(region, sizes, min_pixels, image_base, counted, what):
+    """unet_trace_class_regions with buffers of the ``counted`` {edges, loops, points}: (loops, points) on the host, one
+    read"""
+    import numpy as np
+    n, h, w = region.shape
+    edges, n_loops, n_points = (int(v) for v in counted)
+    if edges == 0:
+        return _no_outlines()
+    lib = L.lib()
+    nbytes = lib.unet_trace_class_regions_workspace(n, h, w, edges)
+    if nbytes == 0 or image_base + n >= 2 ** 31:
+        raise RuntimeError(f"{what}: {edges} edges of {n} x {h} x {w} maps cannot be traced")
+    out = torch.empty(n_loops * len(LOOP_FIELDS) + 3 + n_points, dtype=torch.int64, device=region.device)
+    loops, counts, points = out[:n_loops * 6], out[n_loops * 6:n_loops * 6 + 3], out[n_loops * 6 + 3:]
+    ws = _workspace(nbytes, region.device)
+    L.check(lib.unet_trace_class_regions(_ptr(region), _ptr(sizes), n, h, w, min_pixels, image_base, edges, _ptr(loops),
+                                         n_loops, _ptr(points), n_points, _ptr(counts), _ptr(ws), ws.numel(), _stream()),
+            "unet_trace_class_regions")
+    host = out.cpu().numpy()
+    if host[n_loops * 6:n_loops * 6 + 3].tolist() != [edges, n_loops, n_points]:
+        raise RuntimeError(f"{what}: the two stages count differently")      # cannot happen
+    return (np.ascontiguousarray(host[:n_loops * 6].reshape(n_loops, 6)),
+            np.ascontiguousarray(host[n_loops * 6 + 3:].view(np.int32).reshape(n_points, 2)))
+
+
+def trace_class_regions(region, sizes, min_pixels=1, image_base=0):
+    """The outlines of labelled class regions, traced on the device (csrc/contours.hip; the inverse of
+    ``augment.polygon_masks_u8``).  ``region`` / ``sizes``: the int32 DEVICE tensors [N, H, W] of ``label_class_regions``; a
+    region is traced iff it has at least ``min_pixels`` pixels, the keep rule of ``describe_class_regions``.  Returns
+    (loops, points), numpy: loops int64 [L, 6] of LOOP_FIELDS -- ``image`` = image_base + the map's index, ``root`` = the
+    region's smallest linear index (the ``root`` of the defect records), ``leader`` = the loop's smallest crack edge id,
+    ``n_points`` / ``first_point`` = its rows of ``points``, ``area2`` = twice its signed area: > 0 for a region's one
+    outer loop, < 0 for a hole -- in ascending (image, leader); points int32 [P, 2] = (x, y) pixel centres in walk
+    order.  Pillow's ``ImageDraw.polygon`` of an outer loop's points fills the region with its holes closed
+    (``polygons.outlines`` groups the loops by region).  Integers and prefix sums throughout: two runs give the same
+    bytes.  At most 2^29 pixels.  Two host reads: {edges, loops, points}, which size the buffers, then the outlines."""
+    _require_cuda(region, sizes)
+    if region.dtype != torch.int32 or sizes.dtype != torch.int32 or region.shape != sizes.shape \
+            or region.device != sizes.device:
+        raise ValueError("trace_class_regions: region and sizes are the int32 tensors of label_class_regions")
+    min_pixels, image_base = int(min_pixels), int(image_base)
+    _trace_args("trace_class_regions", region)
+    if min_pixels < 1:
+        raise ValueError(f"trace_class_regions: min_pixels {min_pixels} is below 1")
+    if image_base < 0:
+        raise ValueError(f"trace_class_regions: image_base {image_base} is negative")
+    region, sizes = region.contiguous(), sizes.contiguous()
+    counted = _count_edges(region, sizes, min_pixels).tolist()
+    return _trace_counted(region, sizes, min_pixels, image_base, counted, "trace_class_regions")
 
 
 PAIR_FIELDS = ("image", "truth_root", "pred_root", "overlap")

@@ -30,13 +30,26 @@ circularity, holes; lengths in the image's own pixels, and with ``--pixel_size M
 ``--min_defect_length X`` / ``--min_defect_area X`` (mm and mm2 with ``--pixel_size``, image pixels otherwise; either implies
 ``--measure_shapes``) make ``counted`` also require that length and that area, and a ``size_rules`` block records them.
 With none of the four nothing new is launched and every output byte is as before.
+
+Build-only, off by default too (``seg_cli.POLYGON_FLAGS``, shared likewise): ``--save_polygons`` traces every defect's
+outline on the GPU (``evaluation.trace_class_regions``, csrc/contours.hip, on the labelling the records come from) and
+writes ``labels/<name>.txt`` beside ``masks/``: the defects with ``"counted": true`` as polygons in the Gear label format
+(``class - 1`` then ``(x + 0.5) / W (y + 0.5) / H`` per point: ``polygons.gear_label_lines``), which ``gear_dataset``, the
+trainers, ``analyze_gear_overlaps`` and the ``eval_*`` tools read and a labelling tool can correct.  Pillow's polygon of a
+written outline is the predicted region with its holes filled.  Every defect of ``predictions.json`` gains ``outline``
+([[x, y], ...] in frame pixels), ``outline_original`` and ``hole_outlines``, and a ``polygon_rules`` block records
+``--polygon_tolerance T`` (frame pixels, default 0; implies ``--save_polygons``), by which ``polygons.simplify_closed`` thins
+every outline.  Two limits come with the format: it has no holes, so a hole is filled when the file is loaded, and the
+loader resolves overlaps by class priority (spalling > pitting > scrape), not by nesting, so a lower-priority defect
+inside a higher one's hole is overwritten.  The GPU mask kernel of the loader takes at most 512 points a polygon: thin
+longer outlines with ``--polygon_tolerance``.
 """
 from __future__ import annotations
 
 import argparse
 import os
 
-from . import defects, seg_cli
+from . import defects, polygons, seg_cli
 from .seg_cli import HEAD_WEIGHT  # noqa: F401  (its home; importable from here as before)
 
 TASKS = {"gear": {"image_size": (512, 512), "class_names": ["background", "pitting", "spalling", "scrape"],
@@ -68,7 +81,7 @@ FLAGS = [("--task", dict(type=str, required=True, choices=sorted(TASKS))),
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Defects with boxes and confidence from unlabelled images (MI355X HIP path)")
-    for name, kw in FLAGS + seg_cli.SHAPE_FLAGS:
+    for name, kw in FLAGS + seg_cli.BUILD_FLAGS:
         ap.add_argument(name, **kw)
     args = ap.parse_args(argv)
     if args.image_size is None:
@@ -77,6 +90,7 @@ def parse_args(argv=None):
         ap.error("--image_size must be positive")
     seg_cli.check_predict_flags(ap, args)
     seg_cli.check_shape_flags(ap, args)
+    seg_cli.check_polygon_flags(ap, args)
     return args
 
 
@@ -105,11 +119,12 @@ def collate_images(samples):
     return (torch.stack(imgs) if same else list(imgs)), list(idx)
 
 
-def predict_batches(model, loader, size, num_classes, min_pixels, device, directions=None):
+def predict_batches(model, loader, size, num_classes, min_pixels, device, directions=None, contours=False):
     """Eval-mode pass over ``collate_images`` batches.  Yields per batch (indices, original sizes [(H0, W0)], normalised
     images, labels uint8 [N, H, W], frame mean confidence list, records with ``image`` = the dataset index).  The records
     and the means are the batch's host reads.  With ``directions`` (a number of Feret directions) the records are the
-    pair (records, shape records) of ``evaluation.describe_and_measure_class_regions``: one labelling, the same reads."""
+    pair (records, shape records) of ``evaluation.describe_and_measure_class_regions``: one labelling, the same reads.
+    With ``contours`` they are its four (records, shape records or None, loops, points), ``image`` mapped in the loops too."""
     import numpy as np
     import torch
     from . import sheets
@@ -125,13 +140,15 @@ def predict_batches(model, loader, size, num_classes, min_pixels, device, direct
             logits = model(x)
             labels, conf = sheets.seg_confidence(logits)
             means = per_image_stats(logits)["conf_mean"]
-            if directions is None:
+            if directions is None and not contours:
                 records = describe_class_regions(labels, num_classes, conf, min_pixels)
                 records[:, 0] = np.asarray(idx, np.int64)[records[:, 0]]
             else:
-                records = describe_and_measure_class_regions(labels, num_classes, conf, min_pixels, 0, directions)
-                for rec in records:
-                    rec[:, 0] = np.asarray(idx, np.int64)[rec[:, 0]]
+                records = describe_and_measure_class_regions(labels, num_classes, conf, min_pixels, 0, directions,
+                                                             contours=contours)
+                for rec in records[:3]:
+                    if rec is not None:
+                        rec[:, 0] = np.asarray(idx, np.int64)[rec[:, 0]]
             yield idx, sizes, x, labels, means.tolist(), records
 
 
@@ -151,14 +168,18 @@ def main(argv=None):
 
     mask_dir, overlay_dir, palette, palette_bytes = seg_cli.prediction_outputs(args, task, num_classes, device)
     loader = image_loader(paths, args.batch_size, args.num_workers)
-    originals, frame_means, records, shapes = [None] * len(paths), [None] * len(paths), [], []
-    rules = seg_cli.size_rules_of(args)
+    originals, frame_means, records, shapes, traced = [None] * len(paths), [None] * len(paths), [], [], {}
+    rules, polygon_rules = seg_cli.size_rules_of(args), seg_cli.polygon_rules_of(args)
     for idx, sizes, x, labels, means, rec in predict_batches(model, loader, args.image_size, num_classes,
                                                              args.min_region_pixels, device,
-                                                             None if rules is None else seg_cli.DIRECTIONS):
+                                                             None if rules is None else seg_cli.DIRECTIONS,
+                                                             polygon_rules is not None):
+        if polygon_rules is not None:
+            traced.update(polygons.outlines(rec[2], rec[3]))
         if rules is not None:
-            rec, shp = rec
-            shapes.append(shp)
+            shapes.append(rec[1])
+        if rules is not None or polygon_rules is not None:
+            rec = rec[0]
         records.append(rec)
         if args.mask_size == "frame":
             host = labels.cpu().numpy()
@@ -176,6 +197,11 @@ def main(argv=None):
     entries = defects.defect_entries(np.concatenate(records), class_names, args.image_size, originals,
                                      args.min_confidence, args.reject_classes,
                                      np.concatenate(shapes) if shapes else None, rules)
+    if polygon_rules is not None:
+        polygons.attach_outlines(entries, np.concatenate(records), traced, args.image_size, originals,
+                                 args.polygon_tolerance)
+        for i, e in enumerate(entries):
+            seg_cli.save_label_file(args, names[i], e, args.image_size)
     images = []
     for i, e in enumerate(entries):
         pixels = {name: 0 for name in class_names[1:]}

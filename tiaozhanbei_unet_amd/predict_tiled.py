@@ -38,12 +38,13 @@ FLAGS = [(name, kw) for name, kw in PREDICT_FLAGS if name not in ("--image_size"
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="predict at full resolution: overlapping tiles blended on the GPU")
-    for name, kw in FLAGS + seg_cli.SHAPE_FLAGS:
+    for name, kw in FLAGS + seg_cli.BUILD_FLAGS:
         ap.add_argument(name, **kw)
     args = ap.parse_args(argv)
     seg_cli.check_tile_scale(ap, args, TASKS[args.task]["image_size"])
     seg_cli.check_predict_flags(ap, args)
     seg_cli.check_shape_flags(ap, args)
+    seg_cli.check_polygon_flags(ap, args)
     return args
 
 
@@ -79,9 +80,9 @@ def main(argv=None):
         original = (int(image.shape[0]), int(image.shape[1]))
         x = load_frame(image, working_frame(original, args.scale), device)
         labels, conf, plan = predictor(x)
-        records, shapes = seg_cli.describe_regions(args, labels[None], num_classes, conf[None])
+        records, shapes, traced = seg_cli.describe_regions(args, labels[None], num_classes, conf[None])
         images[i] = seg_cli.save_frame_prediction(args, outputs, paths[i], names[i], original, labels, conf, records,
-                                                  class_names, {"tiling": plan}, frame=x, shapes=shapes)
+                                                  class_names, {"tiling": plan}, frame=x, shapes=shapes, traced=traced)
 
     def tiles(im):
         return f"in {len(im['tiling']['origins_y']) * len(im['tiling']['origins_x'])} tiles"

@@ -49,12 +49,13 @@ def check_views(ap, args, scale=1.0):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="predict at full resolution from several views merged on the GPU")
-    for name, kw in FLAGS + seg_cli.SHAPE_FLAGS:
+    for name, kw in FLAGS + seg_cli.BUILD_FLAGS:
         ap.add_argument(name, **kw)
     args = ap.parse_args(argv)
     seg_cli.check_tile_scale(ap, args, TASKS[args.task]["image_size"])
     seg_cli.check_predict_flags(ap, args)
     seg_cli.check_shape_flags(ap, args)
+    seg_cli.check_polygon_flags(ap, args)
     check_views(ap, args, args.scale)
     return args
 
@@ -88,12 +89,12 @@ def main(argv=None):
         original = (int(image.shape[0]), int(image.shape[1]))
         frame_hw = working_frame(original, args.scale)
         labels, conf, agreement, plan = ensemble(image, frame_hw)
-        records, shapes = seg_cli.describe_regions(args, labels[None], num_classes, conf[None])
+        records, shapes, traced = seg_cli.describe_regions(args, labels[None], num_classes, conf[None])
         agree = agreement_means(labels[None], agreement[None], len(views), num_classes, args.min_region_pixels, records)
         frame = load_frame(image, frame_hw, device) if args.save_overlays else None
         images[i] = seg_cli.save_frame_prediction(args, outputs, paths[i], names[i], original, labels, conf, records,
                                                   class_names, {"tiling": plan[0]["tiling"], "views": plan}, frame=frame,
-                                                  defect_extras={"mean_view_agreement": agree}, shapes=shapes)
+                                                  defect_extras={"mean_view_agreement": agree}, shapes=shapes, traced=traced)
     return seg_cli.write_predictions(args, class_names, images, middle=lambda im: f"in {len(im['views'])} views")
 
 

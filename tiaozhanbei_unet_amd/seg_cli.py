@@ -8,11 +8,13 @@ the ``eval_*`` side   ``parse_dataset_args`` (``--dataset`` first, then that dat
                       checkpoint), ``tiled_predictor``, the full-resolution walk ``full_resolution_images`` /
                       ``normalized_frame``, and the labelled-prediction sources ``frame_predictions`` /
                       ``tiled_predictions`` (``labelled_predictions`` picks one by ``--tiled``)
-the ``predict*`` side the refusals ``check_predict_flags`` and ``check_tile_scale``, the shape flags (``SHAPE_FLAGS``,
-                      ``check_shape_flags``, ``size_rules_of``, ``describe_regions``), ``open_prediction`` (images, state
-                      dict, classes, banner, model), ``prediction_outputs`` (``masks/``, ``overlays/``, palettes),
-                      ``save_mask`` / ``save_overlay``, ``save_frame_prediction`` (one image's entry, mask and overlay)
-                      and ``write_predictions`` (``predictions.json`` and the printed lines)
+the ``predict*`` side the refusals ``check_predict_flags`` and ``check_tile_scale``, the build-only flags ``BUILD_FLAGS``:
+                      the shape flags (``SHAPE_FLAGS``, ``check_shape_flags``, ``size_rules_of``) and the polygon flags
+                      (``POLYGON_FLAGS``, ``check_polygon_flags``, ``polygon_rules_of``, ``save_label_file``), both served
+                      by ``describe_regions``; ``open_prediction`` (images, state dict, classes, banner, model),
+                      ``prediction_outputs`` (``masks/``, ``overlays/``, ``labels/``, palettes), ``save_mask`` /
+                      ``save_overlay``, ``save_frame_prediction`` (one image's entry, mask, overlay and label file) and
+                      ``write_predictions`` (``predictions.json`` and the printed lines)
 
 ``torch`` and the kernels are imported inside the functions: parsing flags and ``--help`` need neither them nor a GPU.
 """
@@ -222,13 +224,57 @@ def size_rules_of(args):
     return defects.size_rules(args.pixel_size, args.min_defect_length, args.min_defect_area)
 
 
+# build-only: every defect's outline as a polygon in the Gear label format (csrc/contours.hip, polygons.py).  Absent by
+# default, like the shape flags: a run that gives neither has the ``args`` of before and launches nothing new.
+_POLYGON_LIMITS = ("the format has no holes (a hole is filled when the file is loaded) and the loader resolves overlaps by "
+                   "class priority, spalling > pitting > scrape, not by nesting (a lower class inside a higher one's hole "
+                   "is overwritten)")
+POLYGON_FLAGS = [("--save_polygons", dict(action="store_true", default=argparse.SUPPRESS,
+                                          help="write labels/<name>.txt, the counted defects' outlines as Gear label "
+                                               "polygons, and add outline / hole_outlines to every defect; "
+                                               + _POLYGON_LIMITS)),
+                 ("--polygon_tolerance", dict(type=float, default=argparse.SUPPRESS, metavar="T",
+                                              help="thin every outline (Douglas-Peucker) by at most T frame pixels, "
+                                                   "default 0: every corner; implies --save_polygons"))]
+BUILD_FLAGS = SHAPE_FLAGS + POLYGON_FLAGS
+
+
+def check_polygon_flags(ap, args):
+    """The rules of ``POLYGON_FLAGS``.  With neither given ``args`` stays as it is; otherwise both are set."""
+    if not any(hasattr(args, name[2:]) for name, _ in POLYGON_FLAGS):
+        return
+    args.save_polygons = True
+    args.polygon_tolerance = getattr(args, "polygon_tolerance", 0.0)
+    if not 0.0 <= args.polygon_tolerance < float("inf"):
+        ap.error("--polygon_tolerance must be at least 0")
+
+
+def polygon_rules_of(args):
+    """the ``polygon_rules`` block of ``predictions.json``, or None when no polygons are written"""
+    if not getattr(args, "save_polygons", False):
+        return None
+    return {"tolerance": args.polygon_tolerance, "labels": "labels/<name>.txt: one line per counted defect, class - 1 then "
+            "(x + 0.5) / W (y + 0.5) / H of its outline's pixel centres", "limits": _POLYGON_LIMITS}
+
+
 def describe_regions(args, labels, num_classes, conf):
-    """(records, shape records or None) of label maps (N, H, W) for a predict tool: ``describe_class_regions``, and with
-    the shape flags ``measure_class_regions`` on the same labelling (one labelling, the same two host reads)"""
-    from . import evaluation
-    if size_rules_of(args) is None:
-        return evaluation.describe_class_regions(labels, num_classes, conf, args.min_region_pixels), None
-    return evaluation.describe_and_measure_class_regions(labels, num_classes, conf, args.min_region_pixels, 0, DIRECTIONS)
+    """(records, shape records or None, outlines or None) of label maps (N, H, W) for a predict tool:
+    ``describe_class_regions``; with the shape flags ``measure_class_regions`` and with the polygon flags
+    ``trace_class_regions`` (as ``polygons.outlines``) on the same labelling: the maps are labelled once."""
+    from . import evaluation, polygons
+    shaped, traced = size_rules_of(args) is not None, polygon_rules_of(args) is not None
+    if not shaped and not traced:
+        return evaluation.describe_class_regions(labels, num_classes, conf, args.min_region_pixels), None, None
+    got = evaluation.describe_and_measure_class_regions(labels, num_classes, conf, args.min_region_pixels, 0,
+                                                        DIRECTIONS if shaped else None, contours=traced)
+    return (got[0], got[1], polygons.outlines(got[2], got[3])) if traced else (got[0], got[1], None)
+
+
+def save_label_file(args, name, entry, frame_hw):
+    """``labels/<name>.txt`` of one image entry whose defects carry their outlines: its counted defects"""
+    from . import polygons
+    with open(os.path.join(args.output_dir, "labels", name + ".txt"), "w") as f:
+        f.write("".join(line + "\n" for line in polygons.entry_label_lines(entry, frame_hw)))
 
 
 def check_tile_scale(ap, args, default_tile):
@@ -280,11 +326,14 @@ def open_prediction(args, task, title, kernel):
 
 
 def prediction_outputs(args, task, num_classes, device):
-    """``{output_dir}/masks`` and, with ``--save_overlays``, ``{output_dir}/overlays``, made; the task's class palette on
-    the device and as the bytes of a Pillow palette.  Returns (mask_dir, overlay_dir, palette, palette_bytes)."""
+    """``{output_dir}/masks`` and, with ``--save_overlays``, ``{output_dir}/overlays`` and, with the polygon flags,
+    ``{output_dir}/labels``, made; the task's class palette on the device and as the bytes of a Pillow palette.  Returns
+    (mask_dir, overlay_dir, palette, palette_bytes)."""
     from . import sheets
     mask_dir = os.path.join(args.output_dir, "masks")
     os.makedirs(mask_dir, exist_ok=True)
+    if polygon_rules_of(args) is not None:
+        os.makedirs(os.path.join(args.output_dir, "labels"), exist_ok=True)
     overlay_dir = os.path.join(args.output_dir, "overlays")
     if args.save_overlays:
         os.makedirs(overlay_dir, exist_ok=True)
@@ -308,13 +357,14 @@ def save_overlay(frame, labels, palette, path):
 
 
 def save_frame_prediction(args, outputs, path, name, original, labels, conf, records, class_names, plans, frame=None,
-                          defect_extras=None, shapes=None):
+                          defect_extras=None, shapes=None, traced=None):
     """One image of ``predict_tiled`` / ``predict_views``: its ``predictions.json`` entry from the ``records`` of its
     label map (H, W) and confidence, ``masks/<name>.png`` at the image's ``original`` size (NEAREST when the frame
     differs), and with ``--save_overlays`` the overlay on ``frame``, the normalised (3, H, W) frame.  ``plans``: the keys
     that follow ``frame_size`` in the entry; ``defect_extras``: {key: one value per listed defect, in the records' order}.
     ``outputs``: what ``prediction_outputs`` returned; ``shapes``: the records' shape records from ``describe_regions``
-    (None unless the shape flags are given).  Returns the entry."""
+    (None unless the shape flags are given); ``traced``: its outlines (None unless the polygon flags are given), which
+    go into the defects and, for the counted ones, into ``labels/<name>.txt``.  Returns the entry."""
     from . import augment, defects
     mask_dir, overlay_dir, palette, palette_bytes = outputs
     frame_hw = (int(labels.shape[0]), int(labels.shape[1]))
@@ -325,6 +375,10 @@ def save_frame_prediction(args, outputs, path, name, original, labels, conf, rec
         for key, values in (defect_extras or {}).items():
             d[key] = values[k]
         pixels[d["class_name"]] += d["pixels"]
+    if traced is not None:
+        from . import polygons
+        polygons.attach_outlines([entry], records, traced, frame_hw, [original], args.polygon_tolerance)
+        save_label_file(args, name, entry, frame_hw)
     mask = labels if frame_hw == original else augment.resize_nearest_u8(labels[None, :, :, None], *original)[0, :, :, 0]
     save_mask(mask.cpu().numpy(), palette_bytes, os.path.join(mask_dir, name + ".png"))
     if args.save_overlays:
@@ -334,16 +388,20 @@ def save_frame_prediction(args, outputs, path, name, original, labels, conf, rec
 
 
 def write_predictions(args, class_names, images, middle=None, frame_size=None):
-    """``{output_dir}/predictions.json`` (args, class_names, [frame_size,] [size_rules,] images, summary) and the printed
+    """``{output_dir}/predictions.json`` (args, class_names, [frame_size,] [size_rules,] [polygon_rules,] images, summary)
+    and the printed
     lines: one per image -- decision, name, then the frame size and ``middle(entry)`` (such as "in 4 tiles") when
     ``middle`` is given, then its first four defects, with their Feret length when shapes were measured -- and the
-    totals.  ``size_rules`` (``size_rules_of``) is there only with the shape flags.  Returns the file's path."""
+    totals.  ``size_rules`` (``size_rules_of``) is there only with the shape flags, ``polygon_rules`` (``polygon_rules_of``)
+    only with the polygon flags.  Returns the file's path."""
     from . import defects
     summary = defects.summarize(images, class_names)
     shared = {} if frame_size is None else {"frame_size": list(frame_size)}
     rules = size_rules_of(args)
     if rules is not None:
         shared["size_rules"] = rules
+    if polygon_rules_of(args) is not None:
+        shared["polygon_rules"] = polygon_rules_of(args)
     unit = "mm" if rules and rules["pixel_size"] is not None else "px"
     length = "feret_length_mm" if unit == "mm" else "feret_length"
     out_path = os.path.join(args.output_dir, "predictions.json")
