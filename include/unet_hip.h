@@ -1027,6 +1027,61 @@ int32_t unet_affine_crop_u8(const uint8_t* src, int64_t src_bytes, const int64_t
                             int32_t n_images, int32_t c, const unet_crop_desc* desc, int32_t n_crops, int32_t out_h,
                             int32_t out_w, int32_t mode, int32_t fill, uint8_t* dst, void* stream);
 
+/* Copy-paste crops (train_gear_paste; no reference counterpart; Ghiasi et al., CVPR 2021): the bilinear image crop and
+ * the nearest mask crop of unet_affine_crop_u8 written together in ONE launch, with labelled defects of any image of the
+ * batch pasted into them on the way out (csrc/paste.hip, restated in numpy int64 by tests/_paste_ref.py).
+ * Buffers: images are 3-channel, packed exactly as for unet_affine_crop_u8 (src, src_bytes, src_offset, src_hw); mask i is
+ * [h][w] bytes at masks + mask_offset[i] with the same (h, w) = src_hw[i], inside masks[0, mask_bytes).  desc[k] is crop
+ * k as above.  paste_start is [n_crops + 1], ascending: crop k owns paste[paste_start[k] .. paste_start[k + 1] - 1],
+ * applied in that order, so a later one lies on top; at most the first UNET_PASTE_MAX of them are looked at.  dst_image:
+ * [n_crops][out_h][out_w][3]; dst_mask: [n_crops][out_h][out_w].  All are DEVICE arrays.  n_pastes may be 0, and paste
+ * may then be NULL.
+ * Output pixel (y, x) of crop k, all in int64:
+ *  1. Base.  pix[ch] is the bilinear rule above on image desc[k].image with `fill`; lab is the nearest rule above on that
+ *     image's mask with `ignore`; inside is that rule's inside.  With no pastes the two outputs are the bytes of the two
+ *     unet_affine_crop_u8 launches.
+ *  2. For each paste j of the crop, in order.  It is skipped when !inside (nothing is pasted onto fill), when (x, y) is
+ *     outside dst, or when the donor image or its mask is not readable.  box is first intersected with the donor image.
+ *     u = b0 x + b1 y + b2, v = b3 x + b4 y + b5; nx = u >> 16, ny = v >> 16.  member(px, py) is true iff (px, py) lies
+ *     in the box and m = mask[py][px] has m != 0 && m != ignore.  If member(nx, ny): lab = mask[ny][nx].  The four
+ *     bilinear taps and fx, fy are the crop rule's: ub = u - 32768, x0 = ub >> 16, x1 = x0 + 1, likewise y.  A tap is a
+ *     member by its own position (x0 or x1, y0 or y1, BEFORE the clamp: a tap outside the donor image is never a
+ *     member); its value is read at the clamped position.  w00 = (256 - fx)(256 - fy), w01 = fx (256 - fy), w10 =
+ *     (256 - fx) fy, w11 = fx fy; alpha = the sum of w_ij over the member taps, 0..65536.  If alpha > 0: d[ch] = the
+ *     crop rule's bilinear value of the donor image, pix[ch] = (alpha d[ch] + (65536 - alpha) pix[ch] + 32768) >> 16.
+ * So: a paste matrix that maps pixel centres to pixel centres copies donor bytes and donor labels exactly where the
+ * donor mask is set inside the box, and changes nothing elsewhere; the image gets a one-pixel soft edge (0 < alpha <
+ * 65536 where member and other taps mix); the label is that of the donor pixel the image pixel mostly came from (the
+ * nearest one); and dst_mask == ignore exactly where the base crop left its image.
+ * Guards: the contract of unet_affine_crop_u8, per buffer.  Whatever the device tables hold, no load leaves
+ * src[0, src_bytes) or masks[0, mask_bytes) and no store leaves the outputs.  A base image index outside 0..n_images-1
+ * gives a crop of all `fill` / `ignore`; a base image that is not readable (src_offset < 0, a side <= 0, src_offset +
+ * 3 h w > src_bytes) is all `fill`, a base mask that is not readable (the same test on mask_offset, h w, mask_bytes) all
+ * `ignore`, and a crop with either takes no paste.  A paste whose donor index is outside 0..n_images-1, or whose donor
+ * image or mask is not readable, is skipped, that paste only.  Paste indices are clamped into [0, n_pastes); a
+ * paste_start that descends owns no paste.
+ * Refused on the host before any launch: a NULL src, src_offset, src_hw, masks, mask_offset, desc, paste_start,
+ * dst_image or dst_mask, or a NULL paste with n_pastes > 0 (UNET_ERR_BAD_ARG); n_pastes < 0, fill or ignore outside
+ * 0..255, out_h or out_w outside 1..4096, n_crops or n_images outside 1..65535, src_bytes or mask_bytes <= 0
+ * (UNET_ERR_UNSUPPORTED).
+ * A block works on a segment of one output row of one crop, so every descriptor, guard and the test of the row and
+ * segment against dst is wave-uniform.  When out_w is a multiple of 4 and both outputs are 4-byte aligned a lane owns 4
+ * consecutive pixels and stores whole dwords (three for the image, one for the mask), else one pixel with byte stores.
+ * No atomics, no LDS, no floating point.  Allocates nothing, does not synchronise. */
+#define UNET_PASTE_MAX 8
+typedef struct unet_paste_desc {   /* 64 bytes */
+  int32_t image;      /* donor image */
+  int32_t b[6];       /* crop pixel (x, y) -> donor source point, 16.16, b2 / b5 holding the half-pixel terms */
+  int32_t box[4];     /* x0, y0, x1, y1, half-open, donor pixels: only donor pixels inside it can be members */
+  int32_t dst[4];     /* x0, y0, x1, y1, half-open, crop pixels: the paste is looked at only inside it */
+  int32_t reserved;
+} unet_paste_desc;
+int32_t unet_paste_crop_u8(const uint8_t* src, int64_t src_bytes, const int64_t* src_offset, const int32_t* src_hw,
+                           int32_t n_images, const uint8_t* masks, int64_t mask_bytes, const int64_t* mask_offset,
+                           const unet_crop_desc* desc, int32_t n_crops, const int32_t* paste_start,
+                           const unet_paste_desc* paste, int32_t n_pastes, int32_t out_h, int32_t out_w,
+                           int32_t fill, int32_t ignore, uint8_t* dst_image, uint8_t* dst_mask, void* stream);
+
 /* One fused step over a flat fp32 parameter arena: L2-coupled weight decay, bias correction,
  * gradient pre-scale (1/world_size under data parallelism). step is 1-based.  The betas are doubles so that 1 - beta is
  * formed in double before rounding to fp32, as torch.optim.Adam's `value=1 - beta2` is. */

@@ -65,6 +65,12 @@ class CropDesc(C.Structure):
 CROP_NEAREST, CROP_BILINEAR = 0, 1
 
 
+class PasteDesc(C.Structure):
+    """struct unet_paste_desc"""
+    _fields_ = [("image", C.c_int32), ("b", C.c_int32 * 6), ("box", C.c_int32 * 4), ("dst", C.c_int32 * 4),
+                ("reserved", C.c_int32)]
+
+
 class MergeView(C.Structure):
     """struct unet_merge_view"""
     _fields_ = [("logits", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("flip_x", C.c_int32), ("flip_y", C.c_int32)]
@@ -204,6 +210,7 @@ SIGNATURES = {
     "unet_tile_blend": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "unet_view_merge": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "unet_affine_crop_u8":(_i, [_p, _l, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "unet_paste_crop_u8": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "unet_adam_chunk_elems": (_i, []),
     "unet_adam_multi": (_i, [_p, _p, _i, _f, _d, _d, _f, _f, _f, _i, _i, _p]),
     "unet_adam_step": (_i, [_p, _p, _p, _p, _l, _f, _d, _d, _f, _f, _f, _i, _p]),

@@ -23,6 +23,7 @@
 // are byte-wide loads, four per output byte of a bilinear crop; measured (profiles/README.md) the kernel writes 0.3 to
 // 0.4 TB/s, far from the HBM rate, which costs a trainer step 0.1 ms per 32 crops of 512 x 512.
 #include "common.h"
+#include "croptaps.h"                              // Taps, taps_of, sample: shared with paste.hip
 
 namespace {
 
@@ -38,52 +39,6 @@ struct CropParams {
   uint8_t* dst;
   int n_images, n_crops, out_h, out_w, fill;
 };
-
-// the sample of one output pixel: where its taps lie (element offsets of the pixel's first channel) and their weights
-struct Taps {
-  bool inside;
-  long long o00, o01, o10, o11;                        // nearest: o00 alone
-  int fx, fy;
-};
-
-template <int MODE>
-__device__ __forceinline__ Taps taps_of(long long u, long long v, int h, int w, int c) {
-  Taps t;
-  const long long nx = u >> 16, ny = v >> 16;
-  t.inside = nx >= 0 && nx < w && ny >= 0 && ny < h;
-  t.o00 = t.o01 = t.o10 = t.o11 = 0;
-  t.fx = t.fy = 0;
-  if (!t.inside) return t;
-  if constexpr (MODE == 0) {
-    t.o00 = (ny * w + nx) * c;
-  } else {
-    const long long ub = u - 32768, vb = v - 32768;
-    long long x0 = ub >> 16, y0 = vb >> 16;
-    long long x1 = x0 + 1, y1 = y0 + 1;
-    t.fx = (int)((ub & 0xFFFF) >> 8);
-    t.fy = (int)((vb & 0xFFFF) >> 8);
-    const long long wm = w - 1, hm = h - 1;
-    x0 = x0 < 0 ? 0 : (x0 > wm ? wm : x0);
-    x1 = x1 < 0 ? 0 : (x1 > wm ? wm : x1);
-    y0 = y0 < 0 ? 0 : (y0 > hm ? hm : y0);
-    y1 = y1 < 0 ? 0 : (y1 > hm ? hm : y1);
-    t.o00 = (y0 * w + x0) * c; t.o01 = (y0 * w + x1) * c;
-    t.o10 = (y1 * w + x0) * c; t.o11 = (y1 * w + x1) * c;
-  }
-  return t;
-}
-
-template <int MODE>
-__device__ __forceinline__ unsigned sample(const uint8_t* __restrict__ img, const Taps& t, int ch, int fill) {
-  if (!t.inside) return (unsigned)fill;
-  if constexpr (MODE == 0) {
-    return img[t.o00 + ch];
-  } else {
-    const int p00 = img[t.o00 + ch], p01 = img[t.o01 + ch], p10 = img[t.o10 + ch], p11 = img[t.o11 + ch];
-    const int top = (256 - t.fx) * p00 + t.fx * p01, bot = (256 - t.fx) * p10 + t.fx * p11;
-    return (unsigned)(((256 - t.fy) * top + t.fy * bot + 32768) >> 16);
-  }
-}
 
 // blockIdx.x = segment of the row, blockIdx.y = output row y, blockIdx.z strides over the crops: no division by a
 // run-time value anywhere.  C = channels; V = bytes of the row a lane writes: 4 (one dword) or 1.

@@ -43,6 +43,12 @@ def parse_args(argv=None):
     for name, kw in FLAGS:
         ap.add_argument(name, **kw)
     args = ap.parse_args(argv)
+    check_args(ap, args)
+    return args
+
+
+def check_args(ap, args):
+    """the refusals of this trainer's own flags (``train_gear_paste`` shares them)"""
     if not all(1 <= v <= 4096 for v in args.crop_size):
         ap.error("--crop_size sides must lie in 1..4096")
     if args.crops_per_image < 1:
@@ -57,7 +63,6 @@ def parse_args(argv=None):
         ap.error("--degrees must lie in 0..180")
     if not 0 <= args.min_overlap < min(args.crop_size):
         ap.error("--min_overlap must be at least 0 and smaller than both crop sides")
-    return args
 
 
 def check_image_sizes(datasets):
@@ -94,13 +99,22 @@ def validate_tiled(model, criterion, loader, predictor, num_classes, device):
     return {"loss": float(total) / max(count, 1), "metrics": metrics.compute_all_metrics()}
 
 
-def main(argv=None):
-    args = parse_args(argv)
+def crop_preprocess(args, crop):
+    """the training batches' ``GearCropPreprocess`` of this trainer's flags"""
+    from .crops import GearCropPreprocess
+    return GearCropPreprocess(crop, train=True, crops_per_image=args.crops_per_image, scale_range=tuple(args.scale_range),
+                              degrees=args.degrees, defect_fraction=args.defect_fraction, seed=args.seed)
+
+
+def run(args, prefix, make_preprocess):
+    """The trainer behind ``train_gear_crops`` and ``train_gear_paste``: the experiment lies under
+    ``{save_dir}/{prefix}_{model}_{ts}``, ``make_preprocess(args, crop)`` makes the training batches'
+    ``GearCropPreprocess``.  Returns the experiment directory."""
     from .train_gear import build_seg_model, fit_segmentation, require_gpu
     device = require_gpu(args)
     import numpy as np
     import torch
-    from .crops import IGNORE_INDEX, GearCropPreprocess
+    from .crops import IGNORE_INDEX
     from .gear_dataset import collate_raw, get_gear_dataloaders, write_synthetic_gear
     from .tiling import TiledPredictor
     from .utils import create_output_dirs
@@ -111,7 +125,7 @@ def main(argv=None):
     if args.synthetic:
         args.data_root = write_synthetic_gear(tempfile.mkdtemp(prefix="gear_syn_"), seed=args.seed)
     stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
-    exp_dir = os.path.join(args.save_dir, f"gear_crops_{args.model}_{stamp}")
+    exp_dir = os.path.join(args.save_dir, f"{prefix}_{args.model}_{stamp}")
     dirs = create_output_dirs(exp_dir)
     print(f"Using device: {device}\nExperiment directory: {exp_dir}")
     with open(os.path.join(exp_dir, "args.json"), "w") as f:
@@ -138,19 +152,23 @@ def main(argv=None):
           f"+-{args.degrees} degrees, {args.defect_fraction:.2f} on defects")
 
     model = build_seg_model(args, num_classes, device)
-    train_pre = GearCropPreprocess(crop, train=True, crops_per_image=args.crops_per_image,
-                                   scale_range=tuple(args.scale_range), degrees=args.degrees,
-                                   defect_fraction=args.defect_fraction, seed=args.seed)
+    train_pre = make_preprocess(args, crop)
     predictor = TiledPredictor(model, crop, args.min_overlap, args.batch_size)
 
     def train_batches(loader):
         for images, polys, sizes, _paths in loader:
             yield train_pre(images, polys, sizes, device=device)
+        if train_pre.paste is not None:
+            print(train_pre.paste.report())
 
     return fit_segmentation(args, exp_dir, dirs, model, train_loader, val_loader, num_classes, device, train_batches, None,
                             ignore_index=IGNORE_INDEX,
                             validate=lambda m, criterion: validate_tiled(m, criterion, val_loader, predictor, num_classes,
                                                                          device))
+
+
+def main(argv=None):
+    return run(parse_args(argv), "gear_crops", crop_preprocess)
 
 
 if __name__ == "__main__":
