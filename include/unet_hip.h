@@ -507,6 +507,39 @@ int32_t unet_match_class_regions(const uint8_t* truth, const int32_t* truth_regi
                                  int32_t* truth_records, int32_t* pred_records, int64_t capacity,
                                  int64_t* record_counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Groups of class regions (no reference counterpart; csrc/groups.hip, restated in numpy by tests/_groups_ref.py): which
+ * regions of a prediction belong to one defect.  A U-Net breaks a thin scratch into a row of fragments a few pixels
+ * apart; grouped, they are measured, filtered and paired as one.  classes, region and sizes are what
+ * unet_label_class_regions takes and makes; gap in 1..32, gap_sq = gap * gap; min_pixels >= 1.  A fragment is a region
+ * with size >= min_pixels; smaller regions are dropped before grouping, so they link nothing and join nothing.  Two
+ * fragments of the same image and class are linked iff they hold pixels p, q with
+ * (py - qy)^2 + (px - qx)^2 <= gap_sq; a group is a connected component of the link graph (linking is transitive), and
+ * fragments of different classes or images are never linked.  Two distinct regions of one class are at least 2 apart,
+ * so gap = 1 gives every fragment its own group.
+ * group[n][h][w] (int32) = 1 + the smallest fragment root index y * w + x of the pixel's group (itself a pixel of the
+ * group), group_sizes[n][h][w] (int32) = the group's pixel count at every one of its pixels; both 0 on background and
+ * on dropped regions: (group, group_sizes) stands in for (region, sizes) in unet_describe_class_regions,
+ * unet_measure_class_regions and unet_region_pairs.  counts[n][num_classes] (int64, device) = groups per image and
+ * class (column 0 stays as it is) is ADDED to: zero it first.  Every fragment yields one record of 5 int64
+ * {image_base + image, class, fragment root, group root, fragment size} at the slot that an atomic add on
+ * fragment_count[1] (int64, device; ADDED to: zero it first) hands out: the order is arbitrary, sort by (image, group
+ * root, fragment root).  capacity = records that the buffer holds; a record past it is counted and not written.
+ * Four launches: the fragment roots link to themselves in a per-pixel link plane; a workgroup per 32 x 32 tile stages
+ * the tile and its halo in LDS, and every edge pixel of a fragment (one with a 4-neighbour inside the frame that is not
+ * of its region) scans the half-disc dy > 0, or dy == 0 and dx > 0, and unites its fragment root with that of every cell
+ * of its class and another region (atomicMin on the links; rows do not wrap); every fragment root finds its group root
+ * and adds its size there; every pixel takes its group's root and count.  Integer atomics only: apart from the record
+ * order the outputs are a function of the inputs alone.  Any h, w >= 1; n < 65536, n h w <= 2^31 - 1,
+ * 2 <= num_classes <= 255 and image_base + n <= 2^31 - 1, else UNET_ERR_UNSUPPORTED (and the workspace query returns 0);
+ * gap outside 1..32, min_pixels < 1, a negative image_base or capacity or a NULL pointer is UNET_ERR_BAD_ARG; all of
+ * that before any launch.  Allocates nothing, does not synchronise. */
+size_t unet_group_class_regions_workspace(int64_t n, int64_t h, int64_t w, int32_t num_classes);
+int32_t unet_group_class_regions(const uint8_t* classes, const int32_t* region, const int32_t* sizes, int64_t n,
+                                 int64_t h, int64_t w, int32_t num_classes, int32_t gap, int32_t min_pixels,
+                                 int32_t image_base, int32_t* group, int32_t* group_sizes, int64_t* counts,
+                                 int64_t* fragments, int64_t capacity, int64_t* fragment_count, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 /* Overlaps of region pairs (no reference counterpart: the sparse contingency table between two region labellings, from
  * which detection against a confidence threshold, "found with the wrong class" and IoU matching are host arithmetic).
  * truth_region / pred_region: two `region` arrays of unet_label_class_regions, int32 [n][h][w], 1 + root index, 0 on

@@ -165,6 +165,8 @@ SIGNATURES = {
     "unet_label_class_regions": (_i, [_p, _l, _l, _l, _i, _p, _p, _p, _p, _z, _p]),
     "unet_match_class_regions_workspace": (_z, [_l, _l, _l, _i]),
     "unet_match_class_regions": (_i, [_p, _p, _p, _p, _p, _p, _l, _l, _l, _i, _i, _i, _p, _p, _l, _p, _p, _z, _p]),
+    "unet_group_class_regions_workspace": (_z, [_l, _l, _l, _i]),
+    "unet_group_class_regions": (_i, [_p, _p, _p, _l, _l, _l, _i, _i, _i, _i, _p, _p, _p, _p, _l, _p, _p, _z, _p]),
     "unet_region_pair_bound": (_i, [_p, _p, _l, _l, _l, _p, _p]),
     "unet_region_pairs_workspace": (_z, [_l, _l]),
     "unet_region_pairs": (_i, [_p, _p, _l, _l, _l, _l, _i, _p, _l, _p, _p, _p, _z, _p]),

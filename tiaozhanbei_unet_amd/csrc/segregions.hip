@@ -22,11 +22,13 @@
 // root, so every output but the record order is a function of the two label maps alone.
 #include "labeller.h"
 #include "segpixel.h"
+#include "slots.h"
 
 namespace {
 
 using namespace uf;                                   // tiles, links, find_root (unionfind.h); the bodies (labeller.h)
 using segpx::class_of;
+using slots::wave_slot;
 constexpr int FIN_ITEMS = 8;                           // pixels per lane of the per-pixel passes
 constexpr int REC = 5;                                 // int32 fields of a record
 static_assert(PX_THREADS == 256, "finish_class_regions keeps one counter per thread and class");
@@ -165,17 +167,6 @@ __global__ __launch_bounds__(PX_THREADS) void count_class_hits(const MatchParams
     wave_add(A.thit + base, tr, hit, lane);
     wave_add(A.phit + base, pr, hit, lane);
   }
-}
-
-// slot of every lane that is on in the record buffer counted by *counter: one atomicAdd per wave
-__device__ __forceinline__ long long wave_slot(unsigned long long* counter, bool on, int lane) {
-  const unsigned long long m = __ballot(on);
-  if (!m) return -1;                                   // wave-uniform
-  const int first = __ffsll((long long)m) - 1;
-  unsigned long long at = 0;
-  if (lane == first) at = atomicAdd(counter, (unsigned long long)__popcll(m));
-  at = __shfl(at, first);
-  return on ? (long long)(at + __popcll(m & ((1ull << lane) - 1ull))) : -1;
 }
 
 __device__ __forceinline__ void put_record(int* rec, long long slot, long long capacity, int image, int cls, int root,

@@ -8,6 +8,8 @@
 //                   the lanes that remain commit on their own.  The first such sum of each of the block's waves goes
 //                   through LDS, where one thread folds the waves that share a slot.  A region that fills the frame costs
 //                   one commit per block; a wave of many small regions falls back to per-lane commits.
+//   wave_slot       a slot in a record buffer for every lane that has a record to append (segregions.hip's region
+//                   records, groups.hip's fragment records): one atomicAdd per wave on the device-side count.
 // What the caller brings: a struct Acc with an int `slot` (< 0: nothing) and, in the namespace of Acc (the including
 // file's unnamed one: flush_by_slot calls them unqualified and argument-dependent lookup finds them there),
 // fold(Acc&, const Acc&) and wave_fold(Acc, bool on) -> the fold over the lanes with `on` (every lane calls it); and a
@@ -20,6 +22,17 @@ namespace slots {
 
 constexpr int LEADERS = 4;                             // slots per wave that are reduced with shuffles
 constexpr int PX_WAVES = uf::PX_THREADS / WAVE;
+
+// slot of every lane that is on in the record buffer counted by *counter: one atomicAdd per wave
+__device__ __forceinline__ long long wave_slot(unsigned long long* counter, bool on, int lane) {
+  const unsigned long long m = __ballot(on);
+  if (!m) return -1;                                   // wave-uniform
+  const int first = __ffsll((long long)m) - 1;
+  unsigned long long at = 0;
+  if (lane == first) at = atomicAdd(counter, (unsigned long long)__popcll(m));
+  at = __shfl(at, first);
+  return on ? (long long)(at + __popcll(m & ((1ull << lane) - 1ull))) : -1;
+}
 
 // a: what the thread still holds (a.slot < 0: nothing).  Every thread of the block calls this, at the kernel's end.
 template <class Acc, class Commit>

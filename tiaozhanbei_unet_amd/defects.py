@@ -91,7 +91,7 @@ def direction_table(directions=32):
     return np.stack([np.rint(np.cos(a) * Q_DIRECTION), np.rint(np.sin(a) * Q_DIRECTION)], axis=1).astype(np.int32)
 
 
-def shape_measures(shape_record, directions, frame_hw, original_hw, pixel_size=None, defect_record=None):
+def shape_measures(shape_record, directions, frame_hw, original_hw, pixel_size=None, defect_record=None, components=1):
     """What a shape record of ``evaluation.measure_class_regions`` (SHAPE_HEAD, pmin_k, pmax_k) says about its region, as
     a dict.  ``directions``: D or the ``direction_table`` the record was made with; ``defect_record``: the aligned record
     of ``describe_class_regions`` (FIELDS; needed: the moments are central about its sum_x / size, sum_y / size);
@@ -113,12 +113,20 @@ def shape_measures(shape_record, directions, frame_hw, original_hw, pixel_size=N
     ``perimeter_crack`` = q1 + q2 + q3 + 2 qd (member / non-member pixel edges), ``perimeter`` = q2 + (q1 + q3 + 2 qd) /
         sqrt 2 (Duda), both in frame pixels; ``perimeter_original`` = perimeter sx only where |sx / sy - 1| <= 1e-6, else
         None: these counts cannot be rescaled anisotropically.  ``circularity`` = 4 pi area / perimeter^2.
-    ``euler_number`` = (q1 - q3 - 2 qd) / 4 (exact, 8-connectivity), ``holes`` = 1 - euler_number.
+    ``euler_number`` = (q1 - q3 - 2 qd) / 4 (exact, 8-connectivity), ``holes`` = components - euler_number.
+    ``components``: the 8-connected pieces the record was summed over: 1 for a region, the number of fragments for a group
+        of ``evaluation.group_class_regions`` (a group's Euler number is its fragments minus its holes).  For such a
+        group ``perimeter`` and ``perimeter_crack`` are the sums over the fragments, and ``circularity``, computed from
+        that sum, is NOT a roundness: several round fragments score far below 1.  The moments and the Feret extents
+        are those of the union of the fragments, which is what the length of a broken scratch is.
     With ``pixel_size``: ``feret_length_mm``, ``feret_width_mm``, ``major_axis_mm``, ``minor_axis_mm``,
         ``perimeter_original_mm`` (or None) and ``area_mm2``."""
     import math
     table = direction_table(directions) if np.ndim(directions) == 0 else np.asarray(directions, np.int64).reshape(-1, 2)
     d = len(table)
+    components = int(components)
+    if components < 1:
+        raise ValueError(f"shape_measures: {components} components, at least 1")
     r = [int(v) for v in np.asarray(shape_record).reshape(-1)]
     if len(r) != len(SHAPE_HEAD) + 2 * d:
         raise ValueError(f"shape_measures: a record of {len(r)} fields, {len(SHAPE_HEAD) + 2 * d} go with {d} directions")
@@ -153,7 +161,7 @@ def shape_measures(shape_record, directions, frame_hw, original_hw, pixel_size=N
         raise ValueError("shape_measures: q1 - q3 - 2 qd is no multiple of 4: these are not the quads of a mask")
     out.update(perimeter_crack=q1 + q2 + q3 + 2 * qd, perimeter=perimeter,
                perimeter_original=perimeter * sx if abs(sx / sy - 1) <= 1e-6 else None,
-               circularity=4 * math.pi * size / (perimeter * perimeter), euler_number=euler, holes=1 - euler)
+               circularity=4 * math.pi * size / (perimeter * perimeter), euler_number=euler, holes=components - euler)
     if pixel_size is not None:
         mm = float(pixel_size)
         for key in ("feret_length", "feret_width", "major_axis", "minor_axis"):
@@ -179,7 +187,7 @@ def passes_size_rules(shape, rules):
 
 
 def defect_entries(records, class_names, frame_hw, original_hw_per_image, min_confidence=0.0, reject_classes=None,
-                   shapes=None, rules=None):
+                   shapes=None, rules=None, fragments=None):
     """Per-image dicts of the records [K, 12] (FIELDS; ``image`` indexes ``original_hw_per_image``, a list of (H0, W0)):
     ``{"defects": [...], "decision": "accept" | "reject"}``.  A defect holds ``class``, ``class_name``, ``pixels``, ``bbox``
     [x0, y0, x1, y1] in the frame (inclusive), ``bbox_original``, ``centroid`` [x, y], ``centroid_original``,
@@ -189,7 +197,13 @@ def defect_entries(records, class_names, frame_hw, original_hw_per_image, min_co
 
     ``shapes``: the aligned records of ``measure_class_regions`` (one per record, the same images and roots); every
     defect then holds ``shape`` = ``shape_measures`` of its record, and with ``rules`` (``size_rules``) ``counted``
-    also requires ``passes_size_rules``.  Without ``shapes`` nothing is added."""
+    also requires ``passes_size_rules``.  Without ``shapes`` nothing is added.
+
+    ``fragments``: the fragment table of ``describe_class_regions(..., merge_gap=g)`` ([F, 5]: image, class, root, group,
+    size) when the records are groups.  Every defect then holds ``fragments``, a list of ``{"root": [x, y], "pixels": s}``
+    in root order, and its ``shape`` is computed with that many components.  ``pixels``, ``bbox``, ``centroid`` and the
+    confidences are those of the whole group; ``shape.perimeter`` is the sum over the fragments and
+    ``shape.circularity`` of a defect of several fragments is not a roundness (``shape_measures``)."""
     rec = np.asarray(records, dtype=np.int64).reshape(-1, len(FIELDS))
     h, w = int(frame_hw[0]), int(frame_hw[1])
     reject = set(class_names[1:]) if reject_classes is None else set(reject_classes)
@@ -205,6 +219,14 @@ def defect_entries(records, class_names, frame_hw, original_hw_per_image, min_co
         pixel_size = None if rules is None else rules["pixel_size"]
     elif rules is not None:
         raise ValueError("defect_entries: size rules need the shape records")
+    members = None
+    if fragments is not None:
+        members = {}
+        frag = np.asarray(fragments, dtype=np.int64).reshape(-1, 5)
+        for image, _cls, root, group, size in frag[np.lexsort((frag[:, 2], frag[:, 3], frag[:, 0]))].tolist():
+            members.setdefault((image, group), []).append({"root": [root % w, root // w], "pixels": size})
+        if sorted(members) != [(r[0], r[2]) for r in rec.tolist()]:
+            raise ValueError("defect_entries: the fragment table is not the one of these records")
     for k, r in enumerate(rec.tolist()):
         image, cls, _root, size, x0, y0, x1, y1, sum_x, sum_y, conf_sum, conf_max = r
         if not 0 <= image < len(out):
@@ -215,8 +237,11 @@ def defect_entries(records, class_names, frame_hw, original_hw_per_image, min_co
         mean = conf_sum / (Q_ONE * size)
         counted = mean >= min_confidence
         extra = {}
+        if members is not None:
+            extra["fragments"] = members[(image, _root)]
         if table is not None:
-            extra["shape"] = shape_measures(shp[k], table, (h, w), (h0, w0), pixel_size, defect_record=r)
+            extra["shape"] = shape_measures(shp[k], table, (h, w), (h0, w0), pixel_size, defect_record=r,
+                                            components=len(extra["fragments"]) if members is not None else 1)
             if rules is not None:
                 counted = counted and passes_size_rules(extra["shape"], rules)
         out[image]["defects"].append({

@@ -8,7 +8,10 @@ the value to give it, defects found with the wrong class, and IoU-matched panopt
     python -m tiaozhanbei_unet_amd.eval_detection --dataset kolektorsdd --checkpoint best_model.pth
 
 Takes ``eval_regions``' flags (``--min_region_pixels`` and ``--coverage_thresholds`` among them) plus
-``--max_false_alarms``, ``--tiled``, ``--tile H W`` and ``--min_overlap``.
+``--max_false_alarms``, ``--tiled``, ``--tile H W`` and ``--min_overlap``, and ``--merge_gap PX`` (2..32 frame pixels;
+absent: off), with which the predicted regions of one class that come within PX pixels of each other are matched as
+one defect (``evaluation.group_class_regions``; the truth regions stay as labelled).  Running the tool with and without
+it is how to measure whether grouping changes the detection figures on a data set.
 
 Frame mode (the default): ``eval_regions``' loaders, device preprocessing and model construction; per batch the model,
 ``sheets.seg_confidence`` for the argmax map and its confidence, ``evaluation.DetectionMatcher.update``.
@@ -50,8 +53,9 @@ def check_flags(ap, args):
 
 def parse_args(argv=None):
     ap, args = seg_cli.parse_dataset_args(argv, "Defect detection curves over confidence of a segmentation checkpoint "
-                                                "(MI355X HIP path)", flags_of)
+                                                "(MI355X HIP path)", lambda dataset: flags_of(dataset) + seg_cli.GROUP_FLAGS)
     check_flags(ap, args)
+    seg_cli.check_group_flags(ap, args)
     return args
 
 
@@ -62,7 +66,7 @@ def main(argv=None):
     mode = seg_cli.mode_of(args)
     device, cli, loader, num_classes, class_names, model = seg_cli.open_checkpoint_session(args, "DETECTION EVALUATION",
                                                                                            mode)
-    matcher, paths = DetectionMatcher(num_classes, args.min_region_pixels), []
+    matcher, paths = DetectionMatcher(num_classes, args.min_region_pixels, getattr(args, "merge_gap", 0)), []
     for labels, conf, masks, batch_paths in seg_cli.labelled_predictions(args, cli, loader, model, device):
         matcher.update(labels, conf, masks)
         paths.extend(batch_paths)
@@ -79,7 +83,8 @@ def main(argv=None):
     images = results.pop("images")
     with open(summary_path, "w") as f:
         json.dump({"evaluation_args": vars(args), "class_names": list(class_names), "images": images, "mode": mode,
-                   "min_region_pixels": args.min_region_pixels, **results}, f, indent=2)
+                   "min_region_pixels": args.min_region_pixels,
+                   **({"merge_gap": args.merge_gap} if hasattr(args, "merge_gap") else {}), **results}, f, indent=2)
     with open(os.path.join(args.save_dir, "detection_regions.json"), "w") as f:
         json.dump(seg_detection.region_entries(got["truth"], got["pred"], got["pairs"], paths, class_names,
                                                got["image_sizes"], args.coverage_thresholds[0]), f, indent=2)

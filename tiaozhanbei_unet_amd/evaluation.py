@@ -316,6 +316,83 @@ def label_class_regions(labels_u8, num_classes):
     return region, sizes, counts
 
 
+FRAGMENT_FIELDS = ("image", "class", "root", "group", "size")
+MAX_MERGE_GAP = 32              # the largest gap of unet_group_class_regions
+
+
+def _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, cap):
+    """unet_group_class_regions on labelled maps: (group, group_sizes, counts, DEVICE int64 buffer of ``cap`` records of
+    FRAGMENT_FIELDS followed by their count); does not synchronise."""
+    n, h, w = t.shape
+    lib = L.lib()
+    group, group_sizes = torch.empty_like(region), torch.empty_like(sizes)
+    counts = torch.zeros((n, c), dtype=torch.int64, device=t.device)
+    out = torch.empty(cap * len(FRAGMENT_FIELDS) + 1, dtype=torch.int64, device=t.device)
+    records, count = out[:-1], out[-1:]
+    count.zero_()
+    ws = _workspace(lib.unet_group_class_regions_workspace(n, h, w, c), t.device)
+    L.check(lib.unet_group_class_regions(_ptr(t), _ptr(region), _ptr(sizes), n, h, w, c, gap, min_pixels, image_base,
+                                         _ptr(group), _ptr(group_sizes), _ptr(counts), _ptr(records), cap, _ptr(count),
+                                         _ptr(ws), ws.numel(), _stream()), "unet_group_class_regions")
+    return group, group_sizes, counts, out
+
+
+def _fragment_records(host, cap, what):
+    """the records of ``_group_labelled``'s buffer on the host, sorted by (image, group, root)"""
+    import numpy as np
+    k = int(host[-1])
+    if k > cap:
+        raise RuntimeError(f"{what}: more fragments than regions")      # cannot happen
+    rec = host[:-1].reshape(cap, len(FRAGMENT_FIELDS))[:k]
+    return np.ascontiguousarray(rec[np.lexsort((rec[:, 2], rec[:, 3], rec[:, 0]))])
+
+
+def _merge_gap(what, merge_gap):
+    g = int(merge_gap)
+    if not 0 <= g <= MAX_MERGE_GAP:
+        raise ValueError(f"{what}: merge_gap {merge_gap} is outside 0..{MAX_MERGE_GAP}")
+    return g
+
+
+def group_class_regions(labels_u8, region, sizes, num_classes, gap, min_pixels=1, image_base=0):
+    """Which class regions belong to one defect.  ``labels_u8``, ``region`` and ``sizes`` are what ``label_class_regions``
+    takes and makes.  A fragment is a region with at least ``min_pixels`` pixels (smaller regions are dropped first: they
+    link nothing and join nothing); two fragments of one image and one class are linked iff they hold pixels p, q with
+    (py - qy)^2 + (px - qx)^2 <= gap^2, ``gap`` in 1..32; a group is a connected component of the link graph, so linking
+    is transitive.  Returns (group, group_sizes, counts, fragments): group (int32 [N, H, W], DEVICE) = 1 + the smallest
+    fragment root of the pixel's group, group_sizes (int32, DEVICE) = the group's pixel count at each of its pixels, both
+    0 on background and on dropped regions, so the pair stands in for (region, sizes) wherever those go; counts (int64
+    [N, num_classes], DEVICE) = groups per image and class; fragments = an int64 [F, 5] numpy array of FRAGMENT_FIELDS,
+    one row per fragment, ``image`` = image_base + the map's index, ``group`` = its group's root, sorted by (image,
+    group, root).  ``gap=1`` gives every fragment its own group (unet_group_class_regions; integers throughout, so the
+    outputs are a function of the inputs alone).  Two host reads: the number of region roots, which bounds the fragments
+    from above and sizes the buffer, and the records with their count."""
+    what = "group_class_regions"
+    t = _class_maps(labels_u8, what)
+    _require_cuda(region, sizes)
+    if region.dtype != torch.int32 or sizes.dtype != torch.int32 or region.shape != t.shape or sizes.shape != t.shape \
+            or region.device != t.device or sizes.device != t.device:
+        raise ValueError(f"{what}: region and sizes are the int32 tensors that label_class_regions made of the labels")
+    n, h, w = t.shape
+    c, gap, min_pixels, image_base = int(num_classes), int(gap), int(min_pixels), int(image_base)
+    lib = L.lib()
+    nbytes = lib.unet_group_class_regions_workspace(n, h, w, c) if 0 <= c < 2 ** 31 else 0
+    if nbytes == 0 or image_base + n >= 2 ** 31:
+        raise _class_regions_error(what, n, h, w, num_classes)
+    if not 1 <= gap <= MAX_MERGE_GAP:
+        raise ValueError(f"{what}: gap {gap} is outside 1..{MAX_MERGE_GAP}")
+    if min_pixels < 1:
+        raise ValueError(f"{what}: min_pixels {min_pixels} is below 1")
+    if image_base < 0:
+        raise ValueError(f"{what}: image_base {image_base} is negative")
+    region, sizes = region.contiguous(), sizes.contiguous()
+    per = h * w
+    index = torch.arange(1, per + 1, dtype=torch.int32, device=t.device).reshape(1, h, w)
+    cap = int((region == index).sum())                 # the region roots: every fragment is one
+    group, group_sizes, counts, out = _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, max(cap, 1))
+    return group, group_sizes, counts, _fragment_records(out.cpu().numpy(), max(cap, 1), what)
+
+
 RECORD_FIELDS = ("image", "class", "root", "size", "hit")
 
 
@@ -414,7 +491,7 @@ class ClassRegionMatcher:
 DEFECT_FIELDS = ("image", "class", "root", "size", "x0", "y0", "x1", "y1", "sum_x", "sum_y", "conf_sum_q", "conf_max_q")
 
 
-def describe_class_regions(labels, num_classes, conf=None, min_pixels=1, image_base=0):
+def describe_class_regions(labels, num_classes, conf=None, min_pixels=1, image_base=0, merge_gap=0):
     """One record per class region of integer label maps [N, H, W] that has at least ``min_pixels`` pixels: an int64
     [K, 12] numpy array of DEFECT_FIELDS, sorted by (image, root).  Regions are those of ``label_class_regions``;
     ``image`` = image_base + the map's index, ``root`` = the smallest linear index y * W + x of the region, ``x0 .. y1``
@@ -422,16 +499,28 @@ def describe_class_regions(labels, num_classes, conf=None, min_pixels=1, image_b
     [N, H, W] (the confidence of ``sheets.seg_confidence``), summed over the region as q(v) = rint(clamp(v, 0, 1) * 65536)
     in ``conf_sum_q`` with its maximum in ``conf_max_q``; both 0 without it (unet_describe_class_regions; integers
     throughout, so the array is a function of the inputs alone).  Two host reads: the region counts, which bound the
-    records from above and size the buffer, and the records with their count."""
+    records from above and size the buffer, and the records with their count.
+
+    ``merge_gap`` >= 1 (at most 32) groups the regions first (``group_class_regions`` with this ``min_pixels``): a record
+    then describes a group, ``root`` is the group's root, and the return value is (records, fragments), the second
+    ``group_class_regions``' table, whose ``group`` column names the record a fragment went into.  0 changes nothing."""
     import numpy as np
-    t, cf, c, min_pixels, image_base = _describe_args("describe_class_regions", labels, num_classes, conf, min_pixels,
-                                                      image_base)
+    what = "describe_class_regions"
+    gap = _merge_gap(what, merge_gap)
+    t, cf, c, min_pixels, image_base = _describe_args(what, labels, num_classes, conf, min_pixels, image_base)
     region, sizes, counts = label_class_regions(t, c)
     cap = int(counts.sum())                            # every record is a region: there cannot be more
+    fd = len(DEFECT_FIELDS)
     if cap == 0:
-        return np.zeros((0, len(DEFECT_FIELDS)), np.int64)
-    out = _describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap)
-    return _defect_records(out.cpu().numpy(), cap, "describe_class_regions")
+        empty = np.zeros((0, fd), np.int64)
+        return (empty, np.zeros((0, len(FRAGMENT_FIELDS)), np.int64)) if gap else empty
+    if not gap:
+        out = _describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap)
+        return _defect_records(out.cpu().numpy(), cap, what)
+    group, group_sizes, _, frag = _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, cap)
+    out = _describe_labelled(t, group, group_sizes, cf, c, min_pixels, image_base, cap)
+    host = torch.cat([out, frag]).cpu().numpy()
+    return _defect_records(host[:cap * fd + 1], cap, what), _fragment_records(host[cap * fd + 1:], cap, what)
 
 
 def _describe_args(what, labels, num_classes, conf, min_pixels, image_base):
@@ -516,7 +605,7 @@ def _measure_args(what, labels, min_pixels, image_base, directions):
     return direction_table(d), d
 
 
-def measure_class_regions(labels, num_classes, min_pixels=1, image_base=0, directions=32):
+def measure_class_regions(labels, num_classes, min_pixels=1, image_base=0, directions=32, merge_gap=0):
     """One shape record per class region of integer label maps [N, H, W] that has at least ``min_pixels`` pixels: an
     int64 [K, 11 + 2 directions] numpy array of ``shape_fields(directions)`` (SHAPE_FIELDS at the default 32), sorted by
     (image, root).  The regions, ``image``, ``root`` and ``size`` are ``describe_class_regions``': with equal arguments the
@@ -525,9 +614,13 @@ def measure_class_regions(labels, num_classes, min_pixels=1, image_base=0, direc
     one member, two edge-adjacent, two diagonal, three, four); ``pmin_k`` / ``pmax_k``: the extremes of x c_k + y s_k for
     ``defects.direction_table(directions)``.  ``defects.shape_measures`` turns a record into lengths
     (unet_measure_class_regions; integers throughout, so the array is a function of the inputs alone).  Sides up to
-    16384, an even number of 2..32 directions.  Two host reads: the region counts and the records with their count."""
+    16384, an even number of 2..32 directions.  Two host reads: the region counts and the records with their count.
+
+    ``merge_gap`` >= 1 measures groups as ``describe_class_regions`` describes them and returns (records, fragments); a
+    group's bit-quads are those of the union of its fragments, so its Euler number is fragments minus holes."""
     import numpy as np
     _require_cuda(labels)
+    gap = _merge_gap("measure_class_regions", merge_gap)
     c = int(num_classes)
     if labels.dim() == 3 and labels.numel():
         n, h, w = labels.shape
@@ -537,10 +630,18 @@ def measure_class_regions(labels, num_classes, min_pixels=1, image_base=0, direc
     t = _class_maps(labels, "measure_class_regions")
     region, sizes, counts = label_class_regions(t, c)
     cap = int(counts.sum())
+    fs = len(SHAPE_HEAD) + 2 * d
     if cap == 0:
-        return np.zeros((0, len(SHAPE_HEAD) + 2 * d), np.int64)
-    out = _measure_labelled(region, sizes, int(min_pixels), int(image_base), cap, table)
-    return _sorted_records(out.cpu().numpy(), cap, len(SHAPE_HEAD) + 2 * d, 1, "measure_class_regions")
+        empty = np.zeros((0, fs), np.int64)
+        return (empty, np.zeros((0, len(FRAGMENT_FIELDS)), np.int64)) if gap else empty
+    if not gap:
+        out = _measure_labelled(region, sizes, int(min_pixels), int(image_base), cap, table)
+        return _sorted_records(out.cpu().numpy(), cap, fs, 1, "measure_class_regions")
+    group, group_sizes, _, frag = _group_labelled(t, region, sizes, c, gap, int(min_pixels), int(image_base), cap)
+    out = _measure_labelled(group, group_sizes, int(min_pixels), int(image_base), cap, table)
+    host = torch.cat([out, frag]).cpu().numpy()
+    return (_sorted_records(host[:cap * fs + 1], cap, fs, 1, "measure_class_regions"),
+            _fragment_records(host[cap * fs + 1:], cap, "measure_class_regions"))
 
 
 def _measure_labelled(region, sizes, min_pixels, image_base, cap, table):
@@ -572,16 +673,22 @@ def _sorted_records(host, cap, fields, root_field, what):
 
 
 def describe_and_measure_class_regions(labels, num_classes, conf=None, min_pixels=1, image_base=0, directions=32,
-                                       contours=False):
+                                       contours=False, merge_gap=0):
     """(``describe_class_regions``' records, ``measure_class_regions``' records) of one labelling: the maps are labelled
     once, both kernels run on that labelling, and the two record sets come to the host in one buffer, so the host reads
     stay two (the region counts, then the records).  The rows of the two arrays align.
 
     ``contours=True`` traces the same labelling too and returns (records, shape records, loops, points), the last two as
     ``trace_class_regions`` gives them: the edge counts come with the records, and the outlines are a third read.  With
-    it ``directions=None`` leaves the shapes out (None in their place)."""
+    it ``directions=None`` leaves the shapes out (None in their place).
+
+    ``merge_gap`` >= 1 groups the regions first (``group_class_regions`` with this ``min_pixels``); both kernels then run
+    on the groups, and the returned tuple gains ``group_class_regions``' fragment table as its last element.  The
+    outlines stay those of the FRAGMENT labelling with the same ``min_pixels`` (a loop's ``root`` is its fragment's, and
+    every fragment has exactly one outer loop); ``polygons.outlines`` attributes them to groups through the table."""
     import numpy as np
     what = "describe_and_measure_class_regions"
+    gap = _merge_gap(what, merge_gap)
     t, cf, c, min_pixels, image_base = _describe_args(what, labels, num_classes, conf, min_pixels, image_base)
     shaped = not (contours and directions is None)
     table, d = _measure_args(what, t, min_pixels, image_base, directions) if shaped else (None, 0)
@@ -592,10 +699,16 @@ def describe_and_measure_class_regions(labels, num_classes, conf=None, min_pixel
     cap = int(counts.sum())
     if cap == 0:
         empty = (np.zeros((0, fd), np.int64), np.zeros((0, fs), np.int64) if shaped else None)
-        return empty + _no_outlines() if contours else empty
-    parts = [_describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap)]
+        empty = empty + _no_outlines() if contours else empty
+        return empty + (np.zeros((0, len(FRAGMENT_FIELDS)), np.int64),) if gap else empty
+    whole, whole_sizes, frag = region, sizes, None     # what is described and measured: the regions or their groups
+    if gap:
+        whole, whole_sizes, _, frag = _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, cap)
+    parts = [_describe_labelled(t, whole, whole_sizes, cf, c, min_pixels, image_base, cap)]
     if shaped:
-        parts.append(_measure_labelled(region, sizes, min_pixels, image_base, cap, table))
+        parts.append(_measure_labelled(whole, whole_sizes, min_pixels, image_base, cap, table))
+    if gap:
+        parts.append(frag)
     if contours:
         parts.append(_count_edges(region, sizes, min_pixels))
     both = torch.cat(parts).cpu().numpy()
@@ -605,9 +718,13 @@ def describe_and_measure_class_regions(labels, num_classes, conf=None, min_pixel
         shapes = _sorted_records(both[cap * fd + 1:cap * (fd + fs) + 2], cap, fs, 1, what)
         if len(rec) != len(shapes) or (rec[:, [0, 2, 3]] != shapes[:, :3]).any():
             raise RuntimeError(f"{what}: the two record sets differ")      # cannot happen
+    tail = ()
+    if gap:
+        at = cap * fd + 1 + (cap * fs + 1 if shaped else 0)
+        tail = (_fragment_records(both[at:at + cap * len(FRAGMENT_FIELDS) + 1], cap, what),)
     if not contours:
-        return rec, shapes
-    return (rec, shapes) + _trace_counted(region, sizes, min_pixels, image_base, both[-3:].tolist(), what)
+        return (rec, shapes) + tail
+    return (rec, shapes) + _trace_counted(region, sizes, min_pixels, image_base, both[-3:].tolist(), what) + tail
 
 
 LOOP_FIELDS = ("image", "root", "leader", "n_points", "first_point", "area2")
@@ -767,10 +884,15 @@ class DetectionMatcher:
     labelling (unet_describe_class_regions: truth without confidence and with every region, the prediction with ``conf``
     and ``min_pixels``) and pairs the two ``region`` halves (``pair_class_regions``' kernels).  Every update may have
     another (H, W).  It reads the region counts, the pair bound and the records back, so it SYNCHRONISES per update: that
-    is acceptable for an evaluation pass, and it keeps nothing on the device."""
+    is acceptable for an evaluation pass, and it keeps nothing on the device.
 
-    def __init__(self, num_classes, min_pixels=1):
+    ``merge_gap`` >= 1 groups the PREDICTED half of the labelling (``group_class_regions`` with ``min_pixels``): a
+    predicted record is then a group, and the pairs are those of the truth regions with the groups.  The truth half stays
+    as labelled.  Dropped regions have id 0 in the grouped map and so make no pairs."""
+
+    def __init__(self, num_classes, min_pixels=1, merge_gap=0):
         self.num_classes, self.min_pixels = int(num_classes), int(min_pixels)
+        self.merge_gap = _merge_gap("DetectionMatcher", merge_gap)
         if not 2 <= self.num_classes <= 255:
             raise ValueError(f"DetectionMatcher: {num_classes} classes, 2..255 are supported")
         if self.min_pixels < 1:
@@ -800,11 +922,14 @@ class DetectionMatcher:
             raise _class_regions_error(what, n, h, w, c)
         region, sizes, counts = label_class_regions(torch.cat([t, p]), c)      # one pass labels both
         cap_t, cap_p = counts.reshape(2, -1).sum(1).tolist()
+        preg, psiz = region[n:], sizes[n:]
+        if self.merge_gap and cap_p:
+            preg, psiz, _, _ = _group_labelled(p, preg, psiz, c, self.merge_gap, self.min_pixels, base, cap_p)
         halves = []
         for maps, reg, siz, cfd, mp, cap in ((t, region[:n], sizes[:n], None, 1, cap_t),
-                                             (p, region[n:], sizes[n:], cf, self.min_pixels, cap_p)):
+                                             (p, preg, psiz, cf, self.min_pixels, cap_p)):
             halves.append(_describe_labelled(maps, reg, siz, cfd, c, mp, base, cap) if cap else None)
-        pairs, record_cap = _pairs_on_device(region[:n], region[n:], base, what)
+        pairs, record_cap = _pairs_on_device(region[:n], preg, base, what)
         empty = np.zeros((0, len(DEFECT_FIELDS)), np.int64)
         trec, prec = (_defect_records(o.cpu().numpy(), cap, what) if o is not None else empty
                       for o, cap in zip(halves, (cap_t, cap_p)))

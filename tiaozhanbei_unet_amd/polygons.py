@@ -17,10 +17,16 @@ from __future__ import annotations
 import numpy as np
 
 
-def outlines(loops, points):
+def outlines(loops, points, fragments=None):
     """{(image, root): (outer, holes)} of ``trace_class_regions``' (loops, points), in the loops' order: ``outer`` = the int32
     [K, 2] points (x, y) of the region's one loop with area2 > 0, ``holes`` = a list of those of its loops with area2 < 0,
-    by leader."""
+    by leader.
+
+    ``fragments``: the fragment table of ``describe_and_measure_class_regions(..., merge_gap=g)`` ([F, 5]: image, class,
+    root, group, size) when the loops are those of the fragments of grouped defects.  The result is then keyed by
+    (image, group root) and holds (outer, holes, fragment_outlines): ``outer`` = the outer loop of the group's largest
+    fragment (ties: the smallest root), ``holes`` = the hole loops of all its fragments, ``fragment_outlines`` = every
+    fragment's outer loop in root order."""
     loops = np.asarray(loops, np.int64).reshape(-1, 6)
     points = np.asarray(points, np.int32).reshape(-1, 2)
     out = {}
@@ -34,7 +40,20 @@ def outlines(loops, points):
         if len(outer) != 1:
             raise ValueError(f"outlines: region {key} has {len(outer)} outer loops")
         out[key] = (outer[0], holes)
-    return out
+    if fragments is None:
+        return out
+    frag = np.asarray(fragments, np.int64).reshape(-1, 5)
+    frag = frag[np.lexsort((frag[:, 2], frag[:, 3], frag[:, 0]))]
+    if sorted(out) != sorted((i, r) for i, r in frag[:, [0, 2]].tolist()):
+        raise ValueError("outlines: the fragment table is not the one of these loops")
+    grouped, largest = {}, {}
+    for image, _cls, root, group, size in frag.tolist():
+        outer, holes = out[(image, root)]
+        lead, all_holes, pieces = grouped.get((image, group), (None, [], []))
+        if size > largest.get((image, group), 0):                # in root order: a tie keeps the smaller root
+            largest[(image, group)], lead = size, outer
+        grouped[(image, group)] = (lead, all_holes + holes, pieces + [outer])
+    return grouped
 
 
 def _segment_distances(pts, a, b):
@@ -99,7 +118,9 @@ def attach_outlines(entries, records, traced, frame_hw, original_hw_per_image, t
     """Adds to every defect of ``defects.defect_entries``' per-image ``entries`` (built from the same ``records``) its
     ``outline`` ([[x, y], ...] in frame pixels, thinned by ``simplify_closed`` with ``tolerance``), ``outline_original``
     (the pixel centres in the image's own pixels, as ``centroid_original``) and ``hole_outlines``.  ``traced``:
-    ``outlines`` of the same maps with the records' ``min_pixels`` and image numbering."""
+    ``outlines`` of the same maps with the records' ``min_pixels`` and image numbering.  Where that was made with a
+    fragment table (grouped defects), ``outline`` is the largest fragment's and every defect gains ``fragment_outlines``,
+    the outlines of all its fragments in root order, thinned alike."""
     rec = np.asarray(records, np.int64).reshape(-1, 12)
     rec = rec[np.lexsort((rec[:, 2], rec[:, 0]))]                # defect_entries' order
     h, w = int(frame_hw[0]), int(frame_hw[1])
@@ -107,16 +128,20 @@ def attach_outlines(entries, records, traced, frame_hw, original_hw_per_image, t
     for image, root in rec[:, [0, 2]].tolist():
         d = entries[image]["defects"][at[image]]
         at[image] += 1
-        outer, holes = traced[(image, root)]
+        outer, holes, *pieces = traced[(image, root)]
         h0, w0 = (int(v) for v in original_hw_per_image[image])
         outer = simplify_closed(outer, tolerance)
         d["outline"] = outer.tolist()
         d["outline_original"] = [[(x + 0.5) * w0 / w - 0.5, (y + 0.5) * h0 / h - 0.5] for x, y in d["outline"]]
         d["hole_outlines"] = [simplify_closed(hole, tolerance).tolist() for hole in holes]
+        if pieces:
+            d["fragment_outlines"] = [simplify_closed(piece, tolerance).tolist() for piece in pieces[0]]
     return entries
 
 
 def entry_label_lines(entry, frame_hw):
-    """``gear_label_lines`` of an image entry's defects with ``"counted": true`` (after ``attach_outlines``)"""
+    """``gear_label_lines`` of an image entry's defects with ``"counted": true`` (after ``attach_outlines``); a grouped
+    defect (one with ``fragment_outlines``) writes one line per fragment"""
     kept = [d for d in entry["defects"] if d["counted"]]
-    return gear_label_lines([d["outline"] for d in kept], [d["class"] for d in kept], frame_hw)
+    loops = [(piece, d["class"]) for d in kept for piece in d.get("fragment_outlines", [d["outline"]])]
+    return gear_label_lines([piece for piece, _ in loops], [cls for _, cls in loops], frame_hw)

@@ -43,6 +43,14 @@ every outline.  Two limits come with the format: it has no holes, so a hole is f
 loader resolves overlaps by class priority (spalling > pitting > scrape), not by nesting, so a lower-priority defect
 inside a higher one's hole is overwritten.  The GPU mask kernel of the loader takes at most 512 points a polygon: thin
 longer outlines with ``--polygon_tolerance``.
+
+Build-only, off by default too (``seg_cli.GROUP_FLAGS``, shared likewise): ``--merge_gap PX`` (2..32 FRAME pixels, which
+this tool squeezes anisotropically from the image) counts the regions of one class that come within PX pixels of each
+other as ONE defect (``evaluation.group_class_regions``, csrc/groups.hip; regions below ``--min_region_pixels`` are dropped
+first and bridge nothing).  ``pixels``, ``bbox``, the confidences, ``shape`` and the size rules are then those of the
+whole group; every defect gains ``fragments`` ([{"root": [x, y], "pixels": s}] in root order) and, with the polygon flags,
+``fragment_outlines``, and ``labels/<name>.txt`` holds one line per fragment.  ``shape.perimeter`` is the sum over the
+fragments and ``shape.circularity`` of several fragments is not a roundness.  A ``grouping_rules`` block records the gap.
 """
 from __future__ import annotations
 
@@ -91,6 +99,7 @@ def parse_args(argv=None):
     seg_cli.check_predict_flags(ap, args)
     seg_cli.check_shape_flags(ap, args)
     seg_cli.check_polygon_flags(ap, args)
+    seg_cli.check_group_flags(ap, args)
     return args
 
 
@@ -119,12 +128,14 @@ def collate_images(samples):
     return (torch.stack(imgs) if same else list(imgs)), list(idx)
 
 
-def predict_batches(model, loader, size, num_classes, min_pixels, device, directions=None, contours=False):
+def predict_batches(model, loader, size, num_classes, min_pixels, device, directions=None, contours=False, merge_gap=0):
     """Eval-mode pass over ``collate_images`` batches.  Yields per batch (indices, original sizes [(H0, W0)], normalised
     images, labels uint8 [N, H, W], frame mean confidence list, records with ``image`` = the dataset index).  The records
     and the means are the batch's host reads.  With ``directions`` (a number of Feret directions) the records are the
     pair (records, shape records) of ``evaluation.describe_and_measure_class_regions``: one labelling, the same reads.
-    With ``contours`` they are its four (records, shape records or None, loops, points), ``image`` mapped in the loops too."""
+    With ``contours`` they are its four (records, shape records or None, loops, points), ``image`` mapped in the loops too.
+    With ``merge_gap`` the records are those of the groups and the tuple (a pair at the least) ends with the fragment
+    table, ``image`` mapped there too."""
     import numpy as np
     import torch
     from . import sheets
@@ -140,13 +151,16 @@ def predict_batches(model, loader, size, num_classes, min_pixels, device, direct
             logits = model(x)
             labels, conf = sheets.seg_confidence(logits)
             means = per_image_stats(logits)["conf_mean"]
-            if directions is None and not contours:
+            if directions is None and not contours and not merge_gap:
                 records = describe_class_regions(labels, num_classes, conf, min_pixels)
                 records[:, 0] = np.asarray(idx, np.int64)[records[:, 0]]
             else:
-                records = describe_and_measure_class_regions(labels, num_classes, conf, min_pixels, 0, directions,
-                                                             contours=contours)
-                for rec in records[:3]:
+                if directions is None and not contours:
+                    records = describe_class_regions(labels, num_classes, conf, min_pixels, merge_gap=merge_gap)
+                else:
+                    records = describe_and_measure_class_regions(labels, num_classes, conf, min_pixels, 0, directions,
+                                                                 contours=contours, merge_gap=merge_gap)
+                for rec in records[:3] + (records[-1:] if merge_gap and len(records) > 3 else ()):
                     if rec is not None:
                         rec[:, 0] = np.asarray(idx, np.int64)[rec[:, 0]]
             yield idx, sizes, x, labels, means.tolist(), records
@@ -170,12 +184,16 @@ def main(argv=None):
     loader = image_loader(paths, args.batch_size, args.num_workers)
     originals, frame_means, records, shapes, traced = [None] * len(paths), [None] * len(paths), [], [], {}
     rules, polygon_rules = seg_cli.size_rules_of(args), seg_cli.polygon_rules_of(args)
+    merge_gap, fragments = getattr(args, "merge_gap", 0), []
     for idx, sizes, x, labels, means, rec in predict_batches(model, loader, args.image_size, num_classes,
                                                              args.min_region_pixels, device,
                                                              None if rules is None else seg_cli.DIRECTIONS,
-                                                             polygon_rules is not None):
+                                                             polygon_rules is not None, merge_gap):
+        if merge_gap:
+            fragments.append(rec[-1])
+            rec = rec[:-1] if len(rec) > 2 else rec[0]
         if polygon_rules is not None:
-            traced.update(polygons.outlines(rec[2], rec[3]))
+            traced.update(polygons.outlines(rec[2], rec[3], fragments[-1] if merge_gap else None))
         if rules is not None:
             shapes.append(rec[1])
         if rules is not None or polygon_rules is not None:
@@ -196,7 +214,8 @@ def main(argv=None):
 
     entries = defects.defect_entries(np.concatenate(records), class_names, args.image_size, originals,
                                      args.min_confidence, args.reject_classes,
-                                     np.concatenate(shapes) if shapes else None, rules)
+                                     np.concatenate(shapes) if shapes else None, rules,
+                                     **({"fragments": np.concatenate(fragments)} if merge_gap else {}))
     if polygon_rules is not None:
         polygons.attach_outlines(entries, np.concatenate(records), traced, args.image_size, originals,
                                  args.polygon_tolerance)

@@ -45,6 +45,7 @@ def parse_args(argv=None):
     seg_cli.check_predict_flags(ap, args)
     seg_cli.check_shape_flags(ap, args)
     seg_cli.check_polygon_flags(ap, args)
+    seg_cli.check_group_flags(ap, args)
     return args
 
 
@@ -80,9 +81,10 @@ def main(argv=None):
         original = (int(image.shape[0]), int(image.shape[1]))
         x = load_frame(image, working_frame(original, args.scale), device)
         labels, conf, plan = predictor(x)
-        records, shapes, traced = seg_cli.describe_regions(args, labels[None], num_classes, conf[None])
+        records, shapes, traced, fragments = seg_cli.describe_regions(args, labels[None], num_classes, conf[None])
         images[i] = seg_cli.save_frame_prediction(args, outputs, paths[i], names[i], original, labels, conf, records,
-                                                  class_names, {"tiling": plan}, frame=x, shapes=shapes, traced=traced)
+                                                  class_names, {"tiling": plan}, frame=x, shapes=shapes, traced=traced,
+                                                  fragments=fragments)
 
     def tiles(im):
         return f"in {len(im['tiling']['origins_y']) * len(im['tiling']['origins_x'])} tiles"

@@ -56,16 +56,20 @@ def parse_args(argv=None):
     seg_cli.check_predict_flags(ap, args)
     seg_cli.check_shape_flags(ap, args)
     seg_cli.check_polygon_flags(ap, args)
+    seg_cli.check_group_flags(ap, args)
     check_views(ap, args, args.scale)
     return args
 
 
-def agreement_means(labels, agreement, n_views, num_classes, min_pixels, records):
+def agreement_means(labels, agreement, n_views, num_classes, min_pixels, records, merge_gap=0):
     """Per record of ``records`` (``describe_class_regions`` of ``labels`` [N, H, W], sorted by image and root) the mean of
     agreement / n_views over its region, conf_sum_q / (65536 size): one more ``describe_class_regions`` with that ratio
-    in the confidence slot, which yields the same regions in the same order."""
+    in the confidence slot, which yields the same regions in the same order.  ``merge_gap``: the gap the records were
+    grouped with (0: not grouped), so that the rows still align."""
     from .evaluation import describe_class_regions
-    again = describe_class_regions(labels, num_classes, agreement.float() / float(n_views), min_pixels)
+    again = describe_class_regions(labels, num_classes, agreement.float() / float(n_views), min_pixels, merge_gap=merge_gap)
+    if merge_gap:
+        again = again[0]
     if again.shape != records.shape or (again[:, :4] != records[:, :4]).any():
         raise RuntimeError("agreement_means: the regions of the two passes differ")
     return [int(r[10]) / (defects.Q_ONE * int(r[3])) for r in again]
@@ -89,12 +93,14 @@ def main(argv=None):
         original = (int(image.shape[0]), int(image.shape[1]))
         frame_hw = working_frame(original, args.scale)
         labels, conf, agreement, plan = ensemble(image, frame_hw)
-        records, shapes, traced = seg_cli.describe_regions(args, labels[None], num_classes, conf[None])
-        agree = agreement_means(labels[None], agreement[None], len(views), num_classes, args.min_region_pixels, records)
+        records, shapes, traced, fragments = seg_cli.describe_regions(args, labels[None], num_classes, conf[None])
+        agree = agreement_means(labels[None], agreement[None], len(views), num_classes, args.min_region_pixels, records,
+                                getattr(args, "merge_gap", 0))
         frame = load_frame(image, frame_hw, device) if args.save_overlays else None
         images[i] = seg_cli.save_frame_prediction(args, outputs, paths[i], names[i], original, labels, conf, records,
                                                   class_names, {"tiling": plan[0]["tiling"], "views": plan}, frame=frame,
-                                                  defect_extras={"mean_view_agreement": agree}, shapes=shapes, traced=traced)
+                                                  defect_extras={"mean_view_agreement": agree}, shapes=shapes, traced=traced,
+                                                  fragments=fragments)
     return seg_cli.write_predictions(args, class_names, images, middle=lambda im: f"in {len(im['views'])} views")
 
 

@@ -236,7 +236,14 @@ POLYGON_FLAGS = [("--save_polygons", dict(action="store_true", default=argparse.
                  ("--polygon_tolerance", dict(type=float, default=argparse.SUPPRESS, metavar="T",
                                               help="thin every outline (Douglas-Peucker) by at most T frame pixels, "
                                                    "default 0: every corner; implies --save_polygons"))]
-BUILD_FLAGS = SHAPE_FLAGS + POLYGON_FLAGS
+# build-only: nearby fragments of one class count as one defect (csrc/groups.hip).  Absent by default, like the flags
+# above: a run without it has the ``args`` of before and launches nothing new.
+GROUP_FLAGS = [("--merge_gap", dict(type=int, default=argparse.SUPPRESS, metavar="PX",
+                                    help="regions of one class whose pixels come within PX frame pixels (2..32, "
+                                         "Euclidean) of each other are one defect: its size, box, confidence, shape "
+                                         "and the size rules are those of the whole group; regions below "
+                                         "--min_region_pixels are dropped first and bridge nothing"))]
+BUILD_FLAGS = SHAPE_FLAGS + POLYGON_FLAGS + GROUP_FLAGS
 
 
 def check_polygon_flags(ap, args):
@@ -249,6 +256,26 @@ def check_polygon_flags(ap, args):
         ap.error("--polygon_tolerance must be at least 0")
 
 
+def check_group_flags(ap, args):
+    """The rule of ``GROUP_FLAGS``.  Without the flag ``args`` stays as it is."""
+    if hasattr(args, "merge_gap") and not 2 <= args.merge_gap <= 32:
+        ap.error("--merge_gap must lie in 2..32 (frame pixels)")
+
+
+def grouping_rules_of(args):
+    """the ``grouping_rules`` block of ``predictions.json``, or None when regions are not grouped"""
+    gap = getattr(args, "merge_gap", 0)
+    if not gap:
+        return None
+    return {"merge_gap": gap,
+            "units": "frame pixels: the frame the model ran at, which predict squeezes anisotropically from the image "
+                     "(predict_tiled and predict_views scale both axes alike)",
+            "rule": "regions of one class in one image with pixels p, q at (py - qy)^2 + (px - qx)^2 <= merge_gap^2 are "
+                    "one defect, transitively; its fragments are listed per defect",
+            "dropped": f"regions below --min_region_pixels ({args.min_region_pixels}) are dropped before grouping: they "
+                       "link nothing and join nothing"}
+
+
 def polygon_rules_of(args):
     """the ``polygon_rules`` block of ``predictions.json``, or None when no polygons are written"""
     if not getattr(args, "save_polygons", False):
@@ -258,16 +285,20 @@ def polygon_rules_of(args):
 
 
 def describe_regions(args, labels, num_classes, conf):
-    """(records, shape records or None, outlines or None) of label maps (N, H, W) for a predict tool:
-    ``describe_class_regions``; with the shape flags ``measure_class_regions`` and with the polygon flags
-    ``trace_class_regions`` (as ``polygons.outlines``) on the same labelling: the maps are labelled once."""
+    """(records, shape records or None, outlines or None, fragment table or None) of label maps (N, H, W) for a predict
+    tool: ``describe_class_regions``; with the shape flags ``measure_class_regions`` and with the polygon flags
+    ``trace_class_regions`` (as ``polygons.outlines``) on the same labelling: the maps are labelled once.  With
+    ``--merge_gap`` the records are those of the groups, and the outlines are keyed by group."""
     from . import evaluation, polygons
     shaped, traced = size_rules_of(args) is not None, polygon_rules_of(args) is not None
+    gap = getattr(args, "merge_gap", 0)
     if not shaped and not traced:
-        return evaluation.describe_class_regions(labels, num_classes, conf, args.min_region_pixels), None, None
+        got = evaluation.describe_class_regions(labels, num_classes, conf, args.min_region_pixels, merge_gap=gap)
+        return (got[0], None, None, got[1]) if gap else (got, None, None, None)
     got = evaluation.describe_and_measure_class_regions(labels, num_classes, conf, args.min_region_pixels, 0,
-                                                        DIRECTIONS if shaped else None, contours=traced)
-    return (got[0], got[1], polygons.outlines(got[2], got[3])) if traced else (got[0], got[1], None)
+                                                        DIRECTIONS if shaped else None, contours=traced, merge_gap=gap)
+    frag = got[-1] if gap else None
+    return got[0], got[1], polygons.outlines(got[2], got[3], frag) if traced else None, frag
 
 
 def save_label_file(args, name, entry, frame_hw):
@@ -357,19 +388,20 @@ def save_overlay(frame, labels, palette, path):
 
 
 def save_frame_prediction(args, outputs, path, name, original, labels, conf, records, class_names, plans, frame=None,
-                          defect_extras=None, shapes=None, traced=None):
+                          defect_extras=None, shapes=None, traced=None, fragments=None):
     """One image of ``predict_tiled`` / ``predict_views``: its ``predictions.json`` entry from the ``records`` of its
     label map (H, W) and confidence, ``masks/<name>.png`` at the image's ``original`` size (NEAREST when the frame
     differs), and with ``--save_overlays`` the overlay on ``frame``, the normalised (3, H, W) frame.  ``plans``: the keys
     that follow ``frame_size`` in the entry; ``defect_extras``: {key: one value per listed defect, in the records' order}.
     ``outputs``: what ``prediction_outputs`` returned; ``shapes``: the records' shape records from ``describe_regions``
     (None unless the shape flags are given); ``traced``: its outlines (None unless the polygon flags are given), which
-    go into the defects and, for the counted ones, into ``labels/<name>.txt``.  Returns the entry."""
+    go into the defects and, for the counted ones, into ``labels/<name>.txt``; ``fragments``: its fragment table (None
+    unless ``--merge_gap`` is given).  Returns the entry."""
     from . import augment, defects
     mask_dir, overlay_dir, palette, palette_bytes = outputs
     frame_hw = (int(labels.shape[0]), int(labels.shape[1]))
     (entry,) = defects.defect_entries(records, class_names, frame_hw, [original], args.min_confidence, args.reject_classes,
-                                      shapes, size_rules_of(args))
+                                      shapes, size_rules_of(args), **({} if fragments is None else {"fragments": fragments}))
     pixels = {cls: 0 for cls in class_names[1:]}
     for k, d in enumerate(entry["defects"]):                # defect_entries keeps the records' order: by root
         for key, values in (defect_extras or {}).items():
@@ -388,7 +420,8 @@ def save_frame_prediction(args, outputs, path, name, original, labels, conf, rec
 
 
 def write_predictions(args, class_names, images, middle=None, frame_size=None):
-    """``{output_dir}/predictions.json`` (args, class_names, [frame_size,] [size_rules,] [polygon_rules,] images, summary)
+    """``{output_dir}/predictions.json`` (args, class_names, [frame_size,] [size_rules,] [polygon_rules,] [grouping_rules,]
+    images, summary)
     and the printed
     lines: one per image -- decision, name, then the frame size and ``middle(entry)`` (such as "in 4 tiles") when
     ``middle`` is given, then its first four defects, with their Feret length when shapes were measured -- and the
@@ -402,6 +435,8 @@ def write_predictions(args, class_names, images, middle=None, frame_size=None):
         shared["size_rules"] = rules
     if polygon_rules_of(args) is not None:
         shared["polygon_rules"] = polygon_rules_of(args)
+    if grouping_rules_of(args) is not None:
+        shared["grouping_rules"] = grouping_rules_of(args)
     unit = "mm" if rules and rules["pixel_size"] is not None else "px"
     length = "feret_length_mm" if unit == "mm" else "feret_length"
     out_path = os.path.join(args.output_dir, "predictions.json")
@@ -410,6 +445,7 @@ def write_predictions(args, class_names, images, middle=None, frame_size=None):
                   indent=2)
     for im in images:
         found = ", ".join(f"{d['class_name']} {d['pixels']} px @ {d['mean_confidence']:.2f}"
+                          + (f" in {len(d['fragments'])} fragments" if len(d.get("fragments", ())) > 1 else "")
                           + (f" length {d['shape'][length]:.1f} {unit}" if "shape" in d else "")
                           + (f" (views {d['mean_view_agreement']:.2f})" if "mean_view_agreement" in d else "")
                           for d in im["defects"][:4])
