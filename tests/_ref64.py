@@ -11,6 +11,12 @@ with ref and S computed in float64 from the bf16-quantised operands.  A dropped 
 mis-zeroed halo element, an epilogue that truncates instead of rounding to nearest-even or a missing split-K slab
 moves an element by far more than that; the max|ref|-relative bound of check() in test_gpu_kernels.py does not see
 them.  Plain helper module: the GPU tests and the CPU self-test (test_cpu_ref64.py) import it.
+
+The convolution references take the compute dtype of the kernel under test (dtype=, default bf16) and read their
+operands with rd().  The fp32 kernels (the "parity" mode: conv3_kernel<float>, igemm_kernel<float>, wgrad_kernel<float>)
+store fp32, so they are held to 2^-18 S alone, on UNROUNDED fp32 operands: an fp32 kernel reads every bit of its inputs,
+and inputs that already lie on the bf16 grid would hide a kernel that narrows its operands on the way to the matrix
+unit (bf16 or a 10-bit mantissa move an element by 30 to 200 bounds, test_cpu_ref64.py).
 """
 import torch
 import torch.nn.functional as F
@@ -55,41 +61,41 @@ def round_bf16_toward_zero(x):
 
 
 # ------------------------------------------------------------------ references: (value, magnitude S) in float64
-def conv3x3(x, w):
+def conv3x3(x, w, dtype=torch.bfloat16):
     """y = conv2d(x, w, padding=1)"""
-    x, w = q64(x), q64(w)
+    x, w = rd(x, dtype), rd(w, dtype)
     return F.conv2d(x, w, padding=1), F.conv2d(x.abs(), w.abs(), padding=1)
 
 
-def conv3x3_dgrad(dy, w):
+def conv3x3_dgrad(dy, w, dtype=torch.bfloat16):
     """dx of y = conv2d(x, w, padding=1)"""
-    dy, w = q64(dy), q64(w)
+    dy, w = rd(dy, dtype), rd(w, dtype)
     return F.conv_transpose2d(dy, w, padding=1), F.conv_transpose2d(dy.abs(), w.abs(), padding=1)
 
 
-def conv3x3_wgrad(x, dy):
+def conv3x3_wgrad(x, dy, dtype=torch.bfloat16):
     """dw of y = conv2d(x, w, padding=1), dw[co, ci, ky, kx]"""
-    x, dy = q64(x), q64(dy)
+    x, dy = rd(x, dtype), rd(dy, dtype)
     shape = (dy.shape[1], x.shape[1], 3, 3)
     g = torch.nn.grad.conv2d_weight
     return g(x, shape, dy, padding=1), g(x.abs(), shape, dy.abs(), padding=1)
 
 
-def convt2x2(x, w, b):
-    """y = conv_transpose2d(x, w, b, stride=2); w[ci, co, 2, 2] bf16-quantised, the bias stays fp32"""
-    x, w, b = q64(x), q64(w), b.detach().to(torch.float64).cpu()
+def convt2x2(x, w, b, dtype=torch.bfloat16):
+    """y = conv_transpose2d(x, w, b, stride=2); x and w[ci, co, 2, 2] read in the compute dtype, the bias stays fp32"""
+    x, w, b = rd(x, dtype), rd(w, dtype), b.detach().to(torch.float64).cpu()
     return F.conv_transpose2d(x, w, b, stride=2), F.conv_transpose2d(x.abs(), w.abs(), b.abs(), stride=2)
 
 
-def convt2x2_dgrad(dy, w):
+def convt2x2_dgrad(dy, w, dtype=torch.bfloat16):
     """dx of y = conv_transpose2d(x, w, stride=2)"""
-    dy, w = q64(dy), q64(w)
+    dy, w = rd(dy, dtype), rd(w, dtype)
     return F.conv2d(dy, w, stride=2), F.conv2d(dy.abs(), w.abs(), stride=2)
 
 
-def convt2x2_wgrad(x, dy):
+def convt2x2_wgrad(x, dy, dtype=torch.bfloat16):
     """(dw[ci, co, 2, 2], db[co]) of y = conv_transpose2d(x, w, b, stride=2)"""
-    x, dy = q64(x), q64(dy)
+    x, dy = rd(x, dtype), rd(dy, dtype)
     n, ci, h, w_ = x.shape
     co = dy.shape[1]
     d = dy.view(n, co, h, 2, w_, 2)

@@ -6,7 +6,10 @@ segmentation loss (seg_loss): torch's float64 operators and autograd agree with 
 partial, a missing tail pixel, wrong Dice coefficients, a dropped focal derivative term, a clamped cross entropy and the
 two contract slips (Dice sum p skipping ignored pixels, focal averaged over valid pixels) are rejected.  At the end the
 folded-BatchNorm inference convolution (conv3x3_bias_relu): an fp32-accumulating emulation passes, a shift from the wrong
-channel, a misplaced or missing ReLU, the neighbouring row's scale, a bf16-rounded shift and a truncating store do not."""
+channel, a misplaced or missing ReLU, the neighbouring row's scale, a bf16-rounded shift and a truncating store do not.
+Last, the fp32 compute dtype of the convolution references (test_gpu_staged.py): fp32 host results on unrounded operands
+pass 2^-18 S; operands narrowed to bf16 or 10 mantissa bits, a zeroed tap, a missing 8 x 16 pixel tile of a weight
+gradient and an accumulate that drops the old value do not."""
 import pytest
 import torch
 
@@ -734,3 +737,120 @@ def test_folded_conv_defects_are_rejected(fold_case, defect):
     x, wt, scale, shift, rs = fold_case
     with pytest.raises(AssertionError):
         R.assert_bf16(_fold_emulation(x, wt, scale, shift, defect), rs, defect)
+
+
+# ====================================================================== fp32 compute dtype (test_gpu_staged.py)
+# The fp32 kernels are held to 2^-18 S on UNROUNDED fp32 operands (dtype=torch.float32 of the references).  At the largest
+# Ctot (256) and the largest weight-gradient K (5 x 17 x 35 = 2975 pixels) of the table of test_gpu_staged.py: the fp32
+# host results pass, and operands narrowed to bf16 or to 10 explicit mantissa bits, one zeroed tap of one input channel,
+# one 8 x 16 pixel tile missing from a weight-gradient reduction and an accumulate that drops the old value do not.
+FP32_CONV_SHAPES = [(2, 128, 128, 20, 40), (1, 256, 192, 17, 35), (3, 128, 256, 7, 13), (1, 72, 64, 9, 21)]      # n, ci, co, h, w
+FP32_WGRAD_SHAPES = [(2, 128, 128, 20, 40), (5, 256, 256, 17, 35)]          # K = 1600 and 2975 pixels
+F32 = torch.float32
+
+
+def _cut10(t):
+    """fp32 cut to 10 explicit mantissa bits (the low 13 bits cleared)"""
+    return (t.float().contiguous().view(torch.int32) & ~0x1FFF).view(torch.float32)
+
+
+def _worst(fn, *a):
+    """err / bound of a result that must be REJECTED, from the assertion's own text"""
+    with pytest.raises(AssertionError) as e:
+        fn(*a)
+    return float(str(e.value).split(" = ")[1].split(" x bound")[0])
+
+
+@pytest.fixture(scope="module", params=FP32_CONV_SHAPES, ids=str)
+def fp32_conv(request):
+    n, ci, co, h, w = request.param
+    seed = 2000 + ci + co + h
+    x, gy = _gen(seed, (n, ci, h, w)).float(), _gen(seed + 1, (n, co, h, w)).float()
+    wt = (_gen(seed + 2, (co, ci, 3, 3)) / (3 * ci ** 0.5)).float()
+    assert not torch.equal(x, x.bfloat16().float())               # the operands are NOT on the bf16 grid
+    return x, wt, gy, R.conv3x3(x, wt, dtype=F32), R.conv3x3_dgrad(gy, wt, dtype=F32)
+
+
+def test_fp32_references_read_unrounded_operands(fp32_conv):
+    x, wt, gy, (ref, S), (dref, dS) = fp32_conv
+    assert _close(ref, F.conv2d(x.double(), wt.double(), padding=1)) and bool((S >= ref.abs()).all())
+    assert _close(dref, F.conv_transpose2d(gy.double(), wt.double(), padding=1))
+    # the default stays the bf16 reference of every earlier caller
+    assert torch.equal(R.conv3x3(x, wt)[0], F.conv2d(R.q64(x), R.q64(wt), padding=1))
+    assert not _close(ref, R.conv3x3(x, wt)[0])
+
+
+def test_fp32_host_convolution_is_accepted(fp32_conv):
+    x, wt, gy, rs, drs = fp32_conv
+    a = R.assert_fp32(F.conv2d(x, wt, padding=1), rs, "fp32 host conv")
+    b = R.assert_fp32(F.conv_transpose2d(gy, wt, padding=1), drs, "fp32 host dgrad")
+    print(f"\nREF64 staged cpu {tuple(x.shape)}: fp32 host conv {a:.3f} dgrad {b:.3f} of the bound")
+    assert max(a, b) <= 1.0
+
+
+@pytest.mark.parametrize("narrow", ["bf16", "10bit"])
+def test_fp32_narrowed_operands_are_rejected(fp32_conv, narrow):
+    x, wt, gy, rs, drs = fp32_conv
+    cut = (lambda t: t.bfloat16().float()) if narrow == "bf16" else _cut10
+    a = _worst(R.assert_fp32, F.conv2d(cut(x), cut(wt), padding=1), rs, f"{narrow} operands")
+    b = _worst(R.assert_fp32, F.conv_transpose2d(cut(gy), cut(wt), padding=1), drs, f"{narrow} operands, dgrad")
+    print(f"\nREF64 staged cpu {tuple(x.shape)}: {narrow} operands {a:.1f} dgrad {b:.1f} x bound")
+    assert min(a, b) > 8.0                   # far outside, not at the edge (2^-9 and 2^-11 per operand against 2^-18)
+
+
+def test_fp32_one_dropped_tap_is_rejected(fp32_conv):
+    """one tap of one input channel zeroed for every output channel (a mis-zeroed halo piece / a skipped k step)"""
+    x, wt, _, rs, _ = fp32_conv
+    bad = wt.clone()
+    bad[:, wt.shape[1] // 2, 0, 2] = 0
+    assert _worst(R.assert_fp32, F.conv2d(x, bad, padding=1), rs, "dropped tap") > 100.0
+
+
+def test_fp32_accumulate_that_drops_the_old_value_is_rejected(fp32_conv):
+    x, wt, _, (ref, S), _ = fp32_conv
+    old = _gen(2999, tuple(ref.shape)).float()
+    acc = (ref + old.double(), S + old.double().abs())
+    R.assert_fp32(old + F.conv2d(x, wt, padding=1), acc, "fp32 host accumulate")
+    assert _worst(R.assert_fp32, F.conv2d(x, wt, padding=1), acc, "accumulate without the old value") > 100.0
+
+
+@pytest.fixture(scope="module", params=FP32_WGRAD_SHAPES, ids=str)
+def fp32_wgrad(request):
+    n, ci, co, h, w = request.param
+    seed = 3000 + ci + co + h
+    x, gy = _gen(seed, (n, ci, h, w)).float(), _gen(seed + 1, (n, co, h, w)).float()
+    return x, gy, R.conv3x3_wgrad(x, gy, dtype=F32)
+
+
+def test_fp32_host_weight_gradient_is_accepted(fp32_wgrad):
+    x, gy, rs = fp32_wgrad
+    assert _close(rs[0], torch.nn.grad.conv2d_weight(x.double(), tuple(rs[0].shape), gy.double(), padding=1))
+    got = R.assert_fp32(torch.nn.grad.conv2d_weight(x, tuple(rs[0].shape), gy, padding=1), rs, "fp32 host wgrad")
+    print(f"\nREF64 staged cpu wgrad K {x.shape[0] * x.shape[2] * x.shape[3]}: fp32 host {got:.3f} of the bound")
+    assert got <= 1.0
+
+
+def test_fp32_missing_pixel_tile_of_a_weight_gradient_is_rejected(fp32_wgrad):
+    """one 8 x 16 pixel tile of the last image (a split-K slab that was never written or never summed)"""
+    x, gy, rs = fp32_wgrad
+    cut = gy.clone()
+    cut[-1, :, 8:16, 16:32] = 0
+    bad = torch.nn.grad.conv2d_weight(x, tuple(rs[0].shape), cut, padding=1)
+    assert _worst(R.assert_fp32, bad, rs, "missing tile") > 100.0
+    assert float(((bad.double() - rs[0]).abs() > R.SUM_EPS * rs[1]).double().mean()) > 0.99      # every element sees it
+    cutb = R.conv3x3_wgrad(x.bfloat16().float(), gy.bfloat16().float(), dtype=F32)[0].float()
+    assert _worst(R.assert_fp32, cutb, rs, "bf16 operands, wgrad") > 8.0
+
+
+def test_fp32_convt_references_read_unrounded_operands():
+    x, w, b = _gen(3100, (2, 128, 5, 9)).float(), (_gen(3101, (128, 64, 2, 2)) * 0.1).float(), _gen(3102, (64,)).float()
+    gy = _gen(3103, (2, 64, 10, 18)).float()
+    y, dx = R.convt2x2(x, w, b, dtype=F32), R.convt2x2_dgrad(gy, w, dtype=F32)
+    (dw, db) = R.convt2x2_wgrad(x, gy, dtype=F32)
+    assert _close(y[0], F.conv_transpose2d(x.double(), w.double(), b.double(), stride=2))
+    R.assert_fp32(F.conv_transpose2d(x, w, b, stride=2), y, "fp32 host convT")
+    R.assert_fp32(F.conv2d(gy, w, stride=2), dx, "fp32 host convT dgrad")
+    R.assert_fp32(torch.einsum("nihw,nohywx->ioyx", x, gy.view(2, 64, 5, 2, 9, 2)), dw, "fp32 host convT wgrad")
+    R.assert_fp32(gy.sum((0, 2, 3)), db, "fp32 host convT bias gradient")
+    assert _worst(R.assert_fp32, F.conv_transpose2d(x.bfloat16().float(), w.bfloat16().float(), b, stride=2), y, "bf16") > 8.0
+    assert _worst(R.assert_fp32, F.conv2d(gy.bfloat16().float(), w.bfloat16().float(), stride=2), dx, "bf16 dgrad") > 8.0

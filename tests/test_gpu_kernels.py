@@ -1,9 +1,12 @@
 """GPU parity tests, kernel level: each C-ABI entry point of libunet_hip.so against the CPU oracle /
 plain fp32 torch on the same seeded inputs.  fp32 kernels are held to tight bounds (the parity mode);
 bf16 kernels are compared on bf16-rounded inputs with a bound set by bf16 output rounding (2^-8).
-The convolutions here, and the BatchNorm, pooling, bilinear, head, loss, anomaly-score and Adam kernels in
-test_gpu_streaming.py and the segmentation loss in test_gpu_segloss.py, are also held
-element by element to the float64 references of _ref64.py."""
+Held element by element to the float64 references of _ref64.py as well: here, the bf16 convolutions (forward, data and
+weight gradient, transposed convolutions, the image-layer kernels) -- the fp32 ones only through check(); the persistent
+bf16 kernels across CU budgets in test_gpu_partition.py; the fp32 mode (conv3_kernel<float>, igemm_kernel<float>,
+wgrad_kernel<float>) and the bf16 register-staged kernels on ragged frames, in their training forms, in
+test_gpu_staged.py; the folded inference form in test_gpu_inference.py; the BatchNorm, pooling, bilinear, head, loss,
+anomaly-score and Adam kernels in test_gpu_streaming.py and the segmentation loss in test_gpu_segloss.py."""
 import ctypes as C
 
 import pytest

@@ -287,8 +287,8 @@ class Guards:
         self.items.append((what, iv, numel, sent))
         return buf[MARGIN:MARGIN + numel]
 
-    def nhwc(self, n, c, h, w, what, fill=None):
-        t = self.alloc(n * c * h * w, torch.bfloat16, what).view(n, h, w, c).permute(0, 3, 1, 2)
+    def nhwc(self, n, c, h, w, what, fill=None, dtype=torch.bfloat16):
+        t = self.alloc(n * c * h * w, dtype, what).view(n, h, w, c).permute(0, 3, 1, 2)
         if fill is not None:
             t.copy_(fill)
         return t
