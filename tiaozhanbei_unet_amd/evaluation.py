@@ -1,6 +1,8 @@
 """Evaluation on the device, outside autograd: scores, confusion counts, AUROC / AUPRC, AUPRO, class regions, uint8 input."""
 import ctypes as C
+from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -149,7 +151,6 @@ class GaussianSmoother:
             raise ValueError(f"GaussianSmoother: sigma {self.sigma} at truncate {self.truncate} needs a radius above "
                              f"{SMOOTH_MAX_RADIUS}; the largest sigma that fits is below {limit:g}")
         self.radius = int(self.truncate * self.sigma + 0.5)
-        import numpy as np
         k = np.arange(self.radius + 1, dtype=np.float64)
         g = np.exp(-0.5 * (k / self.sigma) ** 2) if self.radius > 0 else np.ones(1)
         self.taps64 = g / (g[0] + 2.0 * g[1:].sum())
@@ -320,6 +321,23 @@ FRAGMENT_FIELDS = ("image", "class", "root", "group", "size")
 MAX_MERGE_GAP = 32              # the largest gap of unet_group_class_regions
 
 
+def _record_buffer(cap, fields, device):
+    """(out, records, count): a DEVICE int64 buffer of ``cap`` records of ``fields`` fields followed by their count, its
+    two parts as views, the count zeroed"""
+    out = torch.empty(cap * fields + 1, dtype=torch.int64, device=device)
+    out[-1:].zero_()
+    return out, out[:-1], out[-1:]
+
+
+def _host_records(host, cap, fields, by, too_many):
+    """the records of a ``_record_buffer`` read to the host, sorted by the columns ``by``, the most significant first"""
+    k = int(host[-1])
+    if k > cap:
+        raise RuntimeError(too_many)                   # cannot happen
+    rec = host[:-1].reshape(cap, fields)[:k]
+    return np.ascontiguousarray(rec[np.lexsort(tuple(rec[:, col] for col in reversed(by)))])
+
+
 def _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, cap):
     """unet_group_class_regions on labelled maps: (group, group_sizes, counts, DEVICE int64 buffer of ``cap`` records of
     FRAGMENT_FIELDS followed by their count); does not synchronise."""
@@ -327,9 +345,7 @@ def _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, cap):
     lib = L.lib()
     group, group_sizes = torch.empty_like(region), torch.empty_like(sizes)
     counts = torch.zeros((n, c), dtype=torch.int64, device=t.device)
-    out = torch.empty(cap * len(FRAGMENT_FIELDS) + 1, dtype=torch.int64, device=t.device)
-    records, count = out[:-1], out[-1:]
-    count.zero_()
+    out, records, count = _record_buffer(cap, len(FRAGMENT_FIELDS), t.device)
     ws = _workspace(lib.unet_group_class_regions_workspace(n, h, w, c), t.device)
     L.check(lib.unet_group_class_regions(_ptr(t), _ptr(region), _ptr(sizes), n, h, w, c, gap, min_pixels, image_base,
                                          _ptr(group), _ptr(group_sizes), _ptr(counts), _ptr(records), cap, _ptr(count),
@@ -337,21 +353,18 @@ def _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, cap):
     return group, group_sizes, counts, out
 
 
-def _fragment_records(host, cap, what):
-    """the records of ``_group_labelled``'s buffer on the host, sorted by (image, group, root)"""
-    import numpy as np
-    k = int(host[-1])
-    if k > cap:
-        raise RuntimeError(f"{what}: more fragments than regions")      # cannot happen
-    rec = host[:-1].reshape(cap, len(FRAGMENT_FIELDS))[:k]
-    return np.ascontiguousarray(rec[np.lexsort((rec[:, 2], rec[:, 3], rec[:, 0]))])
-
-
 def _merge_gap(what, merge_gap):
     g = int(merge_gap)
     if not 0 <= g <= MAX_MERGE_GAP:
         raise ValueError(f"{what}: merge_gap {merge_gap} is outside 0..{MAX_MERGE_GAP}")
     return g
+
+
+def _min_pixels_and_base(what, min_pixels, image_base):
+    if min_pixels < 1:
+        raise ValueError(f"{what}: min_pixels {min_pixels} is below 1")
+    if image_base < 0:
+        raise ValueError(f"{what}: image_base {image_base} is negative")
 
 
 def group_class_regions(labels_u8, region, sizes, num_classes, gap, min_pixels=1, image_base=0):
@@ -381,19 +394,27 @@ def group_class_regions(labels_u8, region, sizes, num_classes, gap, min_pixels=1
         raise _class_regions_error(what, n, h, w, num_classes)
     if not 1 <= gap <= MAX_MERGE_GAP:
         raise ValueError(f"{what}: gap {gap} is outside 1..{MAX_MERGE_GAP}")
-    if min_pixels < 1:
-        raise ValueError(f"{what}: min_pixels {min_pixels} is below 1")
-    if image_base < 0:
-        raise ValueError(f"{what}: image_base {image_base} is negative")
+    _min_pixels_and_base(what, min_pixels, image_base)
     region, sizes = region.contiguous(), sizes.contiguous()
     per = h * w
     index = torch.arange(1, per + 1, dtype=torch.int32, device=t.device).reshape(1, h, w)
-    cap = int((region == index).sum())                 # the region roots: every fragment is one
-    group, group_sizes, counts, out = _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, max(cap, 1))
-    return group, group_sizes, counts, _fragment_records(out.cpu().numpy(), max(cap, 1), what)
+    cap = max(int((region == index).sum()), 1)         # the region roots: every fragment is one
+    group, group_sizes, counts, out = _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, cap)
+    return group, group_sizes, counts, _host_records(out.cpu().numpy(), cap, len(FRAGMENT_FIELDS), (0, 3, 2),
+                                                     f"{what}: more fragments than regions")
 
 
 RECORD_FIELDS = ("image", "class", "root", "size", "hit")
+
+
+def _matcher_args(name, num_classes, min_pixels):
+    """(num_classes, min_pixels) of a matcher's constructor, refused outside 2..255 classes and below one pixel"""
+    c, mp = int(num_classes), int(min_pixels)
+    if not 2 <= c <= 255:
+        raise ValueError(f"{name}: {num_classes} classes, 2..255 are supported")
+    if mp < 1:
+        raise ValueError(f"{name}: min_pixels {min_pixels} is below 1")
+    return c, mp
 
 
 class ClassRegionMatcher:
@@ -409,11 +430,7 @@ class ClassRegionMatcher:
     once."""
 
     def __init__(self, num_classes, min_pixels=1):
-        self.num_classes, self.min_pixels = int(num_classes), int(min_pixels)
-        if not 2 <= self.num_classes <= 255:
-            raise ValueError(f"ClassRegionMatcher: {num_classes} classes, 2..255 are supported")
-        if self.min_pixels < 1:
-            raise ValueError(f"ClassRegionMatcher: min_pixels {min_pixels} is below 1")
+        self.num_classes, self.min_pixels = _matcher_args("ClassRegionMatcher", num_classes, min_pixels)
         self.images = 0
         self._chunks = []          # [truth records, pred records, class counts [2n, C], host counts, event or None]
 
@@ -462,7 +479,6 @@ class ClassRegionMatcher:
         """{"truth", "pred"}: int32 [K, 5] numpy records (image, class, root index y * W + x, size, hit), the image index
         counted over all updates, sorted by (image, root index); {"truth_counts", "pred_counts"}: int64
         [images, num_classes] regions per image and class (pred_counts before the min_pixels rule); "images"."""
-        import numpy as np
         c, f = self.num_classes, len(RECORD_FIELDS)
         empty = np.zeros((0, f), np.int32)
         res = {"truth": empty, "pred": empty.copy(), "truth_counts": np.zeros((0, c), np.int64),
@@ -504,23 +520,19 @@ def describe_class_regions(labels, num_classes, conf=None, min_pixels=1, image_b
     ``merge_gap`` >= 1 (at most 32) groups the regions first (``group_class_regions`` with this ``min_pixels``): a record
     then describes a group, ``root`` is the group's root, and the return value is (records, fragments), the second
     ``group_class_regions``' table, whose ``group`` column names the record a fragment went into.  0 changes nothing."""
-    import numpy as np
-    what = "describe_class_regions"
-    gap = _merge_gap(what, merge_gap)
-    t, cf, c, min_pixels, image_base = _describe_args(what, labels, num_classes, conf, min_pixels, image_base)
-    region, sizes, counts = label_class_regions(t, c)
-    cap = int(counts.sum())                            # every record is a region: there cannot be more
-    fd = len(DEFECT_FIELDS)
-    if cap == 0:
-        empty = np.zeros((0, fd), np.int64)
-        return (empty, np.zeros((0, len(FRAGMENT_FIELDS)), np.int64)) if gap else empty
-    if not gap:
-        out = _describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap)
-        return _defect_records(out.cpu().numpy(), cap, what)
-    group, group_sizes, _, frag = _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, cap)
-    out = _describe_labelled(t, group, group_sizes, cf, c, min_pixels, image_base, cap)
-    host = torch.cat([out, frag]).cpu().numpy()
-    return _defect_records(host[:cap * fd + 1], cap, what), _fragment_records(host[cap * fd + 1:], cap, what)
+    got = _checked_region_records("describe_class_regions", labels, num_classes, conf, min_pixels, image_base,
+                                  merge_gap=merge_gap)
+    return got.records if got.fragments is None else (got.records, got.fragments)
+
+
+def _conf_like(what, conf, shape, device):
+    """the fp32 contiguous ``conf``, refused unless it is a float tensor of the labels' ``shape`` on their ``device``"""
+    if not torch.is_tensor(conf) or not conf.is_floating_point() or tuple(conf.shape) != shape:
+        raise ValueError(f"{what}: conf is a float tensor {shape}, like the labels")
+    _require_cuda(conf)
+    if conf.device != device:
+        raise ValueError(f"{what}: labels and conf share one device")
+    return conf.detach().float().contiguous()
 
 
 def _describe_args(what, labels, num_classes, conf, min_pixels, image_base):
@@ -535,19 +547,8 @@ def _describe_args(what, labels, num_classes, conf, min_pixels, image_base):
         if nbytes == 0 or image_base + n >= 2 ** 31:
             raise _class_regions_error(what, n, h, w, num_classes)
     t = _class_maps(labels, what)
-    n, h, w = t.shape
-    if min_pixels < 1:
-        raise ValueError(f"{what}: min_pixels {min_pixels} is below 1")
-    if image_base < 0:
-        raise ValueError(f"{what}: image_base {image_base} is negative")
-    cf = None
-    if conf is not None:
-        if not torch.is_tensor(conf) or not conf.is_floating_point() or tuple(conf.shape) != (n, h, w):
-            raise ValueError(f"{what}: conf is a float tensor {(n, h, w)}, like the labels")
-        _require_cuda(conf)
-        if conf.device != t.device:
-            raise ValueError(f"{what}: labels and conf share one device")
-        cf = conf.detach().float().contiguous()
+    _min_pixels_and_base(what, min_pixels, image_base)
+    cf = None if conf is None else _conf_like(what, conf, tuple(t.shape), t.device)
     return t, cf, c, min_pixels, image_base
 
 
@@ -556,24 +557,12 @@ def _describe_labelled(t, region, sizes, cf, c, min_pixels, image_base, cap):
     DEFECT_FIELDS followed by their count."""
     n, h, w = t.shape
     lib = L.lib()
-    out = torch.empty(cap * len(DEFECT_FIELDS) + 1, dtype=torch.int64, device=t.device)
-    records, count = out[:-1], out[-1:]
-    count.zero_()
+    out, records, count = _record_buffer(cap, len(DEFECT_FIELDS), t.device)
     ws = _workspace(lib.unet_describe_class_regions_workspace(n, h, w, c), t.device)
     L.check(lib.unet_describe_class_regions(_ptr(t), _ptr(region), _ptr(sizes), _ptr(cf), n, h, w, c, min_pixels,
                                             image_base, _ptr(records), cap, _ptr(count), _ptr(ws), ws.numel(), _stream()),
             "unet_describe_class_regions")
     return out
-
-
-def _defect_records(host, cap, what):
-    """the sorted records of ``_describe_labelled``'s buffer, read to the host"""
-    import numpy as np
-    k = int(host[-1])
-    if k > cap:
-        raise RuntimeError(f"{what}: more records than regions")      # cannot happen
-    rec = host[:-1].reshape(cap, len(DEFECT_FIELDS))[:k]
-    return np.ascontiguousarray(rec[np.lexsort((rec[:, 2], rec[:, 0]))])
 
 
 from .defects import SHAPE_HEAD, direction_table  # noqa: E402  (numpy only: the host side of these records)
@@ -589,7 +578,7 @@ SHAPE_FIELDS = shape_fields(32)
 
 
 def _measure_args(what, labels, min_pixels, image_base, directions):
-    """(direction table int32 [D, 2], D) once the shape, ``directions``, ``min_pixels`` and ``image_base`` are known to be
+    """the direction table int32 [D, 2] once the shape, ``directions``, ``min_pixels`` and ``image_base`` are known to be
     ones unet_measure_class_regions takes; nothing is launched"""
     d, min_pixels, image_base = int(directions), int(min_pixels), int(image_base)
     if labels.dim() == 3 and labels.numel():
@@ -598,11 +587,8 @@ def _measure_args(what, labels, min_pixels, image_base, directions):
         if nbytes == 0 or image_base + n >= 2 ** 31:
             raise RuntimeError(f"{what}: {n} x {h} x {w} maps with {directions} directions are not supported (n < 65536, "
                                "at most 2^31 - 1 pixels, sides up to 16384, an even number of 2..32 directions)")
-    if min_pixels < 1:
-        raise ValueError(f"{what}: min_pixels {min_pixels} is below 1")
-    if image_base < 0:
-        raise ValueError(f"{what}: image_base {image_base} is negative")
-    return direction_table(d), d
+    _min_pixels_and_base(what, min_pixels, image_base)
+    return direction_table(d)
 
 
 def measure_class_regions(labels, num_classes, min_pixels=1, image_base=0, directions=32, merge_gap=0):
@@ -618,58 +604,33 @@ def measure_class_regions(labels, num_classes, min_pixels=1, image_base=0, direc
 
     ``merge_gap`` >= 1 measures groups as ``describe_class_regions`` describes them and returns (records, fragments); a
     group's bit-quads are those of the union of its fragments, so its Euler number is fragments minus holes."""
-    import numpy as np
+    what = "measure_class_regions"                     # its own order of refusals, then the family's pipeline
     _require_cuda(labels)
-    gap = _merge_gap("measure_class_regions", merge_gap)
+    gap = _merge_gap(what, merge_gap)
     c = int(num_classes)
     if labels.dim() == 3 and labels.numel():
         n, h, w = labels.shape
         if (L.lib().unet_label_class_regions_workspace(n, h, w, c) if 0 <= c < 2 ** 31 else 0) == 0:
-            raise _class_regions_error("measure_class_regions", n, h, w, num_classes)
-    table, d = _measure_args("measure_class_regions", labels, min_pixels, image_base, directions)
-    t = _class_maps(labels, "measure_class_regions")
-    region, sizes, counts = label_class_regions(t, c)
-    cap = int(counts.sum())
-    fs = len(SHAPE_HEAD) + 2 * d
-    if cap == 0:
-        empty = np.zeros((0, fs), np.int64)
-        return (empty, np.zeros((0, len(FRAGMENT_FIELDS)), np.int64)) if gap else empty
-    if not gap:
-        out = _measure_labelled(region, sizes, int(min_pixels), int(image_base), cap, table)
-        return _sorted_records(out.cpu().numpy(), cap, fs, 1, "measure_class_regions")
-    group, group_sizes, _, frag = _group_labelled(t, region, sizes, c, gap, int(min_pixels), int(image_base), cap)
-    out = _measure_labelled(group, group_sizes, int(min_pixels), int(image_base), cap, table)
-    host = torch.cat([out, frag]).cpu().numpy()
-    return (_sorted_records(host[:cap * fs + 1], cap, fs, 1, "measure_class_regions"),
-            _fragment_records(host[cap * fs + 1:], cap, "measure_class_regions"))
+            raise _class_regions_error(what, n, h, w, num_classes)
+    table = _measure_args(what, labels, min_pixels, image_base, directions)
+    t = _class_maps(labels, what)
+    got = _region_records(what, t, None, c, int(min_pixels), int(image_base), gap, False, table, False)
+    return got.shapes if got.fragments is None else (got.shapes, got.fragments)
 
 
 def _measure_labelled(region, sizes, min_pixels, image_base, cap, table):
     """unet_measure_class_regions on labelled maps: the DEVICE int64 buffer of ``cap`` records of
     ``shape_fields(len(table))`` followed by their count."""
-    import numpy as np
     n, h, w = region.shape
     lib = L.lib()
     table = np.ascontiguousarray(table, np.int32)
     d = table.shape[0]
-    out = torch.empty(cap * (len(SHAPE_HEAD) + 2 * d) + 1, dtype=torch.int64, device=region.device)
-    records, count = out[:-1], out[-1:]
-    count.zero_()
+    out, records, count = _record_buffer(cap, len(SHAPE_HEAD) + 2 * d, region.device)
     ws = _workspace(lib.unet_measure_class_regions_workspace(n, h, w, d), region.device)
     L.check(lib.unet_measure_class_regions(_ptr(region), _ptr(sizes), n, h, w, min_pixels, image_base,
                                            table.ctypes.data, d, _ptr(records), cap, _ptr(count), _ptr(ws), ws.numel(),
                                            _stream()), "unet_measure_class_regions")
     return out
-
-
-def _sorted_records(host, cap, fields, root_field, what):
-    """the records of a ``cap * fields + 1`` buffer (the count last), sorted by (image, root)"""
-    import numpy as np
-    k = int(host[-1])
-    if k > cap:
-        raise RuntimeError(f"{what}: more records than regions")      # cannot happen
-    rec = host[:-1].reshape(cap, fields)[:k]
-    return np.ascontiguousarray(rec[np.lexsort((rec[:, root_field], rec[:, 0]))])
 
 
 def describe_and_measure_class_regions(labels, num_classes, conf=None, min_pixels=1, image_base=0, directions=32,
@@ -686,52 +647,100 @@ def describe_and_measure_class_regions(labels, num_classes, conf=None, min_pixel
     on the groups, and the returned tuple gains ``group_class_regions``' fragment table as its last element.  The
     outlines stay those of the FRAGMENT labelling with the same ``min_pixels`` (a loop's ``root`` is its fragment's, and
     every fragment has exactly one outer loop); ``polygons.outlines`` attributes them to groups through the table."""
-    import numpy as np
-    what = "describe_and_measure_class_regions"
+    got = _checked_region_records("describe_and_measure_class_regions", labels, num_classes, conf, min_pixels, image_base,
+                                  shaped=not (contours and directions is None), directions=directions, contours=contours,
+                                  merge_gap=merge_gap)
+    out = (got.records, got.shapes) + ((got.loops, got.points) if contours else ())
+    return out if got.fragments is None else out + (got.fragments,)
+
+
+class RegionRecords(NamedTuple):
+    """What one labelling of class regions gave, by name: the numpy arrays that ``describe_class_regions``
+    (``records``), ``measure_class_regions`` (``shapes``), ``trace_class_regions`` (``loops``, ``points``) and
+    ``group_class_regions`` (``fragments``) return, None for what was not asked for."""
+    records: Optional[np.ndarray] = None
+    shapes: Optional[np.ndarray] = None
+    loops: Optional[np.ndarray] = None
+    points: Optional[np.ndarray] = None
+    fragments: Optional[np.ndarray] = None
+
+
+def class_region_records(labels, num_classes, conf=None, min_pixels=1, image_base=0, *, describe=True, directions=None,
+                         contours=False, merge_gap=0):
+    """The class-region records of integer label maps [N, H, W], every kind from ONE labelling, as ``RegionRecords``.
+    ``describe`` fills ``records`` as ``describe_class_regions`` gives them (``conf``, ``min_pixels`` and ``image_base``
+    are its arguments), ``directions`` (a number of Feret directions; None: no shapes) fills ``shapes`` as
+    ``measure_class_regions`` gives them, ``contours`` fills ``loops`` and ``points`` as ``trace_class_regions`` gives
+    them, and ``merge_gap`` >= 1 (at most 32) fills ``fragments`` with ``group_class_regions``' table: ``records`` and
+    ``shapes`` are then those of the groups, while the outlines stay those of the fragments.  Everything not asked for is
+    None, and the rows of ``records`` and ``shapes`` align.  Two host reads -- the region counts, then every record set in
+    one buffer -- and with ``contours`` the outlines as a third.  Maps without a region give empty arrays."""
+    return _checked_region_records("class_region_records", labels, num_classes, conf, min_pixels, image_base,
+                                   describe=describe, shaped=directions is not None, directions=directions,
+                                   contours=contours, merge_gap=merge_gap)
+
+
+def _checked_region_records(what, labels, num_classes, conf, min_pixels, image_base, describe=True, shaped=False,
+                            directions=None, contours=False, merge_gap=0):
+    """``_region_records`` of arguments that are refused, under the name ``what``, in the order of
+    ``describe_and_measure_class_regions``: the gap, ``describe_class_regions``' arguments, the directions, the outlines"""
     gap = _merge_gap(what, merge_gap)
     t, cf, c, min_pixels, image_base = _describe_args(what, labels, num_classes, conf, min_pixels, image_base)
-    shaped = not (contours and directions is None)
-    table, d = _measure_args(what, t, min_pixels, image_base, directions) if shaped else (None, 0)
+    table = _measure_args(what, t, min_pixels, image_base, directions) if shaped else None
     if contours:
         _trace_args(what, t)
-    fd, fs = len(DEFECT_FIELDS), len(SHAPE_HEAD) + 2 * d
+    if not (describe or shaped or contours or gap):
+        raise ValueError(f"{what}: nothing was asked for")
+    return _region_records(what, t, cf, c, min_pixels, image_base, gap, describe, table, contours)
+
+
+def _read_parts(parts):
+    """{name: host int64 array} of {name: DEVICE int64 buffer}, all of them in ONE read"""
+    device = list(parts.values())
+    host = (device[0] if len(device) == 1 else torch.cat(device)).cpu().numpy()      # one buffer needs no copy first
+    return dict(zip(parts, np.split(host, np.cumsum([p.numel() for p in device])[:-1])))
+
+
+def _region_records(what, t, cf, c, min_pixels, image_base, gap, describe, table, contours):
+    """The pipeline behind every function of the family, on checked arguments: label, group if ``gap``, launch what was
+    asked for (``describe``, a direction ``table``, ``contours``), read it all at once, sort on the host -> RegionRecords."""
+    fd, ff = len(DEFECT_FIELDS), len(FRAGMENT_FIELDS)
+    fs = 0 if table is None else len(SHAPE_HEAD) + 2 * len(table)
     region, sizes, counts = label_class_regions(t, c)
-    cap = int(counts.sum())
+    cap = int(counts.sum())                            # every record is a region: there cannot be more
     if cap == 0:
-        empty = (np.zeros((0, fd), np.int64), np.zeros((0, fs), np.int64) if shaped else None)
-        empty = empty + _no_outlines() if contours else empty
-        return empty + (np.zeros((0, len(FRAGMENT_FIELDS)), np.int64),) if gap else empty
-    whole, whole_sizes, frag = region, sizes, None     # what is described and measured: the regions or their groups
+        return RegionRecords(np.zeros((0, fd), np.int64) if describe else None,
+                             np.zeros((0, fs), np.int64) if fs else None, *(_no_outlines() if contours else (None, None)),
+                             np.zeros((0, ff), np.int64) if gap else None)
+    whole, whole_sizes, parts = region, sizes, {}      # what is described and measured: the regions or their groups
     if gap:
         whole, whole_sizes, _, frag = _group_labelled(t, region, sizes, c, gap, min_pixels, image_base, cap)
-    parts = [_describe_labelled(t, whole, whole_sizes, cf, c, min_pixels, image_base, cap)]
-    if shaped:
-        parts.append(_measure_labelled(whole, whole_sizes, min_pixels, image_base, cap, table))
+    if describe:
+        parts["records"] = _describe_labelled(t, whole, whole_sizes, cf, c, min_pixels, image_base, cap)
+    if fs:
+        parts["shapes"] = _measure_labelled(whole, whole_sizes, min_pixels, image_base, cap, table)
     if gap:
-        parts.append(frag)
+        parts["fragments"] = frag
     if contours:
-        parts.append(_count_edges(region, sizes, min_pixels))
-    both = torch.cat(parts).cpu().numpy()
-    rec = _defect_records(both[:cap * fd + 1], cap, what)
-    shapes = None
-    if shaped:
-        shapes = _sorted_records(both[cap * fd + 1:cap * (fd + fs) + 2], cap, fs, 1, what)
-        if len(rec) != len(shapes) or (rec[:, [0, 2, 3]] != shapes[:, :3]).any():
-            raise RuntimeError(f"{what}: the two record sets differ")      # cannot happen
-    tail = ()
+        parts["edges"] = _count_edges(region, sizes, min_pixels)
+    host = _read_parts(parts)
+    too_many = f"{what}: more records than regions"
+    rec = _host_records(host["records"], cap, fd, (0, 2), too_many) if describe else None
+    shapes = _host_records(host["shapes"], cap, fs, (0, 1), too_many) if fs else None
+    if describe and fs and (len(rec) != len(shapes) or (rec[:, [0, 2, 3]] != shapes[:, :3]).any()):
+        raise RuntimeError(f"{what}: the two record sets differ")      # cannot happen
+    fragments, loops, points = None, None, None
     if gap:
-        at = cap * fd + 1 + (cap * fs + 1 if shaped else 0)
-        tail = (_fragment_records(both[at:at + cap * len(FRAGMENT_FIELDS) + 1], cap, what),)
-    if not contours:
-        return (rec, shapes) + tail
-    return (rec, shapes) + _trace_counted(region, sizes, min_pixels, image_base, both[-3:].tolist(), what) + tail
+        fragments = _host_records(host["fragments"], cap, ff, (0, 3, 2), f"{what}: more fragments than regions")
+    if contours:
+        loops, points = _trace_counted(region, sizes, min_pixels, image_base, host["edges"].tolist(), what)
+    return RegionRecords(rec, shapes, loops, points, fragments)
 
 
 LOOP_FIELDS = ("image", "root", "leader", "n_points", "first_point", "area2")
 
 
 def _no_outlines():
-    import numpy as np
     return np.zeros((0, len(LOOP_FIELDS)), np.int64), np.zeros((0, 2), np.int32)
 
 
@@ -758,7 +767,6 @@ def _count_edges(region, sizes, min_pixels):
 def _trace_counted(region, sizes, min_pixels, image_base, counted, what):
     """unet_trace_class_regions with buffers of the ``counted`` {edges, loops, points}: (loops, points) on the host, one
     read"""
-    import numpy as np
     n, h, w = region.shape
     edges, n_loops, n_points = (int(v) for v in counted)
     if edges == 0:
@@ -797,10 +805,7 @@ def trace_class_regions(region, sizes, min_pixels=1, image_base=0):
         raise ValueError("trace_class_regions: region and sizes are the int32 tensors of label_class_regions")
     min_pixels, image_base = int(min_pixels), int(image_base)
     _trace_args("trace_class_regions", region)
-    if min_pixels < 1:
-        raise ValueError(f"trace_class_regions: min_pixels {min_pixels} is below 1")
-    if image_base < 0:
-        raise ValueError(f"trace_class_regions: image_base {image_base} is negative")
+    _min_pixels_and_base("trace_class_regions", min_pixels, image_base)
     region, sizes = region.contiguous(), sizes.contiguous()
     counted = _count_edges(region, sizes, min_pixels).tolist()
     return _trace_counted(region, sizes, min_pixels, image_base, counted, "trace_class_regions")
@@ -819,8 +824,7 @@ def _pairs_on_device(truth_region, pred_region, image_base, what):
     if truth_region.shape != pred_region.shape or truth_region.device != pred_region.device:
         raise ValueError(f"{what}: the two region maps differ in shape or device")
     image_base = int(image_base)
-    if image_base < 0:
-        raise ValueError(f"{what}: image_base {image_base} is negative")
+    _min_pixels_and_base(what, 1, image_base)          # pairs have no min_pixels
     tr, pr = truth_region.detach().contiguous(), pred_region.detach().contiguous()
     n, h, w = tr.shape
     if n >= 65536 or n * h * w >= 2 ** 31 or image_base + n >= 2 ** 31:
@@ -849,7 +853,6 @@ def _pairs_on_device(truth_region, pred_region, image_base, what):
 
 def _pair_records(host, record_cap, what):
     """the sorted int64 records of ``_pairs_on_device``'s buffer, read to the host"""
-    import numpy as np
     f = len(PAIR_FIELDS)
     count, overflow = (int(v) for v in host[record_cap * f:].view(np.int64))
     if overflow != 0 or count > record_cap:
@@ -866,7 +869,6 @@ def pair_class_regions(truth_region, pred_region, image_base=0):
     (csrc/regionpairs.hip; integers throughout, so the array is a function of the two maps alone).  Two host reads: the
     bound on the pairs per image, which sizes the hash tables (the next power of two >= twice the largest) and the
     record buffer, and the records with their count."""
-    import numpy as np
     out, record_cap = _pairs_on_device(truth_region, pred_region, image_base, "pair_class_regions")
     if out is None:
         return np.zeros((0, len(PAIR_FIELDS)), np.int64)
@@ -891,12 +893,8 @@ class DetectionMatcher:
     as labelled.  Dropped regions have id 0 in the grouped map and so make no pairs."""
 
     def __init__(self, num_classes, min_pixels=1, merge_gap=0):
-        self.num_classes, self.min_pixels = int(num_classes), int(min_pixels)
         self.merge_gap = _merge_gap("DetectionMatcher", merge_gap)
-        if not 2 <= self.num_classes <= 255:
-            raise ValueError(f"DetectionMatcher: {num_classes} classes, 2..255 are supported")
-        if self.min_pixels < 1:
-            raise ValueError(f"DetectionMatcher: min_pixels {min_pixels} is below 1")
+        self.num_classes, self.min_pixels = _matcher_args("DetectionMatcher", num_classes, min_pixels)
         self.images = 0
         self.image_sizes = []
         self._truth, self._pred, self._pairs = [], [], []
@@ -904,19 +902,13 @@ class DetectionMatcher:
     def update(self, pred_labels, conf, truth):
         """pred_labels / truth: integer device label maps of equal shape [N, H, W] (values outside 0..254 become 255);
         conf: float device tensor [N, H, W], the confidence of ``sheets.seg_confidence`` or of ``tiling.blend_tiles``."""
-        import numpy as np
         what = "DetectionMatcher.update"
         p = _class_maps(pred_labels, what)
         t = _class_maps(truth.to(p.device), what)
         if p.shape != t.shape:
             raise ValueError(f"{what}: prediction / truth shapes differ")
         n, h, w = p.shape
-        if not torch.is_tensor(conf) or not conf.is_floating_point() or tuple(conf.shape) != (n, h, w):
-            raise ValueError(f"{what}: conf is a float tensor {(n, h, w)}, like the labels")
-        _require_cuda(conf)
-        if conf.device != p.device:
-            raise ValueError(f"{what}: labels and conf share one device")
-        cf = conf.detach().float().contiguous()
+        cf = _conf_like(what, conf, (n, h, w), p.device)
         c, base = self.num_classes, self.images
         if L.lib().unet_describe_class_regions_workspace(n, h, w, c) == 0 or base + n >= 2 ** 31:
             raise _class_regions_error(what, n, h, w, c)
@@ -931,7 +923,8 @@ class DetectionMatcher:
             halves.append(_describe_labelled(maps, reg, siz, cfd, c, mp, base, cap) if cap else None)
         pairs, record_cap = _pairs_on_device(region[:n], preg, base, what)
         empty = np.zeros((0, len(DEFECT_FIELDS)), np.int64)
-        trec, prec = (_defect_records(o.cpu().numpy(), cap, what) if o is not None else empty
+        trec, prec = (empty if o is None else _host_records(o.cpu().numpy(), cap, len(DEFECT_FIELDS), (0, 2),
+                                                            f"{what}: more records than regions")
                       for o, cap in zip(halves, (cap_t, cap_p)))
         prs = np.zeros((0, len(PAIR_FIELDS)), np.int64)
         if pairs is not None:
@@ -949,8 +942,6 @@ class DetectionMatcher:
         with conf_sum_q = conf_max_q = 0), "pairs": int64 [K, 4] of PAIR_FIELDS sorted by (image, truth_root, pred_root),
         without the pairs of predicted regions below ``min_pixels``, "image_sizes": [(H, W)] per image, "images".  The
         image index counts over all updates; a root index is y * W + x in its own image's width."""
-        import numpy as np
-
         def cat(parts, fields):
             return np.concatenate(parts) if parts else np.zeros((0, len(fields)), np.int64)
 
@@ -1063,7 +1054,6 @@ class BoundaryMatcher:
         image index counted over all updates; "hist": int64 [num_classes - 1, 2, 1025], direction 0 = prediction to
         truth, 1 = truth to prediction, bin min(floor(distance), 1024); "band_widths" and "image_sizes" per image;
         "tolerances"; "images"}."""
-        import numpy as np
         c, f = self.num_classes, len(BOUNDARY_FIELDS)
         res = {"records": np.zeros((0, f), np.int64), "hist": np.zeros((c - 1, 2, BOUNDARY_HIST_BINS), np.int64),
                "band_widths": list(self.band_widths), "image_sizes": list(self.image_sizes),
@@ -1177,7 +1167,6 @@ class CalibrationMeter:
         """{"hist": int64 [num_classes, bins, 3] numpy {pixels, correct pixels, sum of q = rint(65536 conf)} by predicted
         class and bin, "skipped", "nll": float64 [K] summed over "counted" pixels, "nonfinite": pixels with a non-finite
         logit, set aside by the sweep, "temperatures", "temperature", "bins", "select"}."""
-        import numpy as np
         c, b, k = self.num_classes, self.bins, len(self.temperatures)
         res = {"hist": np.zeros((c, b, 3), np.int64), "skipped": 0, "nll": np.zeros(k, np.float64), "counted": 0,
                "nonfinite": 0, "temperatures": self.temperatures, "temperature": self.temperature, "bins": b,

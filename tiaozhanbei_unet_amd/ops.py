@@ -21,9 +21,9 @@ from ._hipcall import (BN_EPS, _DT, _as_nhwc, _is_nhwc, _nhwc_empty, _pad64, _pt
 from .evaluation import (BOUNDARY_FIELDS, BOUNDARY_NONE, DEFECT_FIELDS, FRAGMENT_FIELDS, LOOP_FIELDS, PAIR_FIELDS,
                          RECORD_FIELDS, SHAPE_FIELDS, BinaryAUC,
                          BoundaryMatcher, CalibrationMeter, ClassRegionMatcher, DetectionMatcher, GaussianSmoother,
-                         RegionOverlapAUC,
-                         anomaly_score, boundary_distance_sq, describe_and_measure_class_regions, describe_class_regions,
-                         group_class_regions, label_class_regions, label_regions, measure_class_regions,
+                         RegionOverlapAUC, RegionRecords,
+                         anomaly_score, boundary_distance_sq, class_region_records, describe_and_measure_class_regions,
+                         describe_class_regions, group_class_regions, label_class_regions, label_regions, measure_class_regions,
                          pair_class_regions, preprocess_u8, shape_fields, threshold_confusion, trace_class_regions)
 from .sheets import (IMAGENET_MEAN, IMAGENET_STD, MAX_PANELS, TAB10, class_palette, colormap_lut, panel_range,
                      render_seg_sheet, render_sheet, seg_confidence, viridis_lut)

@@ -130,17 +130,16 @@ def collate_images(samples):
 
 def predict_batches(model, loader, size, num_classes, min_pixels, device, directions=None, contours=False, merge_gap=0):
     """Eval-mode pass over ``collate_images`` batches.  Yields per batch (indices, original sizes [(H0, W0)], normalised
-    images, labels uint8 [N, H, W], frame mean confidence list, records with ``image`` = the dataset index).  The records
-    and the means are the batch's host reads.  With ``directions`` (a number of Feret directions) the records are the
-    pair (records, shape records) of ``evaluation.describe_and_measure_class_regions``: one labelling, the same reads.
-    With ``contours`` they are its four (records, shape records or None, loops, points), ``image`` mapped in the loops too.
-    With ``merge_gap`` the records are those of the groups and the tuple (a pair at the least) ends with the fragment
-    table, ``image`` mapped there too."""
+    images, labels uint8 [N, H, W], frame mean confidence list, the batch's ``evaluation.RegionRecords``).  The records
+    and the means are the batch's host reads.  ``.records`` is always there; ``directions`` (a number of Feret directions)
+    fills ``.shapes``, ``contours`` fills ``.loops`` and ``.points``, and ``merge_gap`` fills ``.fragments`` and makes the
+    records and shapes those of the groups: one labelling, the same reads, None for what was not asked for.  ``image`` is
+    the dataset index in every member that has the column: records, shapes, loops and fragments."""
     import numpy as np
     import torch
     from . import sheets
     from .augment import DeviceTransform
-    from .evaluation import describe_and_measure_class_regions, describe_class_regions
+    from .evaluation import class_region_records
     from .metrics import per_image_stats
     tf = DeviceTransform(tuple(size), train=False)
     model.eval()
@@ -151,19 +150,12 @@ def predict_batches(model, loader, size, num_classes, min_pixels, device, direct
             logits = model(x)
             labels, conf = sheets.seg_confidence(logits)
             means = per_image_stats(logits)["conf_mean"]
-            if directions is None and not contours and not merge_gap:
-                records = describe_class_regions(labels, num_classes, conf, min_pixels)
-                records[:, 0] = np.asarray(idx, np.int64)[records[:, 0]]
-            else:
-                if directions is None and not contours:
-                    records = describe_class_regions(labels, num_classes, conf, min_pixels, merge_gap=merge_gap)
-                else:
-                    records = describe_and_measure_class_regions(labels, num_classes, conf, min_pixels, 0, directions,
-                                                                 contours=contours, merge_gap=merge_gap)
-                for rec in records[:3] + (records[-1:] if merge_gap and len(records) > 3 else ()):
-                    if rec is not None:
-                        rec[:, 0] = np.asarray(idx, np.int64)[rec[:, 0]]
-            yield idx, sizes, x, labels, means.tolist(), records
+            got = class_region_records(labels, num_classes, conf, min_pixels, directions=directions, contours=contours,
+                                       merge_gap=merge_gap)
+            for rec in (got.records, got.shapes, got.loops, got.fragments):      # ``points`` has no image column
+                if rec is not None:
+                    rec[:, 0] = np.asarray(idx, np.int64)[rec[:, 0]]
+            yield idx, sizes, x, labels, means.tolist(), got
 
 
 def image_loader(paths, batch_size, num_workers):
@@ -185,20 +177,17 @@ def main(argv=None):
     originals, frame_means, records, shapes, traced = [None] * len(paths), [None] * len(paths), [], [], {}
     rules, polygon_rules = seg_cli.size_rules_of(args), seg_cli.polygon_rules_of(args)
     merge_gap, fragments = getattr(args, "merge_gap", 0), []
-    for idx, sizes, x, labels, means, rec in predict_batches(model, loader, args.image_size, num_classes,
+    for idx, sizes, x, labels, means, got in predict_batches(model, loader, args.image_size, num_classes,
                                                              args.min_region_pixels, device,
                                                              None if rules is None else seg_cli.DIRECTIONS,
                                                              polygon_rules is not None, merge_gap):
-        if merge_gap:
-            fragments.append(rec[-1])
-            rec = rec[:-1] if len(rec) > 2 else rec[0]
-        if polygon_rules is not None:
-            traced.update(polygons.outlines(rec[2], rec[3], fragments[-1] if merge_gap else None))
+        records.append(got.records)
         if rules is not None:
-            shapes.append(rec[1])
-        if rules is not None or polygon_rules is not None:
-            rec = rec[0]
-        records.append(rec)
+            shapes.append(got.shapes)
+        if polygon_rules is not None:
+            traced.update(polygons.outlines(got.loops, got.points, got.fragments))
+        if merge_gap:
+            fragments.append(got.fragments)
         if args.mask_size == "frame":
             host = labels.cpu().numpy()
         for k, i in enumerate(idx):

@@ -291,14 +291,11 @@ def describe_regions(args, labels, num_classes, conf):
     ``--merge_gap`` the records are those of the groups, and the outlines are keyed by group."""
     from . import evaluation, polygons
     shaped, traced = size_rules_of(args) is not None, polygon_rules_of(args) is not None
-    gap = getattr(args, "merge_gap", 0)
-    if not shaped and not traced:
-        got = evaluation.describe_class_regions(labels, num_classes, conf, args.min_region_pixels, merge_gap=gap)
-        return (got[0], None, None, got[1]) if gap else (got, None, None, None)
-    got = evaluation.describe_and_measure_class_regions(labels, num_classes, conf, args.min_region_pixels, 0,
-                                                        DIRECTIONS if shaped else None, contours=traced, merge_gap=gap)
-    frag = got[-1] if gap else None
-    return got[0], got[1], polygons.outlines(got[2], got[3], frag) if traced else None, frag
+    got = evaluation.class_region_records(labels, num_classes, conf, args.min_region_pixels,
+                                          directions=DIRECTIONS if shaped else None, contours=traced,
+                                          merge_gap=getattr(args, "merge_gap", 0))
+    outlines = polygons.outlines(got.loops, got.points, got.fragments) if traced else None
+    return got.records, got.shapes, outlines, got.fragments
 
 
 def save_label_file(args, name, entry, frame_hw):
