@@ -1,5 +1,10 @@
 """ctypes binding of libunet_hip.so (C-ABI declared in include/unet_hip.h).
 
+The header is the one statement of every entry point's signature: SIGNATURES (name -> restype, argtypes) is read from
+its declarations when first asked for, by lib() or by name, and a new entry point needs nothing here.  Importing this
+module reads no file.  The structures and enum values below are needed at import, so they restate the header by hand;
+tests/test_cpu_abi.py holds them to it.
+
 The library is the ONLY compute path of this package: there is no CPU or eager
 PyTorch fallback.  If the shared object is missing or a call fails, a RuntimeError
 is raised -- loudly -- instead of silently computing something else.
@@ -7,12 +12,15 @@ is raised -- loudly -- instead of silently computing something else.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UNET_HIP_LIB") or os.path.join(_HERE, "libunet_hip.so")   # (override: diagnostic builds)
 CSRC = os.path.join(_HERE, "csrc")
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "unet_hip.h")
 
 UNET_F32, UNET_BF16 = 0, 1
 PACK_CONV_FWD, PACK_CONV_DGRAD, PACK_CONVT_FWD, PACK_CONVT_DGRAD = 0, 1, 2, 3
@@ -76,147 +84,54 @@ class MergeView(C.Structure):
     _fields_ = [("logits", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("flip_x", C.c_int32), ("flip_y", C.c_int32)]
 
 
-_i, _l, _f, _p, _z, _d = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_double
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double,
+            "size_t": C.c_size_t}
+_DECLARATION = re.compile(r"((?:\bconst\s+)?\b\w+[\s*]+)(unet_[a-z0-9_]+)\s*\(([^;{()]*)\)\s*;")
 
-# name -> (restype, argtypes): every symbol include/unet_hip.h declares
-SIGNATURES = {
-    "unet_abi_version": (_i, []),
-    "unet_last_error": (C.c_char_p, []),
-    "unet_set_reserved_cus": (_i, [_i]),
-    "unet_get_cu_budget": (_i, []),
-    "unet_debug_spin": (_i, [_i, _i, _i, _p]),
-    "unet_prof_enable": (_i, [_i]),
-    "unet_prof_collect": (_i, [_p, _p, _p]),
-    "unet_prof_kernel_stats": (_i, [_i, _p, _p, _p, _p]),
-    "unet_prof_kernel_bytes": (_i, [_i, _p]),
-    "unet_nchw_to_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "unet_nhwc_to_nchw": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "unet_pack_weight": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "unet_pack_weights_batched": (_i, [_p, _i, _i, _p]),
-    "unet_pack_weight_seg": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "unet_pack_conv_weight_folded_seg": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "unet_remap_batched": (_i, [_p, _i, _p]),
-    "unet_widen_channels": (_i, [_p, _i, _p, _i, _i, _i, _i, _p, _i, _i, _p]),
-    "unet_conv3x3": (_i, [_i, _i, _i, _i, C.POINTER(View), _p, _i, C.POINTER(View), _i, _i, _i, _p]),
-    "unet_pack_conv_weight_folded": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "unet_conv3x3_bias_relu": (_i, [_i, _i, _i, _i, C.POINTER(View), _p, _i, _p, _p, _i, _p]),
-    "unet_conv3x3_stats_max_parts": (_z, [_i, _i, _i]),
-    "unet_conv3x3_stats": (_i, [_i, _i, _i, _i, C.POINTER(View), _p, _i, _p, _p, _p, _p]),
-    "unet_conv3x3_first_supported": (_i, [_i, _i, _i, _i]),
-    "unet_conv3x3_first_stats": (_i, [_i, _i, _i, _p, _i, _p, _p, _p, _p, _p]),
-    "unet_conv3x3_first_wgrad_workspace": (_z, [_i, _i, _i]),
-    "unet_conv3x3_first_wgrad": (_i, [_i, _i, _i, _p, _i, _p, _p, _p, _z, _p]),
-    "unet_conv3x3_first_wgrad_bn": (_i, [_i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _z, _p]),
-    "unet_bn_finalize_partials": (_i, [_p, _i, _l, _i, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p]),
-    "unet_convt2x2_dgrad_bnrelu_supported": (_i, [_i, _i, _i, _i, _i, _i]),
-    "unet_convt2x2_dgrad_bnrelu_max_parts": (_z, []),
-    "unet_convt2x2_dgrad_bnrelu": (_i, [_i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
-    "unet_conv3x3_dgrad_bnrelu_supported": (_i, [_i, _i, _i, _i, _i, _i]),
-    "unet_conv3x3_dgrad_bnrelu": (_i, [_i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "unet_conv3x3_wgrad_workspace": (_z, [_i, _i, _i, _i, _i]),
-    "unet_conv3x3_wgrad": (_i, [_i, _i, _i, _i, C.POINTER(View), _p, _i, _p, _i, _p, _z, _p]),
-    "unet_convt2x2_fwd": (_i, [_i, _i, _i, _i, _p, _i, _p, _p, _p, _i, _p]),
-    "unet_convt2x2_dgrad": (_i, [_i, _i, _i, _i, _p, _i, _p, _p, _i, _p]),
-    "unet_convt2x2_wgrad_workspace": (_z, [_i, _i, _i, _i, _i]),
-    "unet_convt2x2_wgrad": (_i, [_i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _z, _p]),
-    "unet_bn_workspace": (_z, [_l, _i]),
-    "unet_bn_train_stats": (_i, [_i, _p, _l, _i, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _z, _p]),
-    "unet_bn_eval_coeffs": (_i, [_i, _p, _p, _p, _p, _f, _p, _p, _p]),
-    "unet_bn_eval_coeffs4": (_i, [_i, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p]),
-    "unet_bn_relu_bwd_frozen": (_i, [_i, _p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "unet_bn_relu_apply": (_i, [_i, _p, _l, _i, _p, _p, _p, _p]),
-    "unet_bn_relu_bwd": (_i, [_i, _p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "unet_bn_bwd_premasked": (_i, [_i, _p, _p, _l, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _z, _p]),
-    "unet_head_bnrelu_fwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p]),
-    "unet_head_bnrelu_max_parts": (_z, []),
-    "unet_head_bnrelu_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "unet_head_bnrelu_bwd_sums": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
-    "unet_head_bnrelu_bwd_apply": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
-    "unet_maxpool2_fwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p]),
-    "unet_maxpool2_bwd": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
-    "unet_bn_relu_pool_supported": (_i, [_i, _i]),
-    "unet_bn_relu_pool_fwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
-    "unet_bn_relu_pool_max_parts": (_z, []),
-    "unet_bn_relu_pool_bwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
-    "unet_bn_relu_pool_bwd_sums": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
-    "unet_bn_relu_pool_bwd_apply": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
-    "unet_upsample_bilinear2x_fwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p]),
-    "unet_upsample_bilinear2x_bwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p]),
-    "unet_head_fwd": (_i, [_i, _p, _i, _i, _i, _i, _p, _p, _i, _i, _p, _p]),
-    "unet_head_bwd_workspace": (_z, [_i, _i, _i, _i, _i]),
-    "unet_head_bwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _z, _p]),
-    "unet_loss_workspace": (_z, [_l]),
-    "unet_loss_mse_focal": (_i, [_p, _p, _l, _p, _p, _l, _f, _f, _p, _p, _p, _p, _z, _p]),
-    "unet_ssim_workspace": (_z, [_i, _i, _i]),
-    "unet_ssim_loss": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
-    "unet_ssim_loss_per_image": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
-    "unet_seg_loss_workspace": (_z, [_i, _i, _l]),
-    "unet_seg_loss": (_i, [_p, _p, _i, _i, _l, _p, _l, _i, _f, _f, _f, _f, _f, _p, _p, _p, _z, _p]),
-    "unet_seg_confusion": (_i, [_p, _p, _i, _i, _l, _l, _p, _p, _p]),
-    "unet_seg_image_stats_workspace": (_z, [_i, _i, _l]),
-    "unet_seg_image_stats": (_i, [_p, _p, _i, _i, _l, _l, _p, _p, _p, _p, _z, _p]),
-    "unet_threshold_confusion": (_i, [_p, _p, _p, _l, _l, _p, _i, _p, _p]),
-    "unet_rank_auc_append": (_i, [_p, _p, _p, _l, _l, _p, _l, _p, _p]),
-    "unet_rank_auc_workspace": (_z, [_l, _l]),
-    "unet_rank_auc": (_i, [_p, _l, _p, _l, _p, _p, _z, _p]),
-    "unet_label_regions_workspace": (_z, [_l, _l, _l]),
-    "unet_label_regions": (_i, [_p, _p, _l, _l, _l, _p, _p, _p, _p, _z, _p]),
-    "unet_label_class_regions_workspace": (_z, [_l, _l, _l, _i]),
-    "unet_label_class_regions": (_i, [_p, _l, _l, _l, _i, _p, _p, _p, _p, _z, _p]),
-    "unet_match_class_regions_workspace": (_z, [_l, _l, _l, _i]),
-    "unet_match_class_regions": (_i, [_p, _p, _p, _p, _p, _p, _l, _l, _l, _i, _i, _i, _p, _p, _l, _p, _p, _z, _p]),
-    "unet_group_class_regions_workspace": (_z, [_l, _l, _l, _i]),
-    "unet_group_class_regions": (_i, [_p, _p, _p, _l, _l, _l, _i, _i, _i, _i, _p, _p, _p, _p, _l, _p, _p, _z, _p]),
-    "unet_region_pair_bound": (_i, [_p, _p, _l, _l, _l, _p, _p]),
-    "unet_region_pairs_workspace": (_z, [_l, _l]),
-    "unet_region_pairs": (_i, [_p, _p, _l, _l, _l, _l, _i, _p, _l, _p, _p, _p, _z, _p]),
-    "unet_describe_class_regions_workspace": (_z, [_l, _l, _l, _i]),
-    "unet_describe_class_regions": (_i, [_p, _p, _p, _p, _l, _l, _l, _i, _i, _i, _p, _l, _p, _p, _z, _p]),
-    "unet_measure_class_regions_workspace": (_z, [_l, _l, _l, _i]),
-    "unet_measure_class_regions": (_i, [_p, _p, _l, _l, _l, _i, _i, _p, _i, _p, _l, _p, _p, _z, _p]),
-    "unet_count_class_region_edges_workspace": (_z, [_l, _l, _l]),
-    "unet_count_class_region_edges": (_i, [_p, _p, _l, _l, _l, _i, _p, _p, _z, _p]),
-    "unet_trace_class_regions_workspace": (_z, [_l, _l, _l, _l]),
-    "unet_trace_class_regions": (_i, [_p, _p, _l, _l, _l, _i, _i, _l, _p, _l, _p, _l, _p, _p, _z, _p]),
-    "unet_boundary_distance_sq_workspace": (_z, [_l, _l, _l, _i]),
-    "unet_boundary_distance_sq": (_i, [_p, _l, _l, _l, _i, _p, _p, _z, _p]),
-    "unet_boundary_stats": (_i, [_p, _p, _p, _p, _l, _l, _l, _i, _p, _i, _i, _i, _p, _p, _p]),
-    "unet_region_auc_append": (_i, [_p, _p, _p, _l, _l, _p, _l, _p, _p]),
-    "unet_region_auc_workspace": (_z, [_l, _l]),
-    "unet_region_auc": (_i, [_p, _l, _p, _l, _l, _l, _d, _p, _p, _z, _p]),
-    "unet_render_range": (_i, [_p, _i, _i, _i, _i, _p, _p]),
-    "unet_render_sheet": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
-    "unet_seg_confidence": (_i, [_p, _i, _i, _l, _p, _p, _p]),
-    "unet_seg_render_sheet": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
-    "unet_seg_confidence_scaled": (_i, [_p, _i, _i, _l, _f, _p, _p, _p]),
-    "unet_reliability_histogram": (_i, [_p, _p, _p, _i, _l, _i, _i, _l, _i, _p, _p, _p]),
-    "unet_temperature_sweep_workspace": (_z, [_i, _l, _i]),
-    "unet_temperature_sweep": (_i, [_p, _p, _i, _i, _l, _l, _i, _p, _i, _p, _p, _p, _z, _p]),
-    "unet_channel_scale": (_i, [_i, _p, _p, _i, _l, _i, _p, _p]),
-    "unet_anomaly_score_workspace": (_z, [_i, _l]),
-    "unet_anomaly_score": (_i, [_p, _p, _i, _i, _l, _i, _p, _p, _p, _z, _p]),
-    "unet_preprocess_u8": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
-    "unet_resize_bilinear_ksize": (_i, [_i, _i]),
-    "unet_resize_bilinear_coeffs": (_i, [_i, _i, _p, _p]),
-    "unet_resize_bilinear_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p]),
-    "unet_resize_nearest_index": (_i, [_i, _i, _p]),
-    "unet_resize_nearest_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
-    "unet_polygon_mask_u8": (_i, [_p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p]),
-    "unet_polygon_class_histogram": (_i, [_p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _p, _p]),
-    "unet_flip_rotate_u8": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
-    "unet_color_jitter_workspace": (_z, [_i]),
-    "unet_color_jitter_normalize_u8": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
-    "unet_synth_anomalies": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "unet_smooth_maps": (_i, [_p, _p, _l, _i, _i, _p, _i, _p, _p]),
-    "unet_tile_gather": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p]),
-    "unet_tile_blend": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
-    "unet_view_merge": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
-    "unet_affine_crop_u8":(_i, [_p, _l, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
-    "unet_paste_crop_u8": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "unet_adam_chunk_elems": (_i, []),
-    "unet_adam_multi": (_i, [_p, _p, _i, _f, _d, _d, _f, _f, _f, _i, _i, _p]),
-    "unet_adam_step": (_i, [_p, _p, _p, _p, _l, _f, _d, _d, _f, _f, _f, _i, _p]),
-}
+
+def _ctype(spec: str, is_param: bool):
+    """One return type, or one parameter with or without its name, through the closed table; None outside it."""
+    words = re.sub(r"\bconst\b|\*|\[\d*\]", " ", spec).split()
+    if "*" in spec or "[" in spec:
+        if is_param and words:
+            return C.POINTER(View) if words[0] == "unet_view" else C.c_void_p
+        return C.c_char_p if "".join(spec.split()) == "constchar*" else None
+    return _SCALARS.get(words[0]) if 1 <= len(words) <= 1 + is_param else None
+
+
+def read_signatures(header: str) -> dict:
+    """name -> (restype, argtypes) of every `ret unet_name(params);` in the text of a header.  A type outside the
+    table above is never guessed: it is an error that quotes the declaration, for whoever adds the type to extend it."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header, flags=re.S)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", " ", text, flags=re.M)     # preprocessor lines, macros among them
+    signatures = {}
+    for decl in _DECLARATION.finditer(text):
+        ret, name, params = decl.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        specs = [(ret, False)] + [(p, True) for p in params]
+        types = [_ctype(spec, is_param) for spec, is_param in specs]
+        if None in types:
+            raise RuntimeError(f"no ctypes type for `{specs[types.index(None)][0].strip()}` in the declaration "
+                               f"`{' '.join(decl.group(0).split())}`: extend the table of _lib.py")
+        signatures[name] = (types[0], types[1:])
+    return signatures
+
+
+@functools.lru_cache(maxsize=None)
+def _signatures() -> dict:
+    if not os.path.exists(HEADER):
+        raise RuntimeError(
+            f"unet_hip.h not found at {HEADER}: it is the one statement of the library's signatures, and the binding "
+            "of libunet_hip.so reads every restype and argtypes from it.")
+    with open(HEADER) as f:
+        return read_signatures(f.read())
+
+
+def __getattr__(name):
+    if name == "SIGNATURES":        # name -> (restype, argtypes): every symbol the header declares, read on first use
+        return _signatures()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
 
 _lib = None
 
@@ -233,7 +148,7 @@ def _stale() -> bool:
         return False
     t = os.path.getmtime(LIB_PATH)
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs.append(os.path.join(_HERE, "..", "include", "unet_hip.h"))
+    srcs.append(HEADER)
     return any(os.path.exists(s) and os.path.getmtime(s) > t for s in srcs)
 
 
@@ -247,7 +162,7 @@ def lib():
                 "tiaozhanbei_unet_amd (no CPU/eager fallback). Build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C tiaozhanbei_unet_amd/csrc`.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in _signatures().items():
             fn = getattr(handle, name)      # AttributeError if the .so does not export it
             fn.restype, fn.argtypes = res, args
         if handle.unet_abi_version() != 1:
