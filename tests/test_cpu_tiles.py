@@ -4,6 +4,7 @@ predict_tiled CLI's flags and refusals."""
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -129,7 +130,10 @@ def test_symbols_are_declared_bound_and_exported():
         assert name in _lib.SIGNATURES, name
         assert hasattr(handle, name), name
     assert handle.unet_abi_version() == 1
-    assert " tiles.hip" in makefile and "build/tiles.o: CXXFLAGS += -ffp-contract=off" in makefile
+    assert " tiles.hip" in makefile
+    for obj in ("build/tiles.o", "build/stamps/tiles.o"):      # what make would run, for the default and the diagnostic build
+        line = subprocess.run(["make", "-C", _lib.CSRC, "-n", "-B", obj], capture_output=True, text=True, check=True).stdout
+        assert re.search(rf" -ffp-contract=off .*-c tiles\.hip -o {obj}\n", line), line
     for name in ("plan_axis", "plan_tiles", "gather_tiles", "blend_tiles", "TiledPredictor"):
         assert hasattr(tiling, name) and not hasattr(ops, name), name
 

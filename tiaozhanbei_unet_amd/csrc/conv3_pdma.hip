@@ -60,9 +60,6 @@ struct CfgP {
 // lock-step tap went to the DMA issue burst, profiles/r02_pdma_stamps.txt).  LDS hazards at distance one barrier: a
 // slab / patch buffer is re-filled by DMAs issued in the slot after its last reads, which are retired (lgkmcnt(0))
 // BEFORE the barrier that ends their LOAD.
-#ifndef PDMA_DEFER128
-#define PDMA_DEFER128 (!PP && !BNBWD)
-#endif
 // PAIR (round 4; BN = 64, exactly two 64-channel chunks = the 128 -> 64 layers at 256 x 256 and the 128 -> 64 data
 // gradient): with 64-channel tiles a tap is only 16 MFMAs per wave, and the stamps (profiles/r04_pdma64_stamps.txt) put
 // ~800 of its 1 300 cycles into what a tap costs regardless of its size -- the barrier skew, the DMA-issue burst, the
@@ -353,11 +350,12 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
     if (grp) __builtin_amdgcn_s_barrier();                              // the stagger: waves 4-7 one barrier behind
   }
 
-#ifdef PDMA_STAMPS
-  // diagnostic build: per-wave cycle sums of (vmcnt wait, barrier, DMA issue, fragment reads + MFMAs) over all taps
-  unsigned long long st_sum[4] = {0, 0, 0, 0}, st_prev = 0, st_taps = 0, st_epi = 0, st_b2 = 0, st_rd = 0;
-  const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  // diagnostic build (stamps.h; nothing in the default build): per-wave cycle sums over all taps.  Lock-step laps: 0 the
+  // counted vmcnt wait, 1 the barrier, 2 DMA issue, 3 fragment reads + MFMAs, 4 the epilogues.  Ping-pong laps: 0 fragment
+  // reads + DMA issue (4: the reads' issue alone, inside 0), 1 the waits, 2 the barrier that ends LOAD, 3 MFMAs, 5 the
+  // barrier that ends COMPUTE.  The clock is paused across an epilogue.
+  StampClock clk;
+  clk.start(false);
   int pbuf_i = 0;                                 // patch buffer of the chunk being computed
   bool after_epilogue = false;
   const bool late_dma = !PP && P.pdma_stagger && __builtin_amdgcn_readfirstlane(wave) < 4;
@@ -369,7 +367,7 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
   // forward kernel has them since the output addressing went scalar (215 -> 247 VGPRs, +0..4 % per layer,
   // profiles/r03_pdma_dense_epilogue.txt); the ping-pong and BatchNorm-backward instantiations (251 / 236) would spill, so
   // there every item reduces and a thread carries the total.  Fixed order either way: deterministic.
-  constexpr bool DEFER = BN == 64 || PDMA_DEFER128;
+  constexpr bool DEFER = BN == 64 || (!PP && !BNBWD);
   // Output addressing of dense destinations (P.pdma_dense: every destination view covers the frame at offset 0; frames are
   // whole 16x16 tiles here anyway): a lane's offset inside a (tile, 32-channel pair) never changes -- lp[view]: pixel row 0
   // of its four; rows 1-3 through the scalar offset operand, which the range check ignores -- and the work item enters
@@ -460,25 +458,17 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
           // ---- LOAD
-#ifdef PDMA_STAMPS
-          const unsigned long long st_a = __builtin_amdgcn_s_memtime();
-          if (st_prev) st_b2 += st_a - st_prev;
-#endif
+          clk.resume(5);
           load_frags(pbuf, (tap / 3) * C::RS + (tap % 3) * C::PSTR, tap % 3);
           __builtin_amdgcn_sched_barrier(0);
-#ifdef PDMA_STAMPS
-          st_rd += __builtin_amdgcn_s_memtime() - st_a;
-#endif
+          clk.add(4, clk.now() - clk.last());
           if (tap < C::NDA) dma_patch(last ? 0 : c + 1, tap, pbuf_i ^ 1, last ? d_live : true);
           if (tap + 2 < 9) dma_w(c_wbase, c, tap + 2, (tap + 2) % 3, true);
           else if (!last) dma_w(c_wbase, c + 1, tap + 2 - 9, (tap + 2) % 3, true);
           else dma_w(d_wbase, 0, tap + 2 - 9, (tap + 2) % 3, d_live);
           // everything older than THIS phase's DMAs has landed: the next step's weight slab (issued one step ago) and,
           // by then, every patch piece of the next chunk [the previous work item's output stores sit in between]
-#ifdef PDMA_STAMPS
-          const unsigned long long st_b = __builtin_amdgcn_s_memtime();
-          st_sum[0] += st_b - st_a;
-#endif
+          clk.mark(0);
           if (tap == 0 && c == 0 && after_epilogue) {                  // (tap 0 always carries a patch piece)
             if (P.stats) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(1 + C::NDW + C::NST + 1) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(1 + C::NDW + C::NST) : "memory");
@@ -488,37 +478,25 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::NDW) : "memory");
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef PDMA_STAMPS
-          const unsigned long long st_c = __builtin_amdgcn_s_memtime();
-          st_sum[1] += st_c - st_b;
-#endif
+          clk.mark(1);
           __builtin_amdgcn_sched_barrier(0);
           __builtin_amdgcn_s_barrier();
           __builtin_amdgcn_sched_barrier(0);
-#ifdef PDMA_STAMPS
-          const unsigned long long st_d = __builtin_amdgcn_s_memtime();
-          st_sum[2] += st_d - st_c;
-#endif
+          clk.mark(2);
           // ---- COMPUTE
           __builtin_amdgcn_s_setprio(1);
           mma_frags();
           __builtin_amdgcn_s_setprio(0);
           __builtin_amdgcn_sched_barrier(0);
-#ifdef PDMA_STAMPS
-          st_prev = __builtin_amdgcn_s_memtime();
-          st_sum[3] += st_prev - st_d;
-          st_taps += 1;
-#endif
+          clk.mark(3);
+          clk.tick();
           __builtin_amdgcn_s_barrier();
           __builtin_amdgcn_sched_barrier(0);
         }
       } else {
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
-#ifdef PDMA_STAMPS
-        const unsigned long long st_a = __builtin_amdgcn_s_memtime();
-        if (st_prev) st_sum[3] += st_a - st_prev;
-#endif
+        clk.resume(3);
         // W(step) was issued two steps ago; younger: the previous step's [patch DMA] + NDW weight DMAs
         // [+ the NST (+1) output stores of the previous work item's epilogue]
         if (tap == 0 && c == 0 && after_epilogue) {
@@ -529,15 +507,9 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
         } else {
           asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::NDW + 1) : "memory");
         }
-#ifdef PDMA_STAMPS
-        const unsigned long long st_b = __builtin_amdgcn_s_memtime();
-        st_sum[0] += st_b - st_a;
-#endif
+        clk.mark(0);
         __builtin_amdgcn_s_barrier();
-#ifdef PDMA_STAMPS
-        const unsigned long long st_c = __builtin_amdgcn_s_memtime();
-        st_sum[1] += st_c - st_b;
-#endif
+        clk.mark(1);
         // This tap's DMA issues (a patch piece of the next chunk, the weight slab two taps ahead).  The two waves of a SIMD
         // (w, w + 4) issue at opposite ends of the tap -- waves 4-7 here, waves 0-3 behind their MFMAs -- so that one of
         // them has MFMAs to issue while the other sits in its burst (+3..8 % on these layers over all eight behind the
@@ -550,11 +522,8 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
           else dma_w(d_wbase, 0, tap + 2 - 9, (tap + 2) % 3, d_live);
         };
         if (!late_dma) issue_dma();
-#ifdef PDMA_STAMPS
-        st_prev = __builtin_amdgcn_s_memtime();
-        st_sum[2] += st_prev - st_c;
-        st_taps += 1;
-#endif
+        clk.mark(2);
+        clk.tick();
         compute(pbuf, (tap / 3) * C::RS + (tap % 3) * C::PSTR, tap % 3);
         if (late_dma) issue_dma();
       }
@@ -562,9 +531,9 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
       pbuf_i ^= 1;
     }
 
-#ifdef PDMA_STAMPS
-    { const unsigned long long t = __builtin_amdgcn_s_memtime(); if (!PP) st_sum[3] += t - st_prev; st_prev = 0; st_epi -= t; }
-#endif
+    const unsigned long long t_epi = clk.now();
+    if (!PP) clk.add(3, t_epi - clk.last());
+    clk.pause();
     // ---- epilogue: D of 16x16x32: col = lane&15 (pixel), rows (lane>>4)*4 + reg (4 consecutive channels).
     // Buffer stores (out-of-range offset = dropped) so every lane issues exactly NST of them.
     __amdgpu_buffer_rsrc_t drs[2];
@@ -790,18 +759,9 @@ __device__ __forceinline__ void conv3_pdma_body(const IgemmParams& P) {
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, tsum), srs, so, 0, 0);
     }
     after_epilogue = true;
-#ifdef PDMA_STAMPS
-    st_epi += __builtin_amdgcn_s_memtime();
-#endif
+    if (!PP) clk.add(4, clk.now() - t_epi);
   }
-#ifdef PDMA_STAMPS
-  if (P.bn_mean && lane == 0) {
-    unsigned long long* o = (unsigned long long*)P.bn_mean + ((size_t)blockIdx.x * 8 + wave) * 8;
-    o[0] = st_sum[0]; o[1] = st_sum[1]; o[2] = st_sum[2]; o[3] = st_sum[3]; o[4] = st_taps; o[5] = PP ? st_rd : st_epi;
-    o[6] = st_b2;                                    // PP: wait at the barrier that ends COMPUTE
-    o[7] = ((__builtin_amdgcn_s_memtime() - st_t0) << 20) / (__builtin_amdgcn_s_memrealtime() - st_r0 + 1);   // clock / 100 MHz, x 2^20
-  }
-#endif
+  clk.store(STAMP_SINK(P.stamps), 8, clk.ticks());
   if constexpr (PP) { if (!grp) __builtin_amdgcn_s_barrier(); }        // pairs with the stagger barrier of waves 4-7
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // drain the dummy DMAs before the wave ends
 }
@@ -861,7 +821,7 @@ int32_t launch_pdma(const IgemmParams& Pin, int kclass, hipStream_t s, int* stat
   P.zdiv = (P.stats && (n_tiles * P.co_il) % blocks == 0) ? 1 : 0;
   if (P.stats && stat_parts) *stat_parts = P.zdiv ? blocks / P.co_il : (int)n_tiles;
 #ifdef PDMA_STAMPS
-  if (!bnbwd) P.bn_mean = (const float*)g_pdma_debug;
+  P.stamps = g_stamp_sink;
 #endif
   // (one bracket name per body: the lock-step and ping-pong instantiations of conv3_pdma_body<BN> are one kernel family)
   // algorithmic bytes: input + packed weights + output, each once (+ y of the fused BatchNorm-backward form, + the old
@@ -875,10 +835,6 @@ int32_t launch_pdma(const IgemmParams& Pin, int kclass, hipStream_t s, int* stat
 }
 
 }  // namespace
-
-#ifdef PDMA_STAMPS
-void* g_pdma_debug = nullptr;      // set by unet_debug_set_buffer (conv_api.hip); also read by conv3_ws.hip
-#endif
 
 int32_t unet_internal_conv3_pdma(const IgemmParams& P, int kclass, hipStream_t s, int* stat_parts) {
   return P.Cout % 128 == 0 ? launch_pdma<128>(P, kclass, s, stat_parts) : launch_pdma<64>(P, kclass, s, stat_parts);

@@ -289,10 +289,7 @@ __global__ __launch_bounds__(512, 1) void conv3_ws_kernel(const IgemmParams P, i
     const char* pb = smem + cur * C::A_BYTES;
     // 36 (tap, 16-channel group) steps of PXT MFMAs; the pixel fragments of step i+2 are requested before the MFMAs
     // of step i and pinned there (left alone, hipcc requests them one MFMA ahead: the LDS round trip showed)
-#ifndef WS_DEPTH
-#define WS_DEPTH 2
-#endif
-    constexpr int DEPTH = STATS == 2 ? 1 : WS_DEPTH;      // (the masked-gradient form needs the registers for its y values)
+    constexpr int DEPTH = STATS == 2 ? 1 : 2;             // (the masked-gradient form needs the registers for its y values)
     auto frag = [&](int i, int pt) {
       const int tap = i >> 2, kg = i & 3;
       return *reinterpret_cast<const bf16x8*>(pb + boff[pt] + (tap / 3) * C::RS + (tap % 3) * C::PSTR + kg * 32);
@@ -660,13 +657,11 @@ __global__ __launch_bounds__(512, 1) void conv3_ws16_kernel(const IgemmParams P,
   for (int d = 0; d < C::NBUF - 1; ++d)
     if (ALWAYS || t_begin + d < t_end) dma_a(d, t_begin + d < t_end);
   int cur = 0;
-#ifdef PDMA_STAMPS
-  unsigned long long w6_st[6] = {0, 0, 0, 0, 0, 0}, w6_prev = __builtin_amdgcn_s_memtime();
-  const unsigned long long w6_t0 = w6_prev, w6_r0 = __builtin_amdgcn_s_memrealtime();
-#define W6_STAMP(i) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); w6_st[i] += t_ - w6_prev; w6_prev = t_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define W6_STAMP(i)
-#endif
+  // diagnostic build (stamps.h; nothing in the default build): per-wave cycle sums over all tiles.  Laps: 0 the counted
+  // vmcnt wait, 1 the barrier, 2 the top of the tile (DMA / deferred stores / geometry), 3 the MFMA loop, 4 the late
+  // DMA, 5 epilogue + stores.  Every stamp is fenced (mark<true>).
+  StampClock clk;
+  clk.start();
   for (int tile = t_begin; tile < t_end; ++tile) {
     const int k = tile - t_begin;
     const bool next_in_flight = ALWAYS || tile + 1 < t_end;
@@ -682,9 +677,9 @@ __global__ __launch_bounds__(512, 1) void conv3_ws16_kernel(const IgemmParams P,
       if (next_in_flight) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::NDMA) : "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    W6_STAMP(0)
+    clk.mark<true>(0);
     __builtin_amdgcn_s_barrier();
-    W6_STAMP(1)
+    clk.mark<true>(1);
     if (k >= 1) take_slots(k - 1);
     constexpr bool RING2 = !ACC && STATS != 2;
     if constexpr (RING2) {
@@ -732,7 +727,7 @@ __global__ __launch_bounds__(512, 1) void conv3_ws16_kernel(const IgemmParams P,
       }
     }
 
-    W6_STAMP(2)
+    clk.mark<true>(2);
     f32x4 acc[2][4];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
@@ -779,7 +774,7 @@ __global__ __launch_bounds__(512, 1) void conv3_ws16_kernel(const IgemmParams P,
         }
       }
     }
-    W6_STAMP(3)
+    clk.mark<true>(3);
     // the ring slot of the next tile
     {
       const int nxt = (cur + 1) % C::NBUF;
@@ -797,7 +792,7 @@ __global__ __launch_bounds__(512, 1) void conv3_ws16_kernel(const IgemmParams P,
       if (ALWAYS || tile + C::NBUF - 1 < t_end) dma_a((k + C::NBUF - 1) % C::NBUF, tile + C::NBUF - 1 < t_end);
     }
 
-    W6_STAMP(4)
+    clk.mark<true>(4);
     // ---- epilogue: D of 16x16x32: column = lane & 15 (pixel), rows 4 kb + j (channel of the 16-tile).  Exactly NST
     // buffer stores per wave (an OOB offset = dropped).
     float sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f}, qa[4] = {0.f, 0.f, 0.f, 0.f}, qb[4] = {0.f, 0.f, 0.f, 0.f};
@@ -894,16 +889,11 @@ __global__ __launch_bounds__(512, 1) void conv3_ws16_kernel(const IgemmParams P,
         }
       }
     }
-    W6_STAMP(5)
+    clk.mark<true>(5);
   }
-#ifdef PDMA_STAMPS
-  if (STATS != 2 && P.bn_mean && lane == 0) {
-    unsigned long long* o = (unsigned long long*)P.bn_mean + ((size_t)(blockIdx.x & 255) * 8 + wave) * 8;
-    for (int i = 0; i < 6; ++i) o[i] = w6_st[i];
-    o[6] = ((__builtin_amdgcn_s_memtime() - w6_t0) << 20) / (__builtin_amdgcn_s_memrealtime() - w6_r0 + 1);
-    o[7] = (unsigned long long)(t_end - t_begin);
-  }
-#endif
+  // (the masked-gradient form stays unstamped: it has no registers for the sums -- with the write-out the diagnostic
+  //  build spills 44 bytes to scratch, and scratch traffic joins the hand-counted vmcnt stream)
+  if (STATS != 2) clk.store(STAMP_SINK(P.stamps), 8, (unsigned long long)(t_end - t_begin));
   if (defer) {                                   // the last tile's results
 #pragma unroll
     for (int pt = 0; pt < 4; ++pt)
@@ -951,7 +941,7 @@ int32_t unet_internal_conv3_ws(IgemmParams P, int kclass, hipStream_t s, int* st
     const double px = (double)P.N * P.H * P.W;
     alg_bytes = 2.0 * (px * (P.Ctot + P.Cout * (1.0 + (mode == 2 ? 1 : 0) + (P.accumulate ? 1 : 0))) + 9.0 * P.Ctot * P.Cout);
 #ifdef PDMA_STAMPS
-    if (mode != 2) P.bn_mean = (const float*)g_pdma_debug;
+    P.stamps = g_stamp_sink;
 #endif
   } else {                // (ragged frames / offset views: conv3_ws_kernel's per-lane geometry)
     kern = P.accumulate ? conv3_ws_kernel<true, 0>

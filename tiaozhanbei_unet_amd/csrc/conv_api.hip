@@ -257,5 +257,8 @@ extern "C" int32_t unet_convt2x2_dgrad_bnrelu(int32_t dtype, int32_t n, int32_t 
 }
 
 #ifdef PDMA_STAMPS
-extern "C" void unet_debug_set_buffer(void* p) { g_pdma_debug = p; }
+// diagnostic build only (not in unet_hip.h; tools/stamps.py binds it itself): the stamp records of every stamped
+// kernel (stamps.h) go to p, room for `records` records of eight uint64; nullptr switches the write-out off
+StampSink g_stamp_sink = {nullptr, 0};
+extern "C" void unet_debug_set_buffer(void* p, int64_t records) { g_stamp_sink = {(unsigned long long*)p, p ? records : 0}; }
 #endif

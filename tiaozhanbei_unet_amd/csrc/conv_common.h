@@ -2,6 +2,7 @@
 // entry points (conv_api.hip) share: parameter structs, the register-staged tile, the DPP row reduction, the launchers.
 #pragma once
 #include "common.h"
+#include "stamps.h"
 
 struct DView { const char* p; int C, H, W, oy, ox; };
 struct DViewW { char* p; int C, H, W, oy, ox; };
@@ -36,6 +37,9 @@ struct IgemmParams {
                     // run-time value on purpose: as a constant, hipcc gives conv3_pdma64x2_kernel 181 instead of 177 VGPRs)
   int pdma_dense;   // conv3_pdma: every destination view covers the frame at offset 0 (scalar output addressing)
   int pdma_dense_src; // conv3_pdma: every source view covers the frame at offset 0, one channel stride (scalar patch addressing)
+#ifdef PDMA_STAMPS
+  StampSink stamps;   // diagnostic build only, last: where conv3_pdma_body / conv3_ws16_kernel write their stamp records
+#endif
 };
 
 struct ConvTParams {
@@ -92,7 +96,3 @@ int32_t unet_internal_conv3_ws(IgemmParams P, int kclass, hipStream_t s, int* st
 // convt_ws.hip: c_in = 128 / 256 (forward), c_out = 64 / 128 (data gradient)
 int32_t unet_internal_convt_ws(int c_in, ConvTParams P, hipStream_t s);
 int32_t unet_internal_convt_dgrad_ws(int c_out, ConvTParams P, hipStream_t s, int* n_parts = nullptr);
-
-#ifdef PDMA_STAMPS
-extern void* g_pdma_debug;         // stamp buffer of the diagnostic build (defined in conv3_pdma.hip)
-#endif

@@ -17,16 +17,14 @@
 #include <algorithm>
 
 #include "common.h"
+#include "stamps.h"
 
 namespace {
 
 struct WView { const char* p; int C, H, W, oy, ox; };
 
-#ifdef PDMA_STAMPS
-void* g_wgrad_debug = nullptr;   // diagnostic build only (unet_debug_set_buffer_wgrad)
-#endif
 struct WgradParams {
-  void* debug;     // diagnostic build: s_memtime sums per wave (tools/wgrad_stamps.py); nullptr otherwise
+  void* debug;     // diagnostic build: the stamp records (stamps.h, tools/stamps.py); nullptr otherwise
   WView rt;        // row tensor, geometry = frame
   WView ct[2];     // column tensor(s); channel tile below ct[0].C reads ct[0], else ct[1]
   int N, H, W;     // frame (pixel grid of the row tensor)
@@ -34,6 +32,10 @@ struct WgradParams {
   float* partial;  // [split][TAPS][Crow][Ccol]
   int split, tilesPerSplit, tilesX, tilesY, nR, nC;
   int xcd_chunk;   // > 0: XCD-aware block order (wgrad_block_coords), blocks per XCD; 0: plain order
+#ifdef PDMA_STAMPS
+  long long debug_records;   // diagnostic build only, last: the room at `debug`, in records
+  __device__ StampSink stamps() const { return {(unsigned long long*)debug, debug_records}; }
+#endif
 };
 
 // Block -> (split, row tile, column tile).  Workgroups go round-robin over the 8 XCDs (blockIdx % 8), each with its own
@@ -289,12 +291,9 @@ __device__ inline bf16x8 tr_frag2(const char* base, int off0, int off1) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
-#ifdef PDMA_STAMPS
-#define WG_STAMP(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); wg_st[i] += t_ - wg_prev; wg_prev = t_; }
-#else
-#define WG_STAMP(i)
-#endif
-
+// The stamp laps of wgrad_dma_kernel and wgrad16_kernel (diagnostic build, stamps.h; nothing in the default build),
+// per-wave cycle sums over all tiles: 0 the vmcnt(0) wait, 1 the barrier, 2 DMA issue, 3 fragment reads + MFMAs;
+// wgrad16_kernel also 4 the partial-slab stores, drained, and 5 the kernel body.
 __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(const WgradParams P) {
   using C = WDma;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -388,20 +387,18 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(const WgradParams P) 
   const int t_begin = sp * P.tilesPerSplit;
   const int t_end = min(t_begin + P.tilesPerSplit, ntiles);
 
-#ifdef PDMA_STAMPS
-  unsigned long long wg_st[4] = {0, 0, 0, 0}, wg_prev = __builtin_amdgcn_s_memtime();
-  const unsigned long long wg_t0 = wg_prev, wg_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  StampClock clk;
+  clk.start();
   if (t_begin < t_end) dma(t_begin, 0);
   for (int tile = t_begin; tile < t_end; ++tile) {
     const int buf = (tile - t_begin) & 1;
-    WG_STAMP(3)
+    clk.mark(3);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's share of tile `tile` has landed
-    WG_STAMP(0)
+    clk.mark(0);
     __builtin_amdgcn_s_barrier();                               // ... everyone's has; buffer buf^1 is free
-    WG_STAMP(1)
+    clk.mark(1);
     if (tile + 1 < t_end) dma(tile + 1, buf ^ 1);
-    WG_STAMP(2)
+    clk.mark(2);
     const char* sR = smem + buf * C::BUF;
     const char* sC = sR + C::R_BYTES;
     // the X fragment of (tile row ty, tap row r, tap column s) is the fragment of (ty+1, r-1, s): keep the
@@ -429,15 +426,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(const WgradParams P) 
     }
   }
 
-#ifdef PDMA_STAMPS
-  WG_STAMP(3)
-  if (P.debug && lane == 0 && blockIdx.x < 512) {
-    unsigned long long* o = (unsigned long long*)P.debug + ((size_t)blockIdx.x * 4 + wave) * 8;
-    for (int i = 0; i < 4; ++i) o[i] = wg_st[i];
-    o[4] = (unsigned long long)(t_end - t_begin);
-    o[5] = ((__builtin_amdgcn_s_memtime() - wg_t0) << 20) / (__builtin_amdgcn_s_memrealtime() - wg_r0 + 1);
-  }
-#endif
+  clk.mark(3);
+  clk.store(STAMP_SINK(P.stamps()), 4, (unsigned long long)(t_end - t_begin));
   const int col = ctile * 64 + wc * 32 + l31;
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
@@ -554,12 +544,9 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
   // The two waves of a SIMD (w, w + 4) issue their pieces at opposite ends of a tile (see the loop): the EARLY waves
   // (4-7) before their MFMAs -- which they therefore start late -- the LATE waves (0-3) after theirs.  The early waves
   // take fewer pieces (NE each, from the end of the list), so that both waves of a SIMD reach the end of the tile
-  // together (W16_NE: stamped / timed at 4, 5, 6, 8)
-#ifndef W16_NE
-#define W16_NE 8
-#endif
+  // together (stamped / timed at NE = 4, 5, 6, 8: profiles/r03_experiments.txt)
   constexpr int NT = 2 * C::R_INSTR + C::C_INSTR;              // pieces per tile: 62 (wide), 68 (paired)
-  constexpr int NE = W16_NE;
+  constexpr int NE = 8;
   constexpr int NLATE = (NT - 4 * NE + 3) / 4;
   // (measured: the waves that compute FIRST must be the ones that win the SIMD's issue arbitration -- the older waves
   //  0-3; the roles swapped, or the early waves raised with s_setprio, cost 8-13 %)
@@ -645,26 +632,25 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
   const int t_begin = sp * P.tilesPerSplit;
   const int t_end = min(t_begin + P.tilesPerSplit, ntiles);
 
-#ifdef PDMA_STAMPS
-  unsigned long long wg_st[4] = {0, 0, 0, 0}, wg_prev = __builtin_amdgcn_s_memtime();
-  const unsigned long long wg_t0 = wg_prev, wg_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  StampClock clk;
+  clk.start();
+  const unsigned long long t_body = clk.last();
   if (t_begin < t_end) dma(0);
   for (int tile = t_begin; tile < t_end; ++tile) {
     const int buf = (tile - t_begin) & 1;
-    WG_STAMP(3)
+    clk.mark(3);
     next_tile();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's share of tile `tile` has landed
-    WG_STAMP(0)
+    clk.mark(0);
     __builtin_amdgcn_s_barrier();                               // ... everyone's has; buffer buf^1 is free
-    WG_STAMP(1)
+    clk.mark(1);
     // The next tile's DMAs: a wave in its burst of 8-10 one-KiB issues (140-250 cycles EACH beside the partner's MFMAs
     // and fragment reads, stamped) feeds no MFMAs.  The two waves of a SIMD (w, w + 4) therefore issue at opposite ends
     // of a tile -- the X waves right here, before their MFMAs, the dY waves after theirs -- so that one of the two
     // always has MFMAs to issue (stamps: the earlier the dY waves issued, the more the two bursts overlapped).
     const bool more = tile + 1 < t_end;
 #ifndef W16_NO_DMA
-    if (more && !late_wave) { dma(buf ^ 1); WG_STAMP(2) }
+    if (more && !late_wave) { dma(buf ^ 1); clk.mark(2); }
 #endif
     const char* sb = smem;                                      // (a_off / b_off carry the buffer's offset)
     auto ldA = [&](int ty, int cb) {
@@ -731,7 +717,7 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
       }
     }
 #ifndef W16_NO_DMA
-    if (more && late_wave) { WG_STAMP(3) dma(buf ^ 1); WG_STAMP(2) }
+    if (more && late_wave) { clk.mark(3); dma(buf ^ 1); clk.mark(2); }
 #endif
     // the fragment addresses move to the other buffer IN PLACE (a second set of registers does not fit beside 200
     // accumulator / fragment registers)
@@ -750,10 +736,8 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
     }
   }
 
-#ifdef PDMA_STAMPS
-  WG_STAMP(3)
-  const unsigned long long wg_e0 = __builtin_amdgcn_s_memtime();
-#endif
+  clk.mark(3);
+  const unsigned long long t_stores = clk.now();
   // ---- partial slab [tap][dY channel][X channel].  The MFMAs ran with A = X, B = dY: D rows (lane >> 4) * 4 + reg = 4
   // CONSECUTIVE X channels, column lane & 15 = the dY channel -> one 16-byte store per accumulator (36 per lane; with the
   // operands the other way round it took 144 four-byte stores, and the store tail is issue-bound)
@@ -770,16 +754,9 @@ __global__ __launch_bounds__(512, 1) void wgrad16_kernel(const WgradParams P) {
       }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef PDMA_STAMPS
-  if (P.debug && lane == 0 && blockIdx.x < 256) {
-    unsigned long long* o = (unsigned long long*)P.debug + ((size_t)blockIdx.x * 8 + wave) * 8;
-    for (int i = 0; i < 4; ++i) o[i] = wg_st[i];
-    o[4] = (unsigned long long)(t_end - t_begin);
-    o[5] = ((__builtin_amdgcn_s_memtime() - wg_t0) << 20) / (__builtin_amdgcn_s_memrealtime() - wg_r0 + 1);
-    o[6] = __builtin_amdgcn_s_memtime() - wg_e0;               // partial-slab stores, drained
-    o[7] = __builtin_amdgcn_s_memtime() - wg_t0;
-  }
-#endif
+  clk.add(4, clk.now() - t_stores);                            // partial-slab stores, drained
+  clk.add(5, clk.now() - t_body);
+  clk.store(STAMP_SINK(P.stamps()), 8, (unsigned long long)(t_end - t_begin));
 }
 
 // Many splits, few outputs (the 64-channel layers: 512 slabs of 9x64x64): one block per (row, 64 columns,
@@ -947,7 +924,8 @@ extern "C" int32_t unet_conv3x3_wgrad(int32_t dtype, int32_t n, int32_t h, int32
   UNET_REQUIRE(workspace_bytes >= need, UNET_ERR_WORKSPACE, "unet_conv3x3_wgrad: workspace %zu < %zu", workspace_bytes, need);
   WgradParams P{};
 #ifdef PDMA_STAMPS
-  P.debug = g_wgrad_debug;
+  P.debug = g_stamp_sink.p;
+  P.debug_records = g_stamp_sink.records;
 #endif
   P.rt = WView{(const char*)dy, c_out, h, w, 0, 0};
   P.ct[0] = WView{(const char*)src[0].ptr, src[0].c, src[0].h, src[0].w, src[0].off_y, src[0].off_x};
@@ -1248,7 +1226,3 @@ extern "C" int32_t unet_convt2x2_wgrad(int32_t dtype, int32_t n, int32_t h, int3
   // bias gradient: column sums of dy; the partial slabs above are consumed (stream order), reuse them
   return unet_internal_colsum(dtype, dy, (int64_t)n * 4 * h * w, c_out, db, (float*)workspace, workspace_bytes, s);
 }
-
-#ifdef PDMA_STAMPS
-extern "C" void unet_debug_set_buffer_wgrad(void* p) { g_wgrad_debug = p; }
-#endif
